@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the Gaussian-distance hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, `config`, `loss_values` and the step priced against HBM peak).  Everything else the line can carry —
+the second and third timed regions (the other backward form, the other input allocation form), the per-kernel durations from
+event pairs bound to the fused dispatches, the copy ceiling, the rocprofv3 traffic passes, the parity / nms / head stand-ins
+and the CPU baselines — runs only with `--full`, after the headline region, as described below.
+`--dump-outputs DIR` writes what the last timed step returned to its caller, as float .npy files: `loss_<loss>.npy` (the
+three loss values), `grad_pred_<loss>.npy` (the gradient rows of a fixed seeded sample of DUMP_ROWS rows, the same rows for
+every loss) and `grad_pred_rows.npy` (those row indices).  The inputs are seeded, so equal arguments give equal inputs.
 
 Metric (BASELINE.json): M box-pairs/s, forward+backward, for GWD / KLD / BCD at 10 M pairs.
 Workload (BASELINE.json configs[2]): 10 M synthetic anchor x gt pairs per GPU (SURVEY.md §8d recipe,
@@ -19,12 +28,12 @@ asynchronously (the next step's kernels overlap it).  Weak scaling: every rank k
 Launch mode.  N = 1 launches eagerly, and on one MI355X the eager step is the FASTER one: same process, same buffers, round 3
 (profiles/r03_step_variants.jsonl): eager 423-427 us per step, hipGraph replay 430 us around 411 us of fused kernels; the
 host needs ~100 us per step.  (Round 2's eager step cost 434-445 us: its backward added a ones-fill, two adds and three
-early-exit launches.)  Every `--event-every`-th step of the timed region (default 5) carries a HIP event pair on each of
+early-exit launches.)  With --full, every `--event-every`-th step of the timed region (default 5) carries a HIP event pair on each of
 its fused launches (gd3d_loss_fused_timed: hipExtLaunchKernel binds them to the dispatch's begin/end timestamps; no
 marker packets): the kernel durations behind `roofline` are measured INSIDE the region, but not on every launch, because a
 dispatch with events bound to it costs ~5 us of GPU time more than a plain one (profiles/r03_event_every_ab.txt: the step
 runs 28.7 us over the sum of its three fused kernels with events on every launch, 14-16 us over it with every fifth step or
-none timed; round 2 timed every launch and so taxed its own `value` by 3.5 %).
+none timed; round 2 timed every launch and so taxed its own `value` by 3.5 %).  A plain run binds no events in its region.
 N > 1 launches eagerly too since round 5: with the plain-backward step and the per-step collective in the loop the eager step is
 the faster one (one rank under torch.distributed.run, RCCL all_gather per step, profiles/r05_rccl_rehearsal_*.json: 439.6 us per
 step eager, 443.6 / 444.9 us as a hipGraph replay, against 416.5 us for the N = 1 step without a collective; rounds 3-4, whose
@@ -46,7 +55,7 @@ per-step asynchronous gather of the three shard losses, MAX-reduce of the elapse
 tensors through GDLoss's `_cpu` twins (tests/test_bench_rehearsal.py); the line then says "device": "cpu" in `config` and
 carries no roofline claim.
 
-The JSON line also carries
+The JSON line also carries (only with --full, except value_form and roofline's step figures)
   value_form   : which step `value` times (plain backward unless --unit-grad) and how the inputs are allocated.
   value_unit_grad, roofline.frac_step_unit_grad : the step handing the library's unit gradient to torch.autograd.backward
                  (no ones-fill, no early-exit launches), timed over a second, shorter region right after the main one (eager).
@@ -59,7 +68,8 @@ The JSON line also carries
                  (88 B/pair) / average launch duration measured with a HIP event pair bound to
                  every fused dispatch, on the stream it is launched on.  `frac` is that kernel alone;
                  `frac_step` prices the WHOLE timed step the same way (3 x 88 B x pairs / ms_per_step / peak:
-                 SURVEY.md §8d's protocol, reduce launches and the backward call included).
+                 SURVEY.md §8d's protocol, reduce launches and the backward call included).  A plain run carries the
+                 step figures only (`achieved_step`, `frac_step`, `frac_step_moved_bytes`): they need no extra run.
   cpu_baseline : the fp32 C oracle ("port") timed on this host's cores on a bounded sample; beside it `torch_chain` = the
                  reference's OWN PyTorch-CPU op chain restated op for op (its time is the reference's time on this host; 1 k / 1 M /
                  10 M pairs, 1 thread and all granted cores), `torch_chain_lean` = an entry-form rewrite 2.2-2.6x faster than
@@ -84,6 +94,15 @@ LOSSES = ('gwd3d', 'kld3d', 'bd3d')
 BYTES_PER_PAIR = 88          # read pred 28 + target 28, write loss 4 + grad_pred 28
 MOVED_BYTES_PER_PAIR = 84    # what the kernel moves under reduction='mean': the per-pair loss is summed, not stored
 HBM_PEAK_GBPS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achievable)
+DUMP_ROWS = 1 << 18          # --dump-outputs: gradient rows sampled per loss (3 x 7.3 MB of float32 at most)
+DUMP_SEED = 0
+# keys of the result line that only a --full run measures (the second and third regions)
+FULL_ONLY_KEYS = ('value_plain_backward', 'ms_per_step_plain_backward', 'plain_backward_steps', 'value_unit_grad',
+                  'ms_per_step_unit_grad', 'unit_grad_steps', 'value_separate_inputs', 'ms_per_step_separate_inputs',
+                  'value_one_allocation', 'ms_per_step_one_allocation')
+# roofline figures of a plain run: the timed step priced against HBM peak (no per-kernel timing, probe or counters)
+PLAIN_ROOFLINE_KEYS = ('bound', 'peak', 'unit', 'achieved_step', 'frac_step', 'frac_step_moved_bytes', 'bytes_per_pair',
+                       'moved_bytes_per_pair')
 
 
 def synthetic_pairs(n, seed, device):
@@ -95,6 +114,16 @@ def synthetic_pairs(n, seed, device):
     tgt = torch.rand(n, 7, generator=g, device=device) * (hi - lo) + lo
     pred = tgt + torch.randn(n, 7, generator=g, device=device) * sigma
     return pred.float().contiguous(), tgt.float().contiguous()
+
+
+def write_outputs(path, arrays):
+    """`--dump-outputs`: every array as <path>/<name>.npy, in float32 (float64 kept as it is)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def shard_rows(pairs, rank, world, strong):
@@ -410,7 +439,13 @@ def main():
     ap.add_argument('--strong', action='store_true',
                     help='strong scaling: --pairs is the TOTAL, split into contiguous row ranges over the ranks '
                          '(SURVEY.md §8e; default is weak scaling, --pairs per GPU)')
-    ap.add_argument('--cpu-sample', type=int, default=10_000_000, help='pairs in the CPU baseline sample (0 = skip)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline region, measure everything else the line can carry: the second and third regions, '
+                         'per-kernel event timings, copy ceiling, traffic passes, stand-ins and CPU baselines (a plain run only '
+                         'sets up, warms up, times the K steps and prints the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's losses and a fixed seeded sample of its gradient rows to DIR/<name>.npy")
+    ap.add_argument('--cpu-sample', type=int, default=10_000_000, help='pairs in the CPU baseline sample (--full; 0 = skip)')
     ap.add_argument('--prewarm', type=float, default=1.0,
                     help='seconds of untimed steps before the W warmup steps (clock ramp of a cold GPU; 0 = off)')
     ap.add_argument('--graph', action='store_true', help='replay a hipGraph of the step (4-20 us per step slower than eager launches for the plain-backward step, with or without the collective)')
@@ -423,24 +458,26 @@ def main():
                          'memory system, DESIGN.md 5.3); by default that form is timed in the third region and reported as '
                          '`value_one_allocation`')
     ap.add_argument('--no-standins', action='store_true',
-                    help='skip the parity / nms / head keys (bench_standins.py: ~10 s after the timed regions, N = 1 only)')
+                    help='--full: skip the parity / nms / head keys (bench_standins.py: ~10 s after the timed regions, N = 1 only)')
     ap.add_argument('--unit-grad', action='store_true',
                     help="main region = rounds 3-4's step: one torch.autograd.backward over the three losses with the library's unit "
                          'gradient (gd_loss.unit_grad) instead of the plain (l0 + l1 + l2).backward() every reference caller runs')
     ap.add_argument('--sum-backward', action='store_true', help=argparse.SUPPRESS)   # the default since round 5
     ap.add_argument('--event-every', type=int, default=5,
-                    help='eager launches: bind a HIP event pair to the fused dispatches of every N-th step of the timed region '
+                    help='--full, eager launches: bind a HIP event pair to the fused dispatches of every N-th step of the timed region '
                          '(1 = every step as in round 2, which costs ~5 us of GPU time per timed launch; 0 = none in the '
                          'region, the kernel durations then come from an eager pass right after it)')
     ap.add_argument('--no-traffic', action='store_true',
-                    help='skip the two rocprofv3 --pmc passes that count HBM bytes per launch (roofline.traffic; N = 1 only, ~40 s)')
+                    help='--full: skip the two rocprofv3 --pmc passes that count HBM bytes per launch (roofline.traffic; N = 1 only, ~40 s)')
     ap.add_argument('--device', choices=('cuda', 'cpu'), default='cuda',
                     help="cpu: rehearse the rank loop on CPU tensors through GDLoss's _cpu twins (no roofline claim)")
     ap.add_argument('--backend', choices=('nccl', 'gloo'), default=None, help='torch.distributed backend (default: nccl = RCCL on cuda, gloo on cpu)')
     ap.add_argument('--plain-steps', type=int, default=-1,
-                    help='steps of the second region that ends in a plain (l0+l1+l2).backward() (default: half of --steps, at least 10; 0 = skip)')
+                    help='--full: steps of the second region, which runs the other backward form (default: half of --steps, at least 10; 0 = skip)')
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     for k, v in RCCL_ENV_DEFAULTS.items():   # before anything touches the GPU, on every launch path
         os.environ.setdefault(k, v)
     args.separate_inputs = not args.arena
@@ -604,10 +641,9 @@ def main():
             # the collective reads its input on RCCL's stream while the next replay may already run: give it a private
             # copy of the graph's static output (12 bytes) instead of the buffer the next replay writes
             outs = graph_outs.clone() if use_dist else graph_outs
+        last['outs'] = outs
         if use_dist:  # one tiny collective per step: (3,) shard losses -> (world, 3)
             last['pending'] = amd.sharded.gather_shard_losses(outs, async_op=True)
-        else:
-            last['outs'] = outs
 
     def sync_all():
         device_sync()
@@ -624,7 +660,7 @@ def main():
     # more than a plain one on this ROCm (round 3: the same eager step ran 13.7 us over the sum of its three fused kernels
     # without events, tools/step_variants.py, and 28.7 us over it with events on every launch), so timing EVERY launch in
     # the region taxes `value` by 3.5 %; every fifth step keeps the durations in-region and the tax under 1 %.
-    every = max(args.event_every, 0) if on_gpu else 0
+    every = max(args.event_every, 0) if (on_gpu and args.full) else 0
     tick = [0]
 
     def sampled():
@@ -639,7 +675,7 @@ def main():
     import gc
     gc.collect()
     gc.disable()
-    if on_gpu:
+    if on_gpu and args.full:
         # the torch kernels the parity sample takes right after the main region (arange, index_select): first use loads their code
         # objects — tens of ms of host time during which the GPU would idle and drop its clocks in front of the second region
         _w = torch.arange(0, 64, 2, device=dev)
@@ -650,11 +686,11 @@ def main():
     # steps it idles the GPU, the clocks drop, and that region and the next run 10-20 % slow (0.46-0.49 ms per step instead of 0.41).
     alt = None
     if graph is None:
-        for form in (not main_plain, main_plain):
+        for form in ((not main_plain, main_plain) if args.full else (main_plain,)):   # a plain run times one form only
             for _ in range(2):
                 step(False, plain=form)
         device_sync()
-        alt = make_alt()
+        alt = make_alt() if args.full else None
         if alt is not None:   # one step on the other allocation form's arrays too: its gradient buffers exist before the clocks ramp
             held0 = (cur['tgt'], dict(preds))   # (AFTER the main form's first steps: the bench's extra arrays must not change what the
             cur['tgt'] = alt[0]                 #  headline form's own allocations draw)
@@ -719,16 +755,28 @@ def main():
         device_sync()
         return tt.item()
     elapsed = max_over_ranks(elapsed)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, taken now (later regions write the gradient buffers again): the three
+        # loss values and the gradient rows of a fixed seeded sample (the whole gradient is 3 x 28 B x pairs)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, DUMP_ROWS), replace=False))
+        rows_dev = torch.from_numpy(rows).to(dev)
+        dump = {'grad_pred_rows': rows.astype(np.float64)}
+        for k, lt in enumerate(LOSSES):
+            if preds[lt].grad is None:
+                raise SystemExit(f'--dump-outputs: the last timed step left no gradient for {lt}')
+            dump[f'loss_{lt}'] = last['outs'][k].detach().clone()
+            dump[f'grad_pred_{lt}'] = preds[lt].grad.index_select(0, rows_dev)
     # rows of the gradients the LAST TIMED STEP left in HBM, for the parity key (bench_standins.parity): taken now, before the
     # later regions and the copy probe write those buffers again
     grad_rows = None
-    if on_gpu and rank == 0 and world == 1 and not args.no_standins and not args.strong and n > 0:
+    if on_gpu and args.full and rank == 0 and world == 1 and not args.no_standins and not args.strong and n > 0:
         sample_idx = torch.arange(0, n, max(1, n // 200_000), device=dev)
         grad_rows = {lt: preds[lt].grad.index_select(0, sample_idx) for lt in LOSSES}
     timing = (f'HIP event pair bound to the fused dispatches of every {every}-th step inside the timed region '
               '(hipExtLaunchKernel start/stop events: begin/end timestamps of the dispatch itself, no marker packets)')
     replay_ms = None
-    if on_gpu and graph is None and not any(events[lt] for lt in LOSSES):   # --event-every 0: an eager pass right after the region
+    if on_gpu and args.full and graph is None and not any(events[lt] for lt in LOSSES):   # --event-every 0: an eager pass right after the region
         for it in range(25):
             compute(True)
             if it == 4:
@@ -738,7 +786,7 @@ def main():
         torch.cuda.synchronize(dev)
         timing = ('HIP event pair bound to every fused dispatch (hipExtLaunchKernel start/stop events), eager pass of 20 steps run '
                   'right after the timed region (which carried no events)')
-    if graph is not None:  # events cannot be bound inside a captured graph on ROCm: eager pass right after
+    if graph is not None and args.full:  # events cannot be bound inside a captured graph on ROCm: eager pass right after
         for it in range(25):
             compute(True)
             if it == 4:   # the first passes re-warm the eager path (event creation, allocator); keep the last 20
@@ -766,7 +814,7 @@ def main():
     # Second, shorter region: the same step ending in a plain `(l0 + l1 + l2).backward()` — what every reference caller does
     # (mmcv's OptimizerHook, set up from tools/train.py:213-220).  Eager launches only (a captured graph would need its own
     # capture of the other backward); same barrier + synchronize brackets and MAX over ranks as the main region.
-    plain_steps = args.plain_steps if args.plain_steps >= 0 else max(10, args.steps // 2)
+    plain_steps = (args.plain_steps if args.plain_steps >= 0 else max(10, args.steps // 2)) if args.full else 0
     plain_elapsed = None      # elapsed time of the second region, which runs the OTHER backward form than the main region
     if graph is None and plain_steps > 0:
         for _ in range(5):
@@ -844,7 +892,7 @@ def main():
     # (measured on every loss's own buffer triple: which three buffers are combined moves both the kernel and the probe by
     #  up to 5 %, DESIGN.md §5.3, so the ceiling that belongs to the dominant kernel is the one of ITS buffers)
     probe_by_loss = {}
-    if rank == 0 and on_gpu and n > 0 and (7 * n) % 4 == 0:
+    if rank == 0 and on_gpu and args.full and n > 0 and (7 * n) % 4 == 0:
         lib = amd.load_library()
         stream = torch.cuda.current_stream().cuda_stream
         for lt in LOSSES:
@@ -873,10 +921,10 @@ def main():
         moved = MOVED_BYTES_PER_PAIR * n / dom_s / 1e9 if dom_s > 0 else 0.0
         ceiling = MOVED_BYTES_PER_PAIR * n / (probe_ms * 1e-3) / 1e9 if probe_ms else None
         traffic, traffic_by_loss, traffic_note = None, {}, None
-        if world == 1 and on_gpu and not args.no_traffic and not args.strong:
+        if args.full and world == 1 and on_gpu and not args.no_traffic and not args.strong:
             traffic_by_loss, traffic_note = measure_traffic(n)
             traffic = traffic_by_loss.get(dom)
-        if traffic is None and on_gpu:   # the counters could not be collected here: fall back to the committed collection, and say so
+        if args.full and traffic is None and on_gpu:   # the counters could not be collected here: fall back to the committed collection, and say so
             why = traffic_note if (world == 1 and on_gpu and not args.no_traffic) else 'not collected in this run (--no-traffic, --device cpu or N > 1)'
             tpath = os.path.join(ROOT, 'profiles', 'traffic.json')
             if os.path.isfile(tpath):
@@ -984,6 +1032,13 @@ def main():
         }
         if not on_gpu:   # a rehearsal of the rank loop on host memory: no roofline claim
             line['roofline'] = None
+        if not args.full:   # a plain run reports what its one region measured, nothing the other regions or probes would have
+            for key in FULL_ONLY_KEYS:
+                del line[key]
+            for key in ('per_rank_kernel_ms', 'graph_replay_ms_per_step'):
+                del line['config'][key]
+            if line['roofline'] is not None:
+                line['roofline'] = {k: line['roofline'][k] for k in PLAIN_ROOFLINE_KEYS}
         if grad_rows is not None:
             # SURVEY.md §8d "plus max-abs-error vs oracle" and BASELINE.md's NMS boxes/s, and the other BASELINE configs' stand-ins:
             # after the timed regions, outside them (bench_standins.py)
@@ -996,8 +1051,10 @@ def main():
                 except Exception as e:  # noqa: BLE001 — a failed stand-in must not cost the headline line; it is reported as failed
                     line[key] = {'error': f'{type(e).__name__}: {str(e)[:200]}'}
             line['standins_s'] = round(time.perf_counter() - t_st, 2)
-        if args.cpu_sample > 0 and world == 1:   # reported baseline: rank 0 at N = 1 only
+        if args.full and args.cpu_sample > 0 and world == 1:   # reported baseline: rank 0 at N = 1 only
             line['cpu_baseline'] = cpu_baseline(args.cpu_sample, seed=0)
+        if dump is not None:
+            write_outputs(args.dump_outputs, dump)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(line) + '\n').encode())
     if use_dist:

@@ -10,7 +10,7 @@ set -u
 export TMPDIR=/tmp
 OUT=gpurun_out/${1:-acc_ab}
 mkdir -p $OUT
-B="python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-sample 0 --no-traffic --no-standins"
+B="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --cpu-sample 0 --no-traffic --no-standins"
 FORMS="all small"
 for v in tools/variants/libgd3d_s*.so; do [ -f $v ] && FORMS="$FORMS $(basename $v .so | sed s/libgd3d_//)"; done
 run() {   # $1 form, rest: command

@@ -7,7 +7,7 @@ set -u
 export TMPDIR=/tmp
 OUT=gpurun_out/$1; shift
 mkdir -p $OUT
-B="python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-sample 0 --no-traffic --no-standins"
+B="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --cpu-sample 0 --no-traffic --no-standins"
 for v in "$@"; do
   GD3D_LIB=tools/variants/libgd3d_$v.so GD3D_HOST=python python3 -m pytest tests/test_gpu_gd_loss.py -m gpu -x -q -k "golden or ragged or determinism or full_size or unaligned" > $OUT/pytest_$v.log 2>&1
   echo "$v: $(tail -1 $OUT/pytest_$v.log)"
