@@ -325,7 +325,7 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    override = os.environ.get('GD3D_LIB')  # A/B runs of experimental builds (tools/build_variants.py)
+    override = os.environ.get('GD3D_LIB')  # an instrumented build (tools/sanitize.sh and the tests it runs)
     if override:
         _lib = _bind(override)
         return _lib

@@ -41,6 +41,8 @@ EXTRA_SOURCES = {
     'center_targets.hip': ['-ffp-contract=off'],  # gaussian_radius in the reference's fp32 operation order
 }
 EXTRAS_PATH = os.path.join(PKG_DIR, 'libgd3d_extras.so')
+# libgd3d.so exports what include/gd3d.h declares and nothing else (a file of csrc/: part of source_hash())
+VERSION_SCRIPT = os.path.join(CSRC, 'gd3d.map')
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 
 # host translation units (the `_cpu` twins of include/gd3d.h): compiled by the ROCm toolchain's own clang++ as plain C++
@@ -141,7 +143,8 @@ def build(force=False, verbose=False):
     main_objs = [objs[s_] for s_ in list(SOURCES) + list(HOST_SOURCES) if s_ in objs]
     extra_objs = [objs[s_] for s_ in EXTRA_SOURCES if s_ in objs]
     tmp = f'{LIB_PATH}.{os.getpid()}.tmp'
-    cmd = [hipcc, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-pthread', '-o', tmp] + main_objs
+    cmd = [hipcc, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-pthread', '-Wl,--version-script=' + VERSION_SCRIPT, '-o', tmp] + \
+          main_objs
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f'link failed:\n{r.stderr[-4000:]}')

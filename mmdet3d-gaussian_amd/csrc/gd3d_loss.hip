@@ -23,19 +23,16 @@
 //     guarded scalar load/store path around the same compute code.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
-#include <cstdlib>
 
 #include "gd3d_device.h"
 
 namespace gd3d {
 
-#ifndef GD_TILE
-#define GD_TILE 256                  // pairs (= threads) per workgroup; multiples of 256 give whole 1-KiB DMA pieces.
-#endif                               // r01 A/B inside bench.py under rocprofv3 (tools/ab_rocprof.sh): 512 halves the
-                                     // partials (reduce stage 6.9 -> 4.9 us) and is neutral for the fused kernel once
-                                     // it is below ~300 VALU/pair, but gave only +0.5 % step throughput with ~1 us
-                                     // longer event-bracketed kernels (noise level); 1024 is 4 % slower.  256 ships.
-constexpr int TILE = GD_TILE;        // pairs per workgroup
+constexpr int TILE = 256;            // pairs (= threads) per workgroup; multiples of 256 give whole 1-KiB DMA pieces.
+                                     // r01 A/B inside bench.py under rocprofv3: 512 halves the partials (reduce stage
+                                     // 6.9 -> 4.9 us) and is neutral for the fused kernel once it is below ~300 VALU/pair,
+                                     // but gave only +0.5 % step throughput with ~1 us longer event-bracketed kernels
+                                     // (noise level); 1024 is 4 % slower.  256 ships.
 constexpr int TILE_F = TILE * 7;     // floats per tensor tile (1792)
 constexpr int TILE_V4 = TILE_F / 4;  // 16-byte vectors per tensor tile (448)
 constexpr int NPIECE = TILE_F / 256; // 1-KiB LDS-DMA pieces per tensor tile (7)
@@ -45,52 +42,32 @@ constexpr int HEAD_T = 256;          // threads per workgroup of the head-level 
 typedef __attribute__((address_space(3))) void lds_ptr_t;
 typedef const __attribute__((address_space(1))) void gbl_cptr_t;
 
-// ---- tuning switches (A/B-tested with tools/build_variants.py + tools/kernel_time.py) ----
-#ifndef GD_NT_LOAD
-#define GD_NT_LOAD 1   // LDS-DMA loads with the nt cache policy: every input byte is read exactly once
-                       // (measured r01, 10 M pairs: nt loads + nt stores 129 us vs 151 us plain; a persistent
-                       //  double-buffered grid-stride variant was 143-160 us and was dropped)
-#endif
+// LDS-DMA loads with the nt cache policy: every input byte is read exactly once (measured r01, 10 M pairs: nt loads + nt
+// stores 129 us vs 151 us plain; a persistent double-buffered grid-stride variant was 143-160 us and was dropped, see
+// DESIGN.md)
+constexpr int DMA_AUX = 2;
 // Occupancy cap.  The fused launch requests AT LEAST this much dynamic LDS, i.e. floor(160 KiB / bytes) workgroups per CU
-// instead of the 8 that its own 14.4 KiB would admit: fewer tiles in flight per CU stream better (tools/hbm_probe2, the
-// kernel's data path without its math: 8 WG/CU 131.0 us, 6: 130.2, 5: 126.7, 4: 126.8, 3: 162; flat copy 127.5), but
-// fewer waves hide less VALU latency, so the best cap depends on the loss.  Measured per loss at FIXED buffer placement
-// (tools/lds_fixed_placement.py, profiles/r02_lds_fixed_placement.txt; 10 M pairs, us per launch, good / bad placement):
+// instead of the 8 that its own 14.4 KiB would admit: fewer tiles in flight per CU stream better (the kernel's data path
+// without its math: 8 WG/CU 131.0 us, 6: 130.2, 5: 126.7, 4: 126.8, 3: 162; flat copy 127.5), but fewer waves hide less
+// VALU latency, so the best cap depends on the loss.  Measured per loss at FIXED buffer placement
+// (profiles/r02_lds_fixed_placement.txt; 10 M pairs, us per launch, good / bad placement):
 //   WG/CU   gwd3d (217 VALU/pair)   kld3d (270)      bd3d (296)
 //     8     134.1 / 137.6           134.2 / 139.5    134.5 / 139.1
 //     7     133.1 / 137.1           131.2 / 138.8    133.0 / 138.3
 //     6     131.7 / 136.4           129.6 / 138.0    130.1 / 137.6
 //     5     131.4 / 134.7           135.8 / 137.6    140.0 / 140.9
 //     4     132.2 / 134.6           136.0 / 136.8    139.9 / 140.3
-#ifndef GD_MIN_LDS
-#define GD_MIN_LDS 27300      // 6 workgroups per CU
-#endif
-#ifndef GD_MIN_LDS_GWD
-#define GD_MIN_LDS_GWD 32768  // 5
-#endif
-#ifndef GD_MIN_LDS_W7
-#define GD_MIN_LDS_W7 32768   // 5, launches with (N,7) weights (any loss)
-#endif
-#ifndef GD_MIN_LDS_KLD
-#define GD_MIN_LDS_KLD GD_MIN_LDS
-#endif
-#ifndef GD_MIN_LDS_BD
-#define GD_MIN_LDS_BD GD_MIN_LDS
-#endif
-#ifndef GD_PLAIN_ALL
-#define GD_PLAIN_ALL 0   // 1: the option-free instantiation for every loss type (gwd3d has it regardless), see launch_one
-#endif
-#ifndef GD_NT_STORE
-#define GD_NT_STORE 1  // nontemporal 16-B gradient stores: written once, never re-read by this kernel
-#endif
-constexpr int DMA_AUX = GD_NT_LOAD ? 2 : 0;
+constexpr int MIN_LDS = 27300;         // 6 workgroups per CU
+constexpr int MIN_LDS_GWD = 32768;     // 5
+constexpr int MIN_LDS_W7 = 32768;      // 5, launches with (N,7) weights (any loss)
+constexpr int MIN_LDS_KLD = MIN_LDS;
+constexpr int MIN_LDS_BD = MIN_LDS;
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 GD_DEV void store_v4(float* dst, const float* src_lds, int idx) {
   const v4f v = reinterpret_cast<const v4f*>(src_lds)[idx];
-  if (GD_NT_STORE) __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(dst) + idx);
-  else reinterpret_cast<v4f*>(dst)[idx] = v;
+  __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(dst) + idx);   // written once, never re-read by this kernel
 }
 
 // 14 LDS-DMA pieces of 1 KiB bring one 256-pair tile of pred and target into LDS; wave w issues pieces w, w+4, w+8, w+12.
@@ -314,17 +291,7 @@ __global__ __launch_bounds__(TILE) void fused_kernel(const LossArgs a_in) {
       alt = fmaf(pv[k], wk, alt);
     }
   }
-#ifdef GD_FAKE_MATH   // experiment builds only: the tile mechanics without the closed forms (what is the floor of this kernel shape?)
-  float L = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    g1[k] = f * (pv[k] - tv[k]);
-    g2[k] = -g1[k];
-    L = fmaf(g1[k], g1[k], L);
-  }
-#else
   const float L = pair_loss<LOSS, FUN, FLAG, GT>(pv, tv, c, a.alpha, a.ia2, a.tau, f, g1, g2);
-#endif
   const float fl = valid ? f * L : 0.0f;
   if (a.pro != GD3D_PRO_NONE) {
     encode_grad(g1, Jp, a.pro == GD3D_PRO_ANCHOR_DELTA);
@@ -1080,7 +1047,7 @@ __global__ __launch_bounds__(FINISH_T) void grad_finish_kernel(const FinishArgs 
 
 // HBM ceiling probe for the access mix of the fused kernel: c = a + b over float4 vectors, nontemporal loads and
 // stores, one vector per thread, full grid of 64-THREAD workgroups — the fastest and the most repeatable of the shapes
-// tools/hbm_probe2.hip measures (126.1-129 us over five processes for 3 x 280 MB; 256-thread workgroups: 126.8-133).
+// a stand-alone probe measured (126.1-129 us over five processes for 3 x 280 MB; 256-thread workgroups: 126.8-133).
 // bench.py runs it on the fused kernel's OWN three buffers right after the timed region, so that
 // `roofline.copy_ceiling_GBps` is the ceiling of that box and of that buffer placement.
 constexpr int PROBE_T = 64;
@@ -1103,27 +1070,20 @@ struct Geometry {
 template <int LOSS, int FUN, bool FLAG, bool GT>
 static void launch_one(const Geometry& g, hipStream_t s, const LossArgs& a) {
   size_t lds = (size_t)(2 * TILE_F + 32 + (a.w7 != nullptr ? TILE_F : 0)) * sizeof(float);
-  constexpr int min_lds = LOSS == GD3D_GWD3D ? GD_MIN_LDS_GWD : (LOSS == GD3D_KLD3D ? GD_MIN_LDS_KLD :
-                          (LOSS == GD3D_BD3D ? GD_MIN_LDS_BD : GD_MIN_LDS));
-  if (lds < (size_t)min_lds) lds = (size_t)min_lds;   // occupancy cap (see GD_MIN_LDS above)
+  constexpr int min_lds = LOSS == GD3D_GWD3D ? MIN_LDS_GWD : (LOSS == GD3D_KLD3D ? MIN_LDS_KLD :
+                          (LOSS == GD3D_BD3D ? MIN_LDS_BD : MIN_LDS));
+  if (lds < (size_t)min_lds) lds = (size_t)min_lds;   // occupancy cap (see MIN_LDS above)
   // with (N,7) weights a workgroup keeps three tiles in flight: 5 per CU for every loss (10 M pairs, fixed placement,
   // 7/6/5/4/3 per CU: kld3d 185.5/185.4/179.8/180.9/202.7 us, bd3d 185.8/184.7/178.0/177.9/204.9, gwd3d 185.0/185.2/182.3/182.7/201.4)
-  if (a.w7 != nullptr && lds < (size_t)GD_MIN_LDS_W7) lds = (size_t)GD_MIN_LDS_W7;
-#ifdef GD_LDS_ENV   // experiment builds only (tools/lds_fixed_placement.py): the cap is re-read from the environment per launch
-  if (const char* e = getenv("GD3D_MIN_LDS")) {
-    const size_t base = (size_t)(2 * TILE_F + 32 + (a.w7 != nullptr ? TILE_F : 0)) * sizeof(float);
-    const size_t want = (size_t)atoi(e);
-    lds = want > base ? want : base;
-  }
-#endif
+  if (a.w7 != nullptr && lds < (size_t)MIN_LDS_W7) lds = (size_t)MIN_LDS_W7;
   // The option-free instantiation, for calls that use none of the options — built and used for gwd3d only, without a
-  // target gradient.  Same buffers, 4 sets, us per 10 M pairs against the general instantiation (tools/variant_probe.py,
-  // profiles/r02_plain_and_dma_issue_ab.txt): gwd3d -2.5 -0.7 -1.8 -0.5 (issue units per wave 424 -> 340), but kld3d
+  // target gradient.  Same buffers, 4 sets, us per 10 M pairs against the general instantiation
+  // (profiles/r02_plain_and_dma_issue_ab.txt): gwd3d -2.5 -0.7 -1.8 -0.5 (issue units per wave 424 -> 340), but kld3d
   // +1.0 +1.5 +1.2 +1.0 and bd3d +0.9 +0.7 +1.1 +1.9 at their cap of 6 workgroups per CU although their streams shrink
   // as well (483 -> 415, 519 -> 433): with less to issue they keep more bytes in flight, which is what the cap exists to
   // limit, and at 5 per CU they lose more than they gain on a fast box (133.0 vs 130.3 us).  gwd3d is the slowest of
   // the three on fast boxes, i.e. the kernel roofline.frac is computed from.
-  constexpr bool HAS_PLAIN = LOSS == GD3D_GWD3D || (GD_PLAIN_ALL && (LOSS == GD3D_KLD3D || LOSS == GD3D_BD3D));
+  constexpr bool HAS_PLAIN = LOSS == GD3D_GWD3D;
   const bool plain = HAS_PLAIN && !GT && a.w == nullptr && a.w7 == nullptr && !a.wsel && a.pro == GD3D_PRO_NONE &&
                      a.loss == nullptr && a.fin == nullptr;
   if (g.ev_start != nullptr || g.ev_stop != nullptr) {

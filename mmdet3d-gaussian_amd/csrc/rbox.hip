@@ -811,14 +811,6 @@ __global__ __launch_bounds__(64) void nms_clip_queue_kernel(const NmsArgs a, con
   }
 }
 
-#ifdef SCAN_PROFILE
-#define SCAN_STAMP(k) do { if (lane == 0) dbg[(size_t)c * 16 + (k)] = clock64(); } while (0)
-#define SCAN_STAMP_SYNC(k) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); SCAN_STAMP(k); } while (0)
-#else
-#define SCAN_STAMP(k) do { } while (0)
-#define SCAN_STAMP_SYNC(k) do { } while (0)
-#endif
-
 // wave-wide OR on the DPP network (row_shr 1/2/4/8 inside each row of 16, row_bcast 15 / 31 across rows; lane 63 holds
 // the result): replaces up to 64 same-address ds_or_b64, which the LDS serialises.
 template <int CTRL, int ROW_MASK>
@@ -848,7 +840,7 @@ __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) 
          (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)lo, 63);
 }
 // ---- greedy scan: one workgroup, phase-shifted waves, one LDS-only barrier per 64-box block ("interval") -------------
-// Measured with the cycle-stamp build (tools/scan_profile.py): a global-memory round trip from this CU is ~2700 cycles,
+// Measured with a cycle-stamp build (profiles/r05_nms_scan_stamps.txt): a global-memory round trip from this CU is ~2700 cycles,
 // a resolved block ~1200.  So no wave may load and use a value inside one interval:
 //   wave 0 (resolver) reads what the NEXT block waits for — colm[64t+l] and the first "urgent" word mask[64t+l][t+1] — from an
 //     LDS ring that other waves filled one interval earlier.  It solves the block wave-parallel (kept = alive; kept' = alive &
@@ -910,7 +902,7 @@ template <int U, int CH>
 __device__ __forceinline__ void nms_scan_body(const NmsArgs& a, const unsigned long long* __restrict__ mask_,
                                               const unsigned long long* __restrict__ colm_,
                                               long long* __restrict__ keep_, long long* __restrict__ num_keep,
-                                              long long* __restrict__ dbg, const ScanWindow& win) {
+                                              const ScanWindow& win) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long remv[];  // cbs words
   __shared__ unsigned long long skept[4];
   __shared__ int scount;        // boxes kept before the block the next scribe step handles (handed from field wave to field wave)
@@ -973,7 +965,6 @@ __device__ __forceinline__ void nms_scan_body(const NmsArgs& a, const unsigned l
     // scenes (stamps, profiles/r05_nms_pmc.txt: lds 180 | solve 176 | ids + urgent ORs + lists 580 | barrier 116 of 1052 cycles).
     unsigned long long carry = 0ull;   // kept boxes of the previous block -> removed lanes of this one
     for (int c = c_begin; c < cb; ++c) {
-      SCAN_STAMP(0);
       const int slot = c & (SCAN_RING - 1);
       const unsigned long long col = rin[slot][0][lane];
       unsigned long long urg1 = rin[slot][1][lane];
@@ -983,22 +974,18 @@ __device__ __forceinline__ void nms_scan_body(const NmsArgs& a, const unsigned l
       if (nvalid < 64) cur |= ~0ull << nvalid;
       const unsigned long long alive = ~cur;
       unsigned long long kept = alive;
-      SCAN_STAMP(1);
       for (;;) {  // <= 65 rounds; the fixed point is the greedy keep set of the block
         const bool sup = ((clo & (unsigned int)kept) | (chi & (unsigned int)(kept >> 32))) != 0u;
         const unsigned long long nk = alive & ~__ballot(sup);
         if (nk == kept) break;
         kept = nk;
       }
-      SCAN_STAMP(2);
       const bool mine = (kept >> lane) & 1ull;
       if (mine) klist[c & 3][__builtin_popcountll(kept & ((1ull << lane) - 1ull))] = lane;
       if (lane == 0) skept[c & 3] = kept;
       urg1 = mine ? urg1 : 0ull;
       carry = (c + 1 < cb) ? wave_or_u64(urg1) : 0ull;   // (uniform bound)
-      SCAN_STAMP(3);
       lds_barrier();
-      SCAN_STAMP(5);
     }
     if (NB == 0 && lane == 0) num_keep[g] = 0;   // an empty group: no block, no scribe step (a windowed launch returned above)
   } else {
@@ -1100,8 +1087,6 @@ __device__ __forceinline__ void nms_scan_body(const NmsArgs& a, const unsigned l
 
     for (int s2 = 0; s2 < S; ++s2) {
       const int t0 = c_begin + grp + 3 * s2;
-      [[maybe_unused]] const int c = t0;  // (SCAN_STAMP index)
-      if (wave == 1) SCAN_STAMP(8);
       // ---- interval t0: issue
       const int bk = t0 - 1;             // block whose kept rows this group spreads
       const int first = t0 + SCAN_NU;    // = bk + 1 + SCAN_NU: first word not covered by the urgent words
@@ -1124,7 +1109,6 @@ __device__ __forceinline__ void nms_scan_body(const NmsArgs& a, const unsigned l
       const int m = cnt > rank ? (cnt - rank + SCAN_GW - 1) / SCAN_GW : 0;  // rows of this wave (uniform)
       // (the lane-list read above is unconditional: a lane beyond m reads a stale or foreign slot that no readlane below ever
       //  selects; predicating the read on lane < m made it wait for the kept word's own LDS round trip first)
-      if (wave == 1) SCAN_STAMP_SYNC(13);
       const unsigned long long* blk = mask + (size_t)(max(bk, c_begin) * 64) * cbs;
       // Loads are unconditional per lane: the word index is clamped into the row (w < cb is the same for every row of a
       // chunk, so the surplus lanes are masked ONCE, at consume time) — a per-row lane predicate cost ~100 cycles per
@@ -1157,8 +1141,6 @@ __device__ __forceinline__ void nms_scan_body(const NmsArgs& a, const unsigned l
           }
         }
       }
-      if (wave == 1) SCAN_STAMP(14);
-      if (wave == 1) SCAN_STAMP(15);
       if (m > U || (m > 0 && first + 64 * CH < cb)) {  // overflow: finish it now, synchronously (rare)
         for (int w0 = first; w0 < cb; w0 += 64) {
           const int w = w0 + lane;
@@ -1170,11 +1152,9 @@ __device__ __forceinline__ void nms_scan_body(const NmsArgs& a, const unsigned l
           if (acc) atomicOr(&remv[w], acc);
         }
       }
-      if (wave == 1) SCAN_STAMP(10);
       lds_barrier();
       // ---- interval t0+1: the loads fly
       lds_barrier();
-      if (wave == 1) SCAN_STAMP(11);
       // ---- interval t0+2: consume.  The empty asm pins the first USE of every loaded register here: without it the
       // scheduler hoists the (pure VALU) OR tree above the two barriers and has to wait for the loads before them.
 #pragma unroll
@@ -1189,9 +1169,7 @@ __device__ __forceinline__ void nms_scan_body(const NmsArgs& a, const unsigned l
         const int w = first + ch * 64 + lane;
         if (w < cb && acc) atomicOr(&remv[w], acc);  // ds_or_b64: waves merge into the same words
       }
-      if (wave == 1) SCAN_STAMP(9);
       lds_barrier();
-      if (wave == 1) SCAN_STAMP(12);
     }
     for (int q = 0; q < trail; ++q) lds_barrier();
   }
@@ -1202,8 +1180,8 @@ template <int U, int CH>
 __global__ __launch_bounds__(SCAN_T) void nms_scan_kernel(const NmsArgs a, const unsigned long long* __restrict__ mask_,
                                                           const unsigned long long* __restrict__ colm_,
                                                           long long* __restrict__ keep_, long long* __restrict__ num_keep,
-                                                          long long* __restrict__ dbg, const ScanWindow win) {
-  nms_scan_body<U, CH>(a, mask_, colm_, keep_, num_keep, dbg, win);
+                                                          const ScanWindow win) {
+  nms_scan_body<U, CH>(a, mask_, colm_, keep_, num_keep, win);
 }
 
 // ---- LIST scan (round 5): the greedy scan on per-box VICTIM LISTS and one state BYTE per box in LDS ----------------------------------
@@ -1247,9 +1225,7 @@ __global__ __launch_bounds__(SCAN_T) void nms_scan_kernel(const NmsArgs a, const
 constexpr int LIST_RING = 16;
 constexpr int LIST_HW = 12;
 constexpr int LIST_SPIN_MAX = 1 << 22;
-#ifndef LIST_POLL_SLEEP
-#define LIST_POLL_SLEEP 2
-#endif
+constexpr int LIST_POLL_SLEEP = 2;
 
 // volatile accesses that stay LDS instructions (a volatile access through a generic pointer becomes a flat_load / flat_store with an
 // immediate wait)
@@ -1282,8 +1258,7 @@ struct RingFields {      // what a ring slot is made of, as loaded
 __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned long long* __restrict__ colm_,
                                               const unsigned short* __restrict__ lists_, const unsigned* __restrict__ lcnt_,
                                               unsigned lblock,
-                                              long long* __restrict__ keep_, long long* __restrict__ num_keep_,
-                                              [[maybe_unused]] long long* __restrict__ dbg) {
+                                              long long* __restrict__ keep_, long long* __restrict__ num_keep_) {
   constexpr int SB = (int)LIST_MAX_N + 384;
   __shared__ __attribute__((aligned(16))) unsigned char stb[SB];   // state byte per box; [LIST_DUMMY + 4 lane] are scratch
   __shared__ unsigned int rent[LIST_RING][LIST_NEAR][64];    // [slot][k][lane]: LDS address of the state byte of the lane's k-th near victim
@@ -1357,9 +1332,6 @@ __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned l
   if (wave < cbp) f0 = load_ring(wave);
   lds_barrier();                                 // (the zero fill above, before anything else is written)
   if (fail != 0u) return false;                  // uniform over the workgroup
-#ifdef SCAN_PROFILE
-  if (lane == 0) dbg[(size_t)(2 * cb + 16) * 16 + wave] = __builtin_amdgcn_s_getreg(63492);   // HW_ID of every wave
-#endif
   for (int j = n + tid; j < cbp * 64; j += SCAN_T) stb[j] = 1;   // boxes past the end: suppressed from the start
   if (wave < cbp) store_ring(wave, f0);
   lds_barrier();                                 // the only barriers of this scan
@@ -1398,11 +1370,6 @@ __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned l
       const unsigned int gen1 = (unsigned int)(c0 >> 4) + 1u;   // what the flag of every block of this group carries
       auto block = [&](auto U) {
         constexpr int u = decltype(U)::value;
-        [[maybe_unused]] const int c = c0 + u;
-        SCAN_STAMP(0);
-#ifdef SCAN_PROFILE
-        if (lane == 0) dbg[(size_t)c * 16 + 6] = dbg[(size_t)c * 16 + 7] = 0;
-#endif
         const unsigned int* const crl = rl0 + u * SLOT_DW;          // this block's slot
         // the slot fetched in this block: block c + 1
         const unsigned int* const frl = u < 3 ? rl0 + (u + 1) * SLOT_DW : rl4;
@@ -1418,9 +1385,6 @@ __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned l
           bool got = false;
           for (int spins = 0; spins < LIST_SPIN_MAX && lds_peek(&failed) == 0u; ++spins) {
             __builtin_amdgcn_s_sleep(1);
-#ifdef SCAN_PROFILE
-            if (lane == 0) dbg[(size_t)c * 16 + 7] = spins + 1;
-#endif
             if (__builtin_amdgcn_readfirstlane((int)lds_peek(&fdp[u])) != 0) {
               got = true;
               break;
@@ -1456,9 +1420,6 @@ __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned l
           for (int spins = 0; spins < LIST_SPIN_MAX && lds_peek(&failed) == 0u; ++spins) {
             __builtin_amdgcn_s_sleep(1);
             COMPILER_FENCE();
-#ifdef SCAN_PROFILE
-            if (lane == 0) dbg[(size_t)c * 16 + 6] = spins + 1;
-#endif
             const unsigned int fl = (unsigned int)__builtin_amdgcn_readfirstlane((int)lds_peek(rf0 + u));
             COMPILER_FENCE();
             l0 = ring4(crl, 0);
@@ -1473,7 +1434,6 @@ __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned l
           if (!got) lds_poke(&failed, 1u);
         }
         unsigned long long kept = __ballot(state == 0);   // nobody kept so far suppresses the lane's box
-        SCAN_STAMP(1);
         if (__builtin_expect((flag & 0x80u) != 0u, 0)) {   // some box of the block has an earlier box of the block on its column word
           const unsigned long long alive = kept;
           const unsigned int clo = (unsigned int)col, chi = (unsigned int)(col >> 32);
@@ -1486,7 +1446,6 @@ __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned l
             }
           }
         }
-        SCAN_STAMP(2);
         const bool mine = __builtin_amdgcn_inverse_ballot_w64(kept);
         // near victims first (read back by THIS wave for later blocks — LDS runs a wave's accesses in order), the block's own state
         // bytes LAST: they are what the helper waves poll, and a helper that sees the block resolved will refill this block's ring
@@ -1504,7 +1463,6 @@ __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned l
         COMPILER_FENCE();
         kw[u * 64] = mine ? 0x80 : 0x02;
         COMPILER_FENCE();
-        SCAN_STAMP(3);
       };
       block(std::integral_constant<int, 0>{});
       block(std::integral_constant<int, 1>{});
@@ -1521,12 +1479,6 @@ __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned l
   auto kept_word = [&](int blk) -> unsigned long long { return __ballot(stb[blk * 64 + lane] == 0x80); };
   unsigned int fcnt_next = hw < cb ? cnt2[min(hw * 64 + lane, n - 1)].y : 0u;   // far count of this wave's next block, one iteration ahead
   for (int t = hw; t < cb; t += LIST_HW) {
-#ifdef SCAN_PROFILE
-#define HSTAMP(k) do { if (lane == 0) dbg[(size_t)(cb + 8 + t) * 16 + (k)] = clock64(); } while (0)
-#else
-#define HSTAMP(k) do { } while (0)
-#endif
-    HSTAMP(0);
     const bool more = t + LIST_RING < cbp;
     // block t's far lists: as many uint4 as its longest one needs (the counts were loaded an iteration ago; lanes past the end have
     // a clamped index and are never kept)
@@ -1551,7 +1503,6 @@ __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned l
       __builtin_amdgcn_s_sleep(LIST_POLL_SLEEP);
     }
     COMPILER_FENCE();
-    HSTAMP(1);
     const unsigned long long kept = kept_word(t);
     const bool mine = (kept >> lane) & 1ull;
     {   // far victims of the kept boxes: due before the resolver reaches block t + LIST_K + 1.  ROLLED, the list rotating through
@@ -1573,7 +1524,6 @@ __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned l
       COMPILER_FENCE();
     }
     // scribe step of block t; its global store goes last (loads and stores share one in-order counter)
-    HSTAMP(2);
     // the kept boxes of the blocks since this wave's last one (all resolved before t).  Straight-line — eleven reads in flight at once,
     // a clamped index and a masked count for the first iteration: as a loop it was eleven LDS round trips in a row (1400-1900 cycles,
     // the longest phase of a helper and most of the kernel's tail after the resolver's last block)
@@ -1583,14 +1533,12 @@ __device__ __forceinline__ bool nms_list_body(const NmsArgs& a, const unsigned l
       base += t - i >= 0 ? cntb : 0;
     }
     const long long id = (long long)rid[t & (LIST_RING - 1)][lane];
-    HSTAMP(3);
     if (more) {
       COMPILER_FENCE();                           // (the id above is read before the slot is overwritten)
       asm volatile("" : "+v"(fr.col), "+v"(fr.id));   // first use of the loaded fields pinned here
       store_ring(t + LIST_RING, fr);
       COMPILER_FENCE();
     }
-    HSTAMP(4);
     if (mine) keep[base + __builtin_popcountll(kept & ((1ull << lane) - 1ull))] = id;
     base += __builtin_popcountll(kept);
     if (t == cb - 1 && lane == 0 && lds_peek(&failed) == 0u) num_keep[0] = base;
@@ -1607,8 +1555,8 @@ __global__ __launch_bounds__(SCAN_T) void nms_list_or_scan_kernel(const NmsArgs 
                                                                   const unsigned short* __restrict__ lists,
                                                                   const unsigned* __restrict__ lcnt, unsigned lblock,
                                                                   long long* __restrict__ keep, long long* __restrict__ num_keep,
-                                                                  long long* __restrict__ dbg, const ScanWindow win) {
-  if (!nms_list_body(a, colm, lists, lcnt, lblock, keep, num_keep, dbg)) nms_scan_body<SCAN_U, CH>(a, mask, colm, keep, num_keep, dbg, win);
+                                                                  const ScanWindow win) {
+  if (!nms_list_body(a, colm, lists, lcnt, lblock, keep, num_keep)) nms_scan_body<SCAN_U, CH>(a, mask, colm, keep, num_keep, win);
 }
 
 // Second level of the two-level scan: after super-block [c_begin, c_end) has been resolved, every box it KEPT suppresses
@@ -1806,22 +1754,18 @@ static int rnms_launch(int mode, const float* boxes, const int64_t* order, const
   const dim3 mgrid((unsigned)(pairs * (64 / rows)), (unsigned)G);
   // queued form (circle tests and clipping as two kernels): from QUEUE_MIN_N boxes on, with a threshold every group shares and
   // that is a plain non-negative number (a negative or NaN threshold makes EVERY pair a candidate: the compacted kernel's case)
-  static const long long queue_min_n = [] {
-    const char* e = getenv("RNMS_QUEUE_MIN_N");   // measurement override (tests/perf/nms_time.py A/B)
-    return e != nullptr ? atoll(e) : (long long)QUEUE_MIN_N;
-  }();
-  const bool queued = mode == MODE_ROT && cap >= queue_min_n && pairs <= 0x7fffffffLL && (thresh_dev != nullptr || thresh >= 0.0f);   // (per-group device thresholds are checked in the kernel)
+  const bool queued = mode == MODE_ROT && cap >= QUEUE_MIN_N && pairs <= 0x7fffffffLL && (thresh_dev != nullptr || thresh >= 0.0f);   // (per-group device thresholds are checked in the kernel)
   // list scan (victim lists and state bytes instead of mask-row propagation): groups of QUEUE_MIN_N .. LIST_MAX_N boxes, rotated and
   // axis-aligned boxes;
   // a full list or an overflowed block pair (a negative / NaN device threshold included) falls back to the classic scan on the
   // device, per group
   static const float list_min_thr = [] {
-    const char* e = getenv("RNMS_LIST_MIN_THR");   // measurement / test override (a value > 1 switches the list scan off)
+    const char* e = getenv("RNMS_LIST_MIN_THR");   // test override (a value > 1 switches the list scan off)
     return e != nullptr ? (float)atof(e) : 0.0f;
   }();
   // (not for circle NMS: its mask kernel is so cheap that building the lists — 15.8 -> 21.9 us at n = 4096 — and clearing the
   // counters in a launch of their own — 4.4 us — cost what the list scan saves, 29.5 -> 18.0 us; axis-aligned: 62 -> 55 us)
-  const bool lists_wanted = list_min_thr <= 1.0f && cap >= queue_min_n && cap <= (int64_t)LIST_MAX_N && mode != MODE_CIRCLE &&
+  const bool lists_wanted = list_min_thr <= 1.0f && cap >= QUEUE_MIN_N && cap <= (int64_t)LIST_MAX_N && mode != MODE_CIRCLE &&
                             (mode != MODE_ROT || thresh_dev != nullptr || thresh >= list_min_thr);
   bool use_lists = false;
   QueueArgs ql;   // the list part alone: what the axis-aligned / circle mask kernel takes
@@ -1887,10 +1831,10 @@ static int rnms_launch(int mode, const float* boxes, const int64_t* order, const
     const unsigned* const lcnt = (const unsigned*)((char*)workspace + W.lcnt);
     if (a.cbs <= 64 + 1 + SCAN_NU)
       hipLaunchKernelGGL((nms_list_or_scan_kernel<1>), sgrid, sblk, slds, s, a, (const unsigned long long*)mask,
-                         (const unsigned long long*)colm, lists, lcnt, W.lblock, (long long*)keep, (long long*)num_keep, (long long*)ob, win);
+                         (const unsigned long long*)colm, lists, lcnt, W.lblock, (long long*)keep, (long long*)num_keep, win);
     else
       hipLaunchKernelGGL((nms_list_or_scan_kernel<2>), sgrid, sblk, slds, s, a, (const unsigned long long*)mask,
-                         (const unsigned long long*)colm, lists, lcnt, W.lblock, (long long*)keep, (long long*)num_keep, (long long*)ob, win);
+                         (const unsigned long long*)colm, lists, lcnt, W.lblock, (long long*)keep, (long long*)num_keep, win);
     return (int)hipGetLastError();
   }
   // n <= 8448: one launch resolves everything.  Beyond that the single workgroup's row propagation (three 64-word chunks
@@ -1900,10 +1844,10 @@ static int rnms_launch(int mode, const float* boxes, const int64_t* order, const
   if (a.cbs <= 128 + 1 + SCAN_NU) {
     if (a.cbs <= 64 + 1 + SCAN_NU)  // one 64-word chunk right of any block (n <= 4352): 16 rows x 1 chunk in flight per row wave
       hipLaunchKernelGGL((nms_scan_kernel<SCAN_U, 1>), sgrid, sblk, slds, s, a, (const unsigned long long*)mask,
-                         (const unsigned long long*)colm, (long long*)keep, (long long*)num_keep, (long long*)ob, win);
+                         (const unsigned long long*)colm, (long long*)keep, (long long*)num_keep, win);
     else
       hipLaunchKernelGGL((nms_scan_kernel<SCAN_U, 2>), sgrid, sblk, slds, s, a, (const unsigned long long*)mask,
-                         (const unsigned long long*)colm, (long long*)keep, (long long*)num_keep, (long long*)ob, win);
+                         (const unsigned long long*)colm, (long long*)keep, (long long*)num_keep, win);
     return (int)hipGetLastError();
   }
   // two-level scan: super-blocks of SCAN_SB blocks resolved one after the other by the scan workgroup (rows stay inside
@@ -1915,7 +1859,7 @@ static int rnms_launch(int mode, const float* boxes, const int64_t* order, const
     win.c_begin = c0;
     win.c_end = c0 + SCAN_SB < a.cbs ? c0 + SCAN_SB : a.cbs;
     hipLaunchKernelGGL((nms_scan_kernel<SCAN_U, 1>), sgrid, sblk, slds, s, a, (const unsigned long long*)mask,
-                       (const unsigned long long*)colm, (long long*)keep, (long long*)num_keep, (long long*)ob, win);
+                       (const unsigned long long*)colm, (long long*)keep, (long long*)num_keep, win);
     if (win.c_end < a.cbs) {
       const int wchunks = (a.cbs - win.c_end + 63) / 64;
       hipLaunchKernelGGL(nms_propagate_kernel, dim3((unsigned)((win.c_end - c0) * wchunks), (unsigned)G), dim3(256), 0, s, a,
@@ -2026,12 +1970,7 @@ static int batched_scored_impl(int32_t mode, const float* boxes, const float* sc
   int* counts = (int*)p;
   hipError_t e;
   const dim3 sg((unsigned)((n + 15) / 16), (unsigned)groups);
-  static const unsigned masked_threads = [] {
-    const char* e = getenv("RNMS_RANK_MASKED_THREADS");   // measurement override (tools/nms_batched_ab.sh)
-    const unsigned v = e != nullptr ? (unsigned)atoi(e) : 256u;
-    return (v == 64u || v == 128u || v == 256u || v == 512u || v == 1024u) ? v : 256u;
-  }();
-  const dim3 sb(valid != nullptr && seg == nullptr ? masked_threads : 1024u);   // masked dense form: four waves per workgroup
+  const dim3 sb(valid != nullptr && seg == nullptr ? 256u : 1024u);   // masked dense form: four waves per workgroup
   unsigned* const qctl = (unsigned*)((char*)workspace + ws_layout((size_t)groups, (size_t)cap).qctl);
   if (mode == MODE_ROT)
     hipLaunchKernelGGL((rank_place_kernel<true>), sg, sb, 0, s, boxes, scores, (const unsigned char*)valid, (const int*)seg,

@@ -21,10 +21,6 @@
 namespace rbox {
 
 #define RB_DEV __device__ __forceinline__
-// phase stamps inside box_overlap for tools/clip_probe.hip (cycle accounting of one clipping pass); nothing in the product
-#ifndef RB_STAMP
-#define RB_STAMP(k) do { } while (0)
-#endif
 
 // ------------------------------------------------------------------ fixed-sequence fp32 math
 RB_DEV void fx_sincosf(float x, float& s, float& c) {
@@ -48,7 +44,7 @@ RB_DEV void fx_sincosf(float x, float& s, float& c) {
 // atan2 as select chains instead of branches: every candidate value is computed with the operations of the branch it
 // belongs to (so the selected one is bit-identical to the branchy evaluation; divisions by zero on untaken candidates
 // produce inf / NaN that are discarded), and independent evaluations can overlap in the pipeline — a lone wave spent
-// ~680 dependent-issue cycles per call on the branchy form (tools/clip_probe.hip).
+// ~680 dependent-issue cycles per call on the branchy form (a stand-alone clipping-pass probe).
 RB_DEV float fx_atanf_pos(float t) {
   const bool hi = t > 2.414213562373095f, mid = t > 0.4142135623730950f;
   const float x_hi = -(1.0f / t);
@@ -157,7 +153,6 @@ RB_DEV float box_overlap(const OBox& A, const OBox& B, VertexScratch<NT>& vs, in
     const float reach = 0.5f * (ra + rb) + 1e-2f;
     if (ddx * ddx + ddy * ddy > reach * reach * 1.0001f) return 0.0f;
   }
-  RB_STAMP(1);
   float pcx = 0.0f, pcy = 0.0f;
   int cnt = 0;
 #pragma unroll
@@ -174,7 +169,6 @@ RB_DEV float box_overlap(const OBox& A, const OBox& B, VertexScratch<NT>& vs, in
       }
     }
   }
-  RB_STAMP(2);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     if (in_box(A, B.c[k]) && cnt < 16) {
@@ -192,14 +186,13 @@ RB_DEV float box_overlap(const OBox& A, const OBox& B, VertexScratch<NT>& vs, in
       ++cnt;
     }
   }
-  RB_STAMP(3);
   if (cnt == 0) return 0.0f;
   pcx = pcx / (float)cnt;
   pcy = pcy / (float)cnt;
   // Fast path for <= 8 vertices (two convex quadrilaterals meet in at most 8 points; more only arise when a point is
   // collected both as an intersection and as a corner): the reference sequence — angle of every vertex about the
   // centroid, STABLE bubble sort by angle, fan area in sorted order — evaluated on registers.  The 8 angle evaluations
-  // are independent (a lone wave otherwise spends ~680 dependent-issue cycles per vertex, tools/clip_probe.hip), the sort
+  // are independent (a lone wave otherwise spends ~680 dependent-issue cycles per vertex in a clipping-pass probe), the sort
   // is a 19-exchange network on the key (angle, collection index) — a strict total order, so the network yields exactly
   // the permutation the stable bubble sort does, ties and +-0 included — and the area sum runs in that order with the
   // reference's operations.  A NaN angle (NaN / inf input boxes) has no place in a total order: those pairs, and the
@@ -237,8 +230,6 @@ RB_DEV float box_overlap(const OBox& A, const OBox& B, VertexScratch<NT>& vs, in
       RB_CE(1, 4) RB_CE(3, 6)
       RB_CE(1, 2) RB_CE(3, 4) RB_CE(5, 6)
 #undef RB_CE
-      RB_STAMP(4);
-      RB_STAMP(5);
       float area = 0.0f;
       const float x0 = X[0], y0 = Y[0];
 #pragma unroll
@@ -248,12 +239,10 @@ RB_DEV float box_overlap(const OBox& A, const OBox& B, VertexScratch<NT>& vs, in
         const float next = area + (ax * by - ay * bx);
         area = (k < cnt - 1) ? next : area;
       }
-      RB_STAMP(6);
       return fabsf(area) / 2.0f;
     }
   }
   for (int k = 0; k < cnt; ++k) vs.a[k][t] = fx_atan2f(vs.y[k][t] - pcy, vs.x[k][t] - pcx);
-  RB_STAMP(4);
   for (int j = 0; j < cnt - 1; ++j)
     for (int i = 0; i < cnt - j - 1; ++i) {
       const float a0 = vs.a[i][t], a1 = vs.a[i + 1][t];
@@ -267,7 +256,6 @@ RB_DEV float box_overlap(const OBox& A, const OBox& B, VertexScratch<NT>& vs, in
         vs.a[i + 1][t] = a0;
       }
     }
-  RB_STAMP(5);
   float area = 0.0f;
   const float x0 = vs.x[0][t], y0 = vs.y[0][t];
   for (int k = 0; k < cnt - 1; ++k) {
@@ -275,7 +263,6 @@ RB_DEV float box_overlap(const OBox& A, const OBox& B, VertexScratch<NT>& vs, in
     const float bx = vs.x[k + 1][t] - x0, by = vs.y[k + 1][t] - y0;
     area = area + (ax * by - ay * bx);
   }
-  RB_STAMP(6);
   return fabsf(area) / 2.0f;
 }
 

@@ -23,9 +23,7 @@
 
 namespace vox {
 
-#ifndef SCATTER_U
-#define SCATTER_U 4  // independent row loads in flight per lane (forward)
-#endif
+constexpr int SCATTER_U = 4;  // independent row loads in flight per lane (forward)
 
 template <int REDUCE>
 __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ feats, const int* __restrict__ order,
@@ -160,9 +158,7 @@ __global__ __launch_bounds__(256) void reduce_v4_kernel(const float* __restrict_
 //   max : ... only where argmax[map[i], ch] == i (the forward's recorded arg max), else 0
 // VEC = 4: a thread moves 4 consecutive channels with 16-byte accesses (c % 4 == 0, 16-byte aligned rows).
 typedef float v4f_t __attribute__((ext_vector_type(4)));
-#ifndef GATHER_GU_SCALAR
-#define GATHER_GU_SCALAR 4   // 8 measured no faster (c = 10 sum 39.8 vs 40.5 us) and slower for mean (50.5 vs 45 us)
-#endif
+constexpr int GATHER_GU_SCALAR = 4;   // 8 measured no faster (c = 10 sum 39.8 vs 40.5 us) and slower for mean (50.5 vs 45 us)
 
 template <int MODE, int VEC>
 __global__ __launch_bounds__(256) void gather_grad_kernel(const float* __restrict__ gvox, const int* __restrict__ map,

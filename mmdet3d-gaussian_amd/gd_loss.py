@@ -29,9 +29,6 @@ FUNS = {'none': 0, 'log1p': 1, 'expm1': 2, 'nlog': 3}
 # bench.py sets this to a list; every fused launch then appends a DispatchTimer: a pair of HIP events bound to the
 # begin / end timestamps of that kernel's own dispatch (gd3d_loss_fused_timed), inside the timed region.
 PROFILE_EVENTS = None
-# measurement switch (tests/perf/small_p_latency.py): 1 = decide the no-positive-weight early-out on the HOST as the
-# reference does (torch.any + a device-to-host wait per call) instead of inside the fused launch
-_HOST_WEIGHT_CHECK = os.environ.get('GD3D_HOST_WEIGHT_CHECK', '0') == '1'
 
 
 class DispatchTimer:
@@ -132,7 +129,7 @@ _capturing = torch._C._cuda_isCurrentStreamCapturing
 def _one_launch_max():
     global _ONE_MAX
     if _ONE_MAX is None:
-        _ONE_MAX = int(_library().gd3d_one_launch_max_n()) if os.environ.get('GD3D_TWO_STAGE', '0') != '1' else -1
+        _ONE_MAX = int(_library().gd3d_one_launch_max_n())
     return _ONE_MAX
 
 
@@ -410,7 +407,7 @@ class GDLoss(nn.Module):
         # there) for particular shapes, which cannot be decided from the device.
         select = False
         if weight is not None and reduction != 'none':
-            if weight.shape == pred.shape and weight.is_cuda and pred.is_cuda and not _HOST_WEIGHT_CHECK:
+            if weight.shape == pred.shape and weight.is_cuda and pred.is_cuda:
                 select = True
             elif not torch.any(weight > 0):
                 return (pred * weight).sum()

@@ -6,14 +6,12 @@ weight (P,7) = 1, avg_factor = P).  Per P:
   amortised_us  : 8 GDLoss calls summed, ONE backward() — the shape of a real training step, where the loss is one of
                   many nodes of a single backward pass; per-call cost = step / 8;
   forward_us    : forward only;
-  eager_torch_us: the reference-style eager PyTorch op chain on the same GPU (oracle/gd_torch.py), isolated.
-Run twice for the weight-path A/B: GD3D_HOST_WEIGHT_CHECK=1 decides the early-out on the host as the reference does."""
+  eager_torch_us: the reference-style eager PyTorch op chain on the same GPU (oracle/gd_torch.py), isolated."""
 import os, sys, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import math, torch
 import mmdet3d_gaussian_amd as amd
-from mmdet3d_gaussian_amd import gd_loss as gdl
 from oracle import gd_torch
 dev = torch.device('cuda:0')
 def pairs(n, seed=0):
@@ -61,7 +59,7 @@ while time.perf_counter() - _t0 < 2.0:
     _wp.grad = None; _wm(_wp, _wt).backward()
 torch.cuda.synchronize()
 print(json.dumps(floor_rows()), flush=True)
-mode = 'host torch.any check (reference control flow)' if gdl._HOST_WEIGHT_CHECK else 'early-out resolved in the fused launch'
+mode = 'early-out resolved in the fused launch'
 lt = 'kld3d'
 mod = amd.GDLoss(lt, fun='log1p', tau=0.0, loss_weight=5.0)
 for weighted, sizes in ((True, (64, 512, 4096, 100_000, 1_000_000, 10_000_000)), (False, (64, 512, 4096, 100_000, 1_000_000, 10_000_000)),

@@ -4,6 +4,7 @@ reference module's constructor and argument handling.  No GPU needed."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 import torch
@@ -29,6 +30,10 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), f'{n} declared in include/gd3d.h but not exported by libgd3d.so'
     assert sorted(_lib.SYMBOLS) == names, 'ctypes table and header disagree'
+    # nothing else: no kernel stubs, template instances or other extern C++ symbols (csrc/gd3d.map)
+    nm = subprocess.run(['nm', '-D', '--defined-only', amd.lib_path()], capture_output=True, text=True, check=True).stdout
+    exported = sorted(f[2] for f in (line.split() for line in nm.splitlines()) if len(f) == 3 and f[1] in 'TWi')
+    assert exported == names, f'libgd3d.so exports beyond include/gd3d.h: {sorted(set(exported) - set(names))[:10]}'
     extra = _header_functions('gd3d_extras.h')
     assert len(extra) >= 10 and not set(extra) & set(names)
     xlib = ctypes.CDLL(_lib.extras_path())

@@ -26,7 +26,6 @@ rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_I
   --output-format csv -d $OUT/pmc_sq -- $SHORT > $OUT/pmc_sq.log 2>&1
 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR GRBM_GUI_ACTIVE \
   --output-format csv -d $OUT/pmc_sq2 -- $SHORT > $OUT/pmc_sq2.log 2>&1
-python3 tools/build_probes.py > /dev/null; [ -x tools/hbm_probe ] && ./tools/hbm_probe > $OUT/${R}_hbm_probe.txt 2>&1
 # multi-GPU rehearsal with ONE rank under torch.distributed.run (RCCL backend, hipGraph replay + per-step all_gather): the
 # N > 1 code path of bench.py as far as one GPU can exercise it; weak and strong scaling (--graph: one rank alone would launch
 # eagerly, N > 1 ranks replay a graph), and the eager form
@@ -35,8 +34,7 @@ $RUN1 --master-port 29511 bench.py --gpus 1 --steps 20 --warmup 5 --full --cpu-s
 $RUN1 --master-port 29512 bench.py --gpus 1 --steps 20 --warmup 5 --full --cpu-sample 0 --no-traffic --graph --strong > $OUT/${R}_rccl_rehearsal_strong.json 2> $OUT/rehearsal_strong.err
 $RUN1 --master-port 29513 bench.py --gpus 1 --steps 20 --warmup 5 --full --cpu-sample 0 --no-traffic --no-graph > $OUT/${R}_rccl_rehearsal_weak_eager.json 2> $OUT/rehearsal_weak_eager.err
 python3 tests/perf/nms_time.py 2>&1 | grep -v amdgpu.ids > $OUT/${R}_nms_time.txt
-FORMS="single batched batched_c multi" tools/nms_batched_ab.sh product 2>&1 | grep -v amdgpu.ids > $OUT/${R}_nms_batched_kernels.txt
-[ -x tools/launch_floor ] && ./tools/launch_floor > $OUT/${R}_launch_floor.txt 2>&1
+FORMS="single batched batched_c multi" tools/nms_batched_kernels.sh 2>&1 | grep -v amdgpu.ids > $OUT/${R}_nms_batched_kernels.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_nms -- python3 tests/perf/nms_time.py > /dev/null 2>&1
 cp $OUT/kt_nms/*/*kernel_stats.csv $OUT/${R}_nms_kernel_stats.csv 2>/dev/null
 python3 tests/perf/small_p_latency.py 2>&1 | grep -v amdgpu.ids > $OUT/${R}_small_p_latency.jsonl
@@ -47,10 +45,6 @@ tools/pmc_issue_mix.sh $OUT/${R}_pmc_issue_mix.txt > /dev/null 2>&1
 python3 tests/perf/eval_time.py 2>&1 | grep -v amdgpu.ids > $OUT/${R}_eval_time.jsonl
 python3 tools/scatter_time.py 2>&1 | grep -v amdgpu.ids > $OUT/${R}_scatter_time.jsonl
 python3 tools/scatter_kernel_time.py 2>&1 | grep -v amdgpu.ids > $OUT/${R}_scatter_kernel_time.txt
-# the NMS scan's cycle stamps (profiling build) and the proof that the parity gates bite (damaged builds must fail)
-python3 tools/build_variants.py prof="-DSCAN_PROFILE=1" > /dev/null 2>&1
-GD3D_LIB=tools/variants/libgd3d_prof.so GD3D_HOST=python python3 tools/scan_profile.py 2>&1 | grep -v amdgpu.ids > $OUT/${R}_nms_scan_stamps.txt
-python3 tools/gate_bites.py $OUT/${R}_gate_bites.txt > /dev/null 2>&1
 # host glue A/B at training sizes: the Python autograd.Function + ctypes layer against the optional C++ node, same box
 GD3D_HOST=python python3 tests/perf/small_p_latency.py 2>&1 | grep -v amdgpu.ids > $OUT/${R}_small_p_latency_python_glue.jsonl
 GD3D_HOST=cpp python3 tests/perf/small_p_latency.py 2>&1 | grep -v amdgpu.ids > $OUT/${R}_small_p_latency_cpp_glue.jsonl

@@ -1,5 +1,5 @@
 """Timing of match_coco on problems the GENERIC matcher kernel takes (more than 256 gts): sparse and dense cost matrices.
-usage: tools/match_wide_time.py   (GD3D_LIB selects a library variant)"""
+usage: tools/match_wide_time.py"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,5 +1,5 @@
 """The configs[4] stand-in under rocprofv3: 3 classes x 4096 boxes, thr 0.25, 60 calls of ONE form.
-usage: tools/nms_batched_one.py single|batched|batched_c   (GD3D_LIB selects a library variant)
+usage: tools/nms_batched_one.py single|batched|batched_c|multi
   single    : nms_gpu on one class (scored path: rank_place + circle + clip + scan)
   batched   : nms_gpu_batched over the 12 288 shared boxes with a (3, 12288) validity mask (pvrcnn_bbox_head.py:438-464)
   batched_c : the same through the C ABI only (rnms_batched_scored; no Python between the launches)"""

@@ -45,7 +45,7 @@ def run(j):
     if r.returncode: raise SystemExit(' '.join(j[1]) + '\n' + r.stderr[-3000:])
     return j[0]
 with concurrent.futures.ThreadPoolExecutor(6) as ex: objs = list(ex.map(run, jobs))
-r = subprocess.run([b.hipcc_path(), '--offload-arch=gfx950', '-shared', '-fPIC', '-pthread', '-shared-libsan'] + san + ['-fno-gpu-sanitize', '-o', os.path.join(out, 'libgd3d.so')] + objs, capture_output=True, text=True)
+r = subprocess.run([b.hipcc_path(), '--offload-arch=gfx950', '-shared', '-fPIC', '-pthread', '-shared-libsan'] + san + ['-fno-gpu-sanitize', '-Wl,--version-script=' + b.VERSION_SCRIPT, '-o', os.path.join(out, 'libgd3d.so')] + objs, capture_output=True, text=True)
 if r.returncode: raise SystemExit('link: ' + r.stderr[-3000:])
 cmd = b.node_command(os.path.join(out, '_gd3d_node.so'))
 cmd = [c for c in cmd if c != '-O2'] + ['-O1', '-g', '-shared-libsan'] + san
