@@ -82,6 +82,8 @@ typedef struct gd3d_params {
  * n == 0 is legal (loss_sum = 0).  workspace: gd3d_loss_workspace_bytes(n) bytes,
  * 16-byte aligned; required when loss_sum != NULL; whenever it is given the kernel leaves one
  * fp32 partial sum per 256-pair tile at its start.
+ * The order in which a launch visits the tiles is internal (it alternates between launches on the same
+ * target); every output, the partial sums included, is bit-identical in either order.
  * ---------------------------------------------------------------------------------- */
 size_t gd3d_loss_workspace_bytes(int64_t n);
 

@@ -24,6 +24,9 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <mutex>
+#include <unordered_map>
+
 #include "gd3d_device.h"
 
 namespace gd3d {
@@ -42,10 +45,18 @@ constexpr int HEAD_T = 256;          // threads per workgroup of the head-level 
 typedef __attribute__((address_space(3))) void lds_ptr_t;
 typedef const __attribute__((address_space(1))) void gbl_cptr_t;
 
-// LDS-DMA loads with the nt cache policy: every input byte is read exactly once (measured r01, 10 M pairs: nt loads + nt
-// stores 129 us vs 151 us plain; a persistent double-buffered grid-stride variant was 143-160 us and was dropped, see
-// DESIGN.md)
+// LDS-DMA loads of pred (and of the optional (N,7) weights) with the nt cache policy: those bytes are read exactly once
+// (measured r01, 10 M pairs: nt loads + nt stores 129 us vs 151 us plain; a persistent double-buffered grid-stride variant
+// was 143-160 us and was dropped)
 constexpr int DMA_AUX = 2;
+// The TARGET is read with the default policy instead: a training step evaluates several losses against the same target
+// back to back (GDLoss.forward(pred_k, target)), and default-policy lines stay in the 256 MiB Infinity Cache for the next
+// launch while nt lines do not.  The launcher walks every launch on the same target opposite to the one before, so the rows
+// read last are read again first (loss_launch).  tools/target_reuse_probe.hip, profiles/r07_target_reuse_probe.txt: three
+// 2-read-1-write passes over a shared 280 MB buffer, us per pass after the first: nt 131, default 99-102 in alternating
+// order (116 ascending); the first pass from clean caches 137 vs 134 with nt.  sc0 / sc1 behave as the default policy,
+// sc0 nt / sc1 nt as nt.
+constexpr int DMA_AUX_TARGET = 0;
 // Occupancy cap.  The fused launch requests AT LEAST this much dynamic LDS, i.e. floor(160 KiB / bytes) workgroups per CU
 // instead of the 8 that its own 14.4 KiB would admit: fewer tiles in flight per CU stream better (the kernel's data path
 // without its math: 8 WG/CU 131.0 us, 6: 130.2, 5: 126.7, 4: 126.8, 3: 162; flat copy 127.5), but fewer waves hide less
@@ -57,6 +68,10 @@ constexpr int DMA_AUX = 2;
 //     6     131.7 / 136.4           129.6 / 138.0    130.1 / 137.6
 //     5     131.4 / 134.7           135.8 / 137.6    140.0 / 140.9
 //     4     132.2 / 134.6           136.0 / 136.8    139.9 / 140.3
+// A launch that re-reads the target the previous launch read (loss_launch: Geometry::reuse) is NOT capped: with part of
+// its bytes served by the Infinity Cache the math is what is left to hide, and 8 workgroups per CU hide it best
+// (profiles/r07_target_reuse_ab.txt, bench step, us per fused launch: capped as below 130.7-133.7, 7 per CU 115.6-116.9,
+// 8 per CU 117.2-117.4; a launch on a target nobody read just before keeps the cap: uncapped it took 135.5 against 133.0).
 constexpr int MIN_LDS = 27300;         // 6 workgroups per CU
 constexpr int MIN_LDS_GWD = 32768;     // 5
 constexpr int MIN_LDS_W7 = 32768;      // 5, launches with (N,7) weights (any loss)
@@ -72,9 +87,10 @@ GD_DEV void store_v4(float* dst, const float* src_lds, int idx) {
 
 // 14 LDS-DMA pieces of 1 KiB bring one 256-pair tile of pred and target into LDS; wave w issues pieces w, w+4, w+8, w+12.
 // The two tiles are adjacent in LDS (st = sp + TILE_F = sp + 7 pieces), so piece j of the 14 lands at sp + j * 256 and only
-// its SOURCE depends on which tensor it belongs to — a scalar select, no branch.  (Written as a loop over both tensors
-// with per-piece if / else-if, the compiler built a tree of ~60 scalar compares and branches in front of the first load:
-// issue slots on every workgroup's critical path, profiles/r02_pmc_issue_mix_by_cap.txt.)
+// its SOURCE and its cache policy depend on which tensor it belongs to.  Rounds 0 and 2-3 are pred-only / target-only at
+// compile time; round 1 (pieces 4-7) is the only one that mixes them and takes one wave-uniform branch.  (Written as a loop
+// over both tensors with per-piece if / else-if, the compiler built a tree of ~60 scalar compares and branches in front of
+// the first load: issue slots on every workgroup's critical path, profiles/r02_pmc_issue_mix_by_cap.txt.)
 // (an optional third tile, the (256,7) weights, sits behind the wave sums and keeps its own loop)
 GD_DEV void issue_tile_dma(const float* gpred, const float* gtarget, float* sp, float* st, int wave, int lane,
                            const float* gw7, float* sw7) {
@@ -84,9 +100,18 @@ GD_DEV void issue_tile_dma(const float* gpred, const float* gtarget, float* sp, 
 #pragma unroll
   for (int k = 0; k * NWAVE < 2 * NPIECE; ++k) {
     const int j = wave + k * NWAVE;  // wave-uniform
-    if ((k + 1) * NWAVE <= 2 * NPIECE || j < 2 * NPIECE) {   // only the last round needs the runtime test
-      const float* src = (j < NPIECE ? gpred : t_shifted) + j * 256 + lane * 4;
-      __builtin_amdgcn_global_load_lds((gbl_cptr_t*)src, (lds_ptr_t*)(sp + j * 256), 16, 0, DMA_AUX);
+    const float* const p_src = gpred + j * 256 + lane * 4;
+    const float* const t_src = t_shifted + j * 256 + lane * 4;
+    lds_ptr_t* const dst = (lds_ptr_t*)(sp + j * 256);
+    if ((k + 1) * NWAVE <= NPIECE) {                // whole round in pred
+      __builtin_amdgcn_global_load_lds((gbl_cptr_t*)p_src, dst, 16, 0, DMA_AUX);
+    } else if (k * NWAVE >= NPIECE) {               // whole round in target; only the last round needs the runtime test
+      if ((k + 1) * NWAVE <= 2 * NPIECE || j < 2 * NPIECE)
+        __builtin_amdgcn_global_load_lds((gbl_cptr_t*)t_src, dst, 16, 0, DMA_AUX_TARGET);
+    } else if (j < NPIECE) {                        // the mixed round: a wave-uniform branch
+      __builtin_amdgcn_global_load_lds((gbl_cptr_t*)p_src, dst, 16, 0, DMA_AUX);
+    } else {
+      __builtin_amdgcn_global_load_lds((gbl_cptr_t*)t_src, dst, 16, 0, DMA_AUX_TARGET);
     }
   }
   if (gw7 != nullptr) {
@@ -122,6 +147,7 @@ struct LossArgs {
   float scale, alpha, ia2, tau;
   float c0, c1, c2;
   int vec_ok;        // all (N,7) pointers 16-byte aligned
+  int rev;           // tile order: workgroup b takes tile nb - 1 - b (chosen by loss_launch; results do not depend on it)
   // bbox-coder decode fused into the prologue (include/gd3d.h gd3d_prologue)
   int pro;
   int norm_bbox;
@@ -217,7 +243,9 @@ __global__ __launch_bounds__(TILE) void fused_kernel(const LossArgs a_in) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform: scalar branches below
-  const long long base = (long long)blockIdx.x * TILE;
+  // every per-tile index (rows, partial sums) follows the tile, not the workgroup: the order changes no result
+  const unsigned tile = a.rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const long long base = (long long)tile * TILE;
   const long long rows_left = a.n - base;
   const bool full = rows_left >= TILE;
   const bool fast = full && a.vec_ok;  // workgroup-uniform
@@ -335,16 +363,16 @@ __global__ __launch_bounds__(TILE) void fused_kernel(const LossArgs a_in) {
       }
     }
     if (a.fin == nullptr) {
-      a.partials[blockIdx.x] = bsum;
+      a.partials[tile] = bsum;
       if (a.wsel) {
-        a.partials[a.nbp + blockIdx.x] = asum;
-        a.partials[2 * a.nbp + blockIdx.x] = fany;   // > 0: some weight of this tile is > 0
+        a.partials[a.nbp + tile] = asum;
+        a.partials[2 * a.nbp + tile] = fany;   // > 0: some weight of this tile is > 0
       }
     } else {   // handed to the last workgroup: write-through (sc1) stores, see the finish below
-      __hip_atomic_store(a.partials + blockIdx.x, bsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(a.partials + tile, bsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (a.wsel) {
-        __hip_atomic_store(a.partials + a.nbp + blockIdx.x, asum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(a.partials + 2 * a.nbp + blockIdx.x, fany, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.partials + a.nbp + tile, asum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.partials + 2 * a.nbp + tile, fany, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
   }
@@ -1065,6 +1093,7 @@ struct Geometry {
   unsigned tgrid;  // one workgroup per 256-pair tile
   // profiling only (gd3d_loss_fused_timed): events bound to THIS dispatch, see launch_one
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  bool reuse = false;  // the previous fused launch on this stream read the same target: no occupancy cap (MIN_LDS above)
 };
 
 template <int LOSS, int FUN, bool FLAG, bool GT>
@@ -1072,7 +1101,7 @@ static void launch_one(const Geometry& g, hipStream_t s, const LossArgs& a) {
   size_t lds = (size_t)(2 * TILE_F + 32 + (a.w7 != nullptr ? TILE_F : 0)) * sizeof(float);
   constexpr int min_lds = LOSS == GD3D_GWD3D ? MIN_LDS_GWD : (LOSS == GD3D_KLD3D ? MIN_LDS_KLD :
                           (LOSS == GD3D_BD3D ? MIN_LDS_BD : MIN_LDS));
-  if (lds < (size_t)min_lds) lds = (size_t)min_lds;   // occupancy cap (see MIN_LDS above)
+  if (!g.reuse && lds < (size_t)min_lds) lds = (size_t)min_lds;   // occupancy cap (see MIN_LDS above)
   // with (N,7) weights a workgroup keeps three tiles in flight: 5 per CU for every loss (10 M pairs, fixed placement,
   // 7/6/5/4/3 per CU: kld3d 185.5/185.4/179.8/180.9/202.7 us, bd3d 185.8/184.7/178.0/177.9/204.9, gwd3d 185.0/185.2/182.3/182.7/201.4)
   if (a.w7 != nullptr && lds < (size_t)MIN_LDS_W7) lds = (size_t)MIN_LDS_W7;
@@ -1201,6 +1230,29 @@ int gd3d_loss_fused_one_launch(const gd3d_params* p, const gd3d_prologue* pro, c
 
 int64_t gd3d_one_launch_max_n(void) { return 64 * (int64_t)TILE; }
 
+// Tile order of the fused launch.  Callers evaluate several losses against ONE target back to back (the benchmark step:
+// gwd3d, kld3d, bd3d); a launch on the same target and n as the previous fused launch of its stream walks the tiles
+// opposite to it, so that it starts on the target rows that launch read last, which are still in the Infinity Cache
+// (DMA_AUX_TARGET), and runs without the occupancy cap (MIN_LDS).  Any other launch ascends, capped.  One record per stream; calls may come from several threads.  Under graph
+// capture the order is fixed at capture time: a graph of an odd number of such launches, replayed back to back, starts
+// each replay in the direction its previous replay started in, and its first launch loses the reuse.
+static bool next_tile_order_reversed(hipStream_t s, const float* target, int64_t n, bool* reuse) {
+  struct Last {
+    const float* target;
+    int64_t n;
+    bool rev;
+  };
+  static std::mutex mu;
+  static std::unordered_map<hipStream_t, Last> last;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = last.find(s);
+  *reuse = it != last.end() && it->second.target == target && it->second.n == n;
+  const bool rev = *reuse && !it->second.rev;
+  if (it == last.end() && last.size() >= 256) last.clear();   // stream handles of destroyed streams: keep the table small
+  last[s] = Last{target, n, rev};
+  return rev;
+}
+
 static int loss_launch(const gd3d_params* p, const gd3d_prologue* pro, const float* pred, const float* target,
                        const float* row_weight, const float* weight7, int64_t n, float scale, float* loss,
                        float* loss_sum, float* grad_pred, float* grad_target, void* workspace, void* stream,
@@ -1269,12 +1321,15 @@ static int loss_launch(const gd3d_params* p, const gd3d_prologue* pro, const flo
   const uintptr_t bits = (uintptr_t)pred | (uintptr_t)target | (uintptr_t)grad_pred | (uintptr_t)grad_target |
                          (uintptr_t)weight7;
   a.vec_ok = (bits & 15) == 0;
+  bool reuse = false;
+  a.rev = next_tile_order_reversed(s, target, n, &reuse) ? 1 : 0;
   const bool gt = grad_target != nullptr;
   const bool flag = p->flag != 0;
   Geometry grid;
   grid.tgrid = (unsigned)nb;
   grid.ev_start = (hipEvent_t)start_event;
   grid.ev_stop = (hipEvent_t)stop_event;
+  grid.reuse = reuse;
   hipError_t e;
   switch (p->loss_type) {
     case GD3D_GWD3D: e = launch_fun<GD3D_GWD3D>(p->fun, flag, gt, grid, s, a); break;
