@@ -17,12 +17,15 @@ LIB_PATH = os.path.join(PKG_DIR, 'libgd3d.so')
 ARCH = 'gfx950'
 
 # per-translation-unit flags:
-#  * gd3d_loss.hip: 1-ulp v_rcp/v_sqrt instead of the ~10-instruction correctly-rounded sequences
+#  * gd3d_loss.hip, gd3d_anchor_head.hip, gd3d_center_head.hip (the GD-loss kernels, one unit per kernel family, compiled
+#    in parallel): 1-ulp v_rcp/v_sqrt instead of the ~10-instruction correctly-rounded sequences
 #    (the losses are graded at 1e-5; the kernel must stay HBM-bound, not VALU-bound);
 #  * rbox.hip: correctly-rounded IEEE division/sqrt and NO fma contraction, because the NMS keep
 #    indices must be bit-identical to a CPU evaluation of the same fp32 operation sequence.
 SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'gd3d_loss.hip': ['-fno-hip-fp32-correctly-rounded-divide-sqrt', '-ffp-contract=fast'],
+    'gd3d_anchor_head.hip': ['-fno-hip-fp32-correctly-rounded-divide-sqrt', '-ffp-contract=fast'],
+    'gd3d_center_head.hip': ['-fno-hip-fp32-correctly-rounded-divide-sqrt', '-ffp-contract=fast'],
     'rbox.hip': ['-ffp-contract=off'],
     'voxel_scatter.hip': [],
     'voxel_index.hip': [],                     # rocPRIM radix sort + scan between hand-written kernels

@@ -15,6 +15,7 @@
 // that already has torch's); training-size calls (< 64 tiles) run on the calling thread.
 #define GD3D_HOST_TWIN 1
 #include "gd3d_device.h"
+#include "gd3d_instances.h"
 
 #include <algorithm>
 #include <cstring>
@@ -76,38 +77,12 @@ void run_tiles(const Job& j, int64_t t0, int64_t t1) {
 
 using TileFn = void (*)(const Job&, int64_t, int64_t);
 
-template <int LOSS, int FUN>
-TileFn pick_flag_gt(bool flag, bool gt) {
-  switch ((flag ? 2 : 0) | (gt ? 1 : 0)) {
-    case 0: return run_tiles<LOSS, FUN, false, false>;
-    case 1: return run_tiles<LOSS, FUN, false, true>;
-    case 2: return run_tiles<LOSS, FUN, true, false>;
-    default: return run_tiles<LOSS, FUN, true, true>;
-  }
-}
-
-template <int LOSS>
-TileFn pick_fun(int fun, bool flag, bool gt) {
-  return fun == GD3D_FUN_LOG1P ? pick_flag_gt<LOSS, GD3D_FUN_LOG1P>(flag, gt) : pick_flag_gt<LOSS, GD3D_FUN_NONE>(flag, gt);
-}
-
-// the instantiation table of csrc/gd3d_loss.hip (launch_fun / launch_kfiou): kfiou3d ignores `sqrt` (ref :228)
+// the instance from the table every launcher uses (csrc/gd3d_instances.h); GT is this call site's own two-way branch
 TileFn pick(const gd3d_params* p, bool gt) {
-  const bool flag = p->flag != 0;
-  switch (p->loss_type) {
-    case GD3D_GWD3D: return pick_fun<GD3D_GWD3D>(p->fun, flag, gt);
-    case GD3D_KLD3D: return pick_fun<GD3D_KLD3D>(p->fun, flag, gt);
-    case GD3D_BD3D: return pick_fun<GD3D_BD3D>(p->fun, flag, gt);
-    case GD3D_JD3D: return pick_fun<GD3D_JD3D>(p->fun, flag, gt);
-    case GD3D_KLD3D_SYMMAX: return pick_fun<GD3D_KLD3D_SYMMAX>(p->fun, flag, gt);
-    case GD3D_KLD3D_SYMMIN: return pick_fun<GD3D_KLD3D_SYMMIN>(p->fun, flag, gt);
-    default:
-      switch (p->fun) {
-        case GD3D_FUN_EXPM1: return pick_flag_gt<GD3D_KFIOU3D, GD3D_FUN_EXPM1>(false, gt);
-        case GD3D_FUN_NLOG: return pick_flag_gt<GD3D_KFIOU3D, GD3D_FUN_NLOG>(false, gt);
-        default: return pick_flag_gt<GD3D_KFIOU3D, GD3D_FUN_NONE>(false, gt);
-      }
-  }
+  return with_instance(p->loss_type, p->fun, p->flag != 0, [&](auto inst) -> TileFn {
+    using I = decltype(inst);
+    return gt ? run_tiles<I::loss, I::fun, I::flag, true> : run_tiles<I::loss, I::fun, I::flag, false>;
+  });
 }
 
 int team_size(int32_t nthreads, int64_t tiles) {   // at least 16 tiles (4096 pairs) per thread; < 64 tiles run inline
@@ -132,12 +107,7 @@ int gd3d_loss_fused_cpu(const gd3d_params* p, const float* pred, const float* ta
   if (row_weight != nullptr && weight7 != nullptr) return GD3D_E_BADARG;
   if (p == nullptr || n < 0) return GD3D_E_BADARG;
   if (n > 0 && (pred == nullptr || target == nullptr)) return GD3D_E_BADARG;
-  if (p->loss_type < 0 || p->loss_type >= GD3D_NUM_LOSS_TYPES) return GD3D_E_BADARG;
-  if (p->loss_type == GD3D_KFIOU3D) {
-    if (p->fun != GD3D_FUN_NONE && p->fun != GD3D_FUN_EXPM1 && p->fun != GD3D_FUN_NLOG) return GD3D_E_BADARG;
-  } else if (p->fun != GD3D_FUN_NONE && p->fun != GD3D_FUN_LOG1P) {
-    return GD3D_E_BADARG;
-  }
+  if (check_instance(p->loss_type, p->fun) != 0) return GD3D_E_BADARG;
   if (loss_sum != nullptr && workspace == nullptr) return GD3D_E_BADARG;
   const int64_t tiles = (n + TILE - 1) / TILE;
   if (tiles > 0x7fffffffLL) return GD3D_E_TOOLARGE;

@@ -1,8 +1,9 @@
 """Every (loss type, fun, flag) instance of the GD-loss kernels, written out once for the suites that sweep them.
 
-The kernels of csrc/gd3d_loss.hip are templates: `fused_kernel`, `head_anchor_kernel` and `head_center_kernel` are compiled
-once per (loss type, fun, flag), where flag is `normalize` for gwd3d and `sqrt` for the others.  The fun domain is the one
-the launchers enforce (GDLoss.__init__ asserts the same, gaussian_distance_loss.py:267-270): kfiou3d takes
+The GD-loss kernels are templates: `fused_kernel` (csrc/gd3d_loss.hip), `head_anchor_kernel` (csrc/gd3d_anchor_head.hip)
+and `head_center_kernel` (csrc/gd3d_center_head.hip) are compiled once per (loss type, fun, flag), where flag is `normalize`
+for gwd3d and `sqrt` for the others; csrc/gd3d_instances.h is the one table every launcher takes its instance from.  The fun
+domain is the one its check_instance() enforces (GDLoss.__init__ asserts the same, gaussian_distance_loss.py:267-270): kfiou3d takes
 {none, expm1, nlog}, every other loss {none, log1p}.  kfiou3d accepts `sqrt` and ignores it (ref :228): it has one
 instance per fun, compiled with the flag off.  tests/test_gd_instances.py derives this set from the product and asserts it
 equals INSTANCES, so a new loss type or fun fails there until it is listed here.

@@ -1,6 +1,7 @@
 """tests/gd_instances.py lists every compiled (loss type, fun, flag) instance of the GD-loss kernels.  Here the same set is
 derived from the product itself: its loss types and funs (gd_loss.LOSS_TYPES / FUNS), the fun domain that GDLoss.__init__
-asserts and the `_cpu` twin's launcher enforces (the HIP launchers share its rule), and the flags.  A loss type or fun the
+asserts and the `_cpu` twin's launcher enforces (check_instance() of csrc/gd3d_instances.h, which the HIP launchers call
+too), and the flags.  A loss type or fun the
 product gains fails here until the list covers it.  CPU only."""
 import ctypes
 
@@ -12,7 +13,7 @@ import gd_instances
 
 
 def _domain(lt, fun):
-    """the fun domain per loss type (gaussian_distance_loss.py:267-270; loss_launch in csrc/gd3d_loss.hip)"""
+    """the fun domain per loss type (gaussian_distance_loss.py:267-270; check_instance in csrc/gd3d_instances.h)"""
     return fun in (('nlog', 'expm1', 'none') if lt == 'kfiou3d' else ('log1p', 'none'))
 
 

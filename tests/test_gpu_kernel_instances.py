@@ -1,7 +1,8 @@
 """Every compiled instance of the GD-loss kernels against the fp64 oracles (tests/gd_instances.py lists them).
 
-`head_anchor_kernel`, `head_center_kernel` and `fused_kernel` (csrc/gd3d_loss.hip) are compiled per (loss type, fun, flag),
-and `fused_kernel` also per target gradient, with an option-free gwd3d form besides.  Each instance runs here with the
+`head_anchor_kernel` (csrc/gd3d_anchor_head.hip), `head_center_kernel` (csrc/gd3d_center_head.hip) and `fused_kernel`
+(csrc/gd3d_loss.hip) are compiled per (loss type, fun, flag) of the table in csrc/gd3d_instances.h, and `fused_kernel` also
+per target gradient, with an option-free gwd3d form besides.  Each instance runs here with the
 reference defaults and with seeded non-default hyper-parameters (alpha, tau, center_offset reach the head launchers through
 their own argument structs), at positive counts on both sides of the 256-thread tile.  References and bounds are the
 suite's own:
