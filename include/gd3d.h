@@ -608,6 +608,96 @@ int vox_scatter_backward_grouped(const float* grad_vox, const int32_t* order, co
                                  const int32_t* argmax, int64_t n, int32_t c, int64_t v, int reduce,
                                  float* grad_feats, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Voxel-set-abstraction ops of PV-RCNN (an addition inside ABI 6): stacked ball query, point grouping forward / backward,
+ * the two fused into one launch, and furthest point sampling.  Replace the reference's own CUDA extension
+ *   /root/reference/mmdet3d_gaussian/ops/vsa/src/ball_query.cu:12-72 (ball_query_kernel),
+ *   src/group_points.cu:14-49 (group_points_grad_kernel), :52-90 (group_points_kernel),
+ *   src/sampling.cu:22-152 (furthest_point_sampling_kernel)
+ * behind ops/vsa/group_points.py (BallQuery :7-39, GroupingOperation :42-94, QueryAndGroup :97-183) and
+ * ops/vsa/sample_points.py:7-33.
+ *
+ * Stacked data: xyz (N,3) fp32 = the points of B samples one after another, xyz_batch_cnt (B) int32 their counts; new_xyz (M,3)
+ * fp32 the query centres with new_xyz_batch_cnt (B) int32.  A query sees the points of its own sample only and every index is
+ * LOCAL to the sample.  The kernels find the samples' start offsets from the count arrays themselves (no host prefix sum, no
+ * host read).  Nothing validates the counts on the host; instead every count is clamped to [0, rows left in the array] and
+ * every gathered index to [0, points of its sample), so inconsistent counts or indices cannot read or write outside the
+ * buffers.  Query rows that the counts do not cover are empty balls (forward) and pass no gradient (backward).
+ *
+ * Ball query: radius2 = radius * radius (fp32); walking the sample's points in ascending index,
+ *   d2 = (nx-x)*(nx-x) + (ny-y)*(ny-y) + (nz-z)*(nz-z)   fp32, left to right, no fma contraction;
+ * the first nsample points with d2 < radius2 (strict) fill idx[m,:], the slots past the member count repeat the first member;
+ * an empty ball gives idx[m,:] = 0 and empty_mask[m] = 1.  cnt[m] = min(members, nsample).  idx (M,nsample) int32; cnt (M)
+ * int32 and empty_mask (M) bytes are nullable.  1 <= nsample <= 1024, else GD3D_E_TOOLARGE.
+ * ---------------------------------------------------------------------------------- */
+int gd3d_vsa_ball_query(const float* xyz, const int32_t* xyz_batch_cnt, const float* new_xyz,
+                        const int32_t* new_xyz_batch_cnt, int32_t B, int64_t N, int64_t M, float radius,
+                        int32_t nsample, int32_t* idx, int32_t* cnt, uint8_t* empty_mask, void* stream);
+
+/* Grouping: out[m, c, s] = features[start_b + idx[m, s], c], features (N,C) fp32, out (M,C,nsample) (a sample without points
+ * gives zeros).  Backward: grad_features[start_b + idx[m, s], c] += grad_out[m, c, s]; grad_features (N,C) is zero-filled
+ * by the call.  The sums are float atomics: the last bits depend on the order of arrival, as with the reference's atomicAdd. */
+int gd3d_vsa_group(const float* features, const int32_t* features_batch_cnt, const int32_t* idx,
+                   const int32_t* idx_batch_cnt, int32_t B, int64_t N, int64_t M, int32_t C, int32_t nsample,
+                   float* out, void* stream);
+int gd3d_vsa_group_backward(const float* grad_out, const int32_t* idx, const int32_t* idx_batch_cnt,
+                            const int32_t* features_batch_cnt, int32_t B, int64_t N, int64_t M, int32_t C,
+                            int32_t nsample, float* grad_features, void* stream);
+
+/* QueryAndGroup.forward in ONE launch: the ball query, then out (M, (use_xyz ? 3 : 0) + C, nsample) = [grouped xyz minus the
+ * query centre (use_xyz), grouped features (features != NULL, C > 0)], every channel of an empty ball zero.  idx / cnt /
+ * empty_mask as gd3d_vsa_ball_query (idx required).  Its backward wrt features reads grad_out (M, c_off + C, nsample) from
+ * channel c_off (0 or 3) on; the padded slots s >= cnt[m] all name the first member and are summed before ONE add; rows with
+ * cnt[m] == 0 pass nothing.  grad_features (N,C) is zero-filled by the call. */
+int gd3d_vsa_query_and_group(const float* xyz, const int32_t* xyz_batch_cnt, const float* new_xyz,
+                             const int32_t* new_xyz_batch_cnt, const float* features, int32_t B, int64_t N,
+                             int64_t M, int32_t C, float radius, int32_t nsample, int32_t use_xyz, float* out,
+                             int32_t* idx, int32_t* cnt, uint8_t* empty_mask, void* stream);
+int gd3d_vsa_query_and_group_backward(const float* grad_out, const int32_t* idx, const int32_t* cnt,
+                                      const int32_t* new_xyz_batch_cnt, const int32_t* xyz_batch_cnt, int32_t B,
+                                      int64_t N, int64_t M, int32_t C, int32_t nsample, int32_t c_off,
+                                      float* grad_features, void* stream);
+
+/* Furthest point sampling, all samples in one launch (one workgroup per sample).  Pick 0 is index 0; pick j is the arg max over
+ * the sample of the running min of the squared distances (expression above) to picks 0..j-1, and of exactly equal
+ * distances the LOWEST index wins.  A sample with n < npoint points returns its n picks cyclically (out[j] = out[j % n]), one
+ * with n == 0 zeros.
+ *   gd3d_vsa_fps        : xyz (B,n,3) -> out (B,npoint) int32
+ *   gd3d_vsa_fps_stacked: xyz (N,3) + xyz_batch_cnt (B) -> out (B,npoint) int64, indices local to the sample
+ * workspace: gd3d_vsa_fps_workspace_bytes(N total rows) bytes (the running minimum of the points beyond the
+ * gd3d_vsa_fps_register_points() = 16384 per sample that live in registers); needs no initialisation. */
+int gd3d_vsa_fps_register_points(void);
+size_t gd3d_vsa_fps_workspace_bytes(int64_t N);
+int gd3d_vsa_fps(const float* xyz, int32_t B, int32_t n, int32_t npoint, int32_t* out, void* workspace,
+                 void* stream);
+int gd3d_vsa_fps_stacked(const float* xyz, const int32_t* xyz_batch_cnt, int32_t B, int64_t N, int32_t npoint,
+                         int64_t* out, void* workspace, void* stream);
+
+/* `_cpu` twins (csrc/vsa_cpu.cpp): the same contracts on HOST memory, plain loops over the same fp32 operation sequence
+ * compiled with the same -ffp-contract=off, so idx, cnt, the mask and the FPS picks are BIT-IDENTICAL to the kernels' and the
+ * grouped outputs (copies and one subtraction) too.  The backward twins add in ascending (m, s) order.  nthreads <= 0:
+ * std::thread::hardware_concurrency(). */
+int gd3d_vsa_ball_query_cpu(const float* xyz, const int32_t* xyz_batch_cnt, const float* new_xyz,
+                            const int32_t* new_xyz_batch_cnt, int32_t B, int64_t N, int64_t M, float radius,
+                            int32_t nsample, int32_t* idx, int32_t* cnt, uint8_t* empty_mask, int32_t nthreads);
+int gd3d_vsa_group_cpu(const float* features, const int32_t* features_batch_cnt, const int32_t* idx,
+                       const int32_t* idx_batch_cnt, int32_t B, int64_t N, int64_t M, int32_t C, int32_t nsample,
+                       float* out, int32_t nthreads);
+int gd3d_vsa_group_backward_cpu(const float* grad_out, const int32_t* idx, const int32_t* idx_batch_cnt,
+                                const int32_t* features_batch_cnt, int32_t B, int64_t N, int64_t M, int32_t C,
+                                int32_t nsample, float* grad_features);
+int gd3d_vsa_query_and_group_cpu(const float* xyz, const int32_t* xyz_batch_cnt, const float* new_xyz,
+                                 const int32_t* new_xyz_batch_cnt, const float* features, int32_t B, int64_t N,
+                                 int64_t M, int32_t C, float radius, int32_t nsample, int32_t use_xyz, float* out,
+                                 int32_t* idx, int32_t* cnt, uint8_t* empty_mask, int32_t nthreads);
+int gd3d_vsa_query_and_group_backward_cpu(const float* grad_out, const int32_t* idx, const int32_t* cnt,
+                                          const int32_t* new_xyz_batch_cnt, const int32_t* xyz_batch_cnt, int32_t B,
+                                          int64_t N, int64_t M, int32_t C, int32_t nsample, int32_t c_off,
+                                          float* grad_features);
+int gd3d_vsa_fps_cpu(const float* xyz, int32_t B, int32_t n, int32_t npoint, int32_t* out, int32_t nthreads);
+int gd3d_vsa_fps_stacked_cpu(const float* xyz, const int32_t* xyz_batch_cnt, int32_t B, int64_t N, int32_t npoint,
+                             int64_t* out, int32_t nthreads);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

@@ -10,6 +10,8 @@
                                  head-level regression slices with the decode fused into the kernel
                                  (gd_anchor3d_head.py:95-161, gd_centerpoint_head.py:413-434)
   * ``Scatter`` / ``scatter_index`` / ``scatter_reduce`` — §8 f4: ops/voxel/scatter.py
+  * ``QueryAndGroup`` / ``ball_query`` / ``grouping`` / ``furthest_point_sample`` / ``furthest_point_sample_stacked`` — PV-RCNN's
+                                 voxel-set-abstraction ops: ops/vsa/group_points.py, ops/vsa/sample_points.py
   * ``GraphedStep``            — a launch-bound loss slice, forward and backward, captured once as a hipGraph and replayed
 Everything outside §8 that earlier rounds built (frozen, DESIGN_EXTRAS.md) lives in ``mmdet3d_gaussian_amd.extras``.
 
@@ -30,6 +32,7 @@ from .coders import CenterPointBBoxCoderRev, CenterPointBBoxYawCoder, DeltaXYZWL
 from .graphed import GraphedStep
 from .evaluation import match_coco, trans_bev
 from .scatter import Scatter, scatter_index, scatter_reduce
+from .vsa import QueryAndGroup, ball_query, furthest_point_sample, furthest_point_sample_stacked, grouping
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
                         anchor_head_decoded_loss_fused, center_head_gd_loss, center_head_losses)
 from . import extras
@@ -48,4 +51,5 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'trans_bev', 'match_coco', 'sharded', 'build', 'load_library', 'lib_path', 'host_glue', 'set_host_glue',
            'CenterPointBBoxCoderRev', 'CenterPointBBoxYawCoder', 'DeltaXYZWLHRBBoxCoder', 'PointBBoxYawCoder', 'GraphedStep',
            'anchor_decoded_gd_loss', 'anchor_head_decoded_loss', 'anchor_head_decoded_loss_fused', 'anchor_head_bbox_loss', 'center_head_gd_loss',
-           'center_head_losses', 'Scatter', 'scatter_index', 'scatter_reduce', 'extras']
+           'center_head_losses', 'Scatter', 'scatter_index', 'scatter_reduce', 'QueryAndGroup', 'ball_query', 'grouping',
+           'furthest_point_sample', 'furthest_point_sample_stacked', 'extras']

@@ -99,6 +99,7 @@ class AnchorTargetsDesc(ctypes.Structure):
 
 # every symbol include/gd3d.h declares: name -> (restype, argtypes)
 _vp, _i64, _f32, _int, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_size_t
+_i32 = ctypes.c_int32
 SYMBOLS = {
     'gd3d_loss_workspace_bytes': (_sz, [_i64]),
     'gd3d_loss_fused': (_int, [ctypes.POINTER(Params), _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -209,6 +210,22 @@ SYMBOLS = {
                                         ctypes.c_int32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     'gd3d_anchor_cls_dir_loss_dyn': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, _f32, _f32, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_vsa_ball_query': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp]),
+    'gd3d_vsa_group': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp]),
+    'gd3d_vsa_group_backward': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp]),
+    'gd3d_vsa_query_and_group': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_vsa_query_and_group_backward': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    'gd3d_vsa_fps_register_points': (_int, []),
+    'gd3d_vsa_fps_workspace_bytes': (_sz, [_i64]),
+    'gd3d_vsa_fps': (_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'gd3d_vsa_fps_stacked': (_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
+    'gd3d_vsa_ball_query_cpu': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _i32]),
+    'gd3d_vsa_group_cpu': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _i32]),
+    'gd3d_vsa_group_backward_cpu': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp]),
+    'gd3d_vsa_query_and_group_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i32]),
+    'gd3d_vsa_query_and_group_backward_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp]),
+    'gd3d_vsa_fps_cpu': (_int, [_vp, _i32, _i32, _i32, _vp, _i32]),
+    'gd3d_vsa_fps_stacked_cpu': (_int, [_vp, _vp, _i32, _i64, _i32, _vp, _i32]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 

@@ -31,6 +31,7 @@ SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'voxel_index.hip': [],                     # rocPRIM radix sort + scan between hand-written kernels
     'eval_match.hip': ['-ffp-contract=off'],
     'coders.hip': ['-ffp-contract=off'],      # same rounding sequence as the torch elementwise ops it replaces
+    'vsa.hip': ['-ffp-contract=off'],         # ball-query membership and FPS arg-max decisions replay bit for bit in vsa_cpu.cpp
 }
 # The frozen round-3 extras OUTSIDE §8 (DESIGN_EXTRAS.md; include/gd3d_extras.h): a library of their own since round 6,
 # libgd3d_extras.so, linked against libgd3d.so (the inference slices call its rnms_* entry points) and loaded only by
@@ -54,6 +55,7 @@ COMMON = ['--offload-arch=' + ARCH, '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno
 HOST_SOURCES = {
     'gd3d_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=fast', '-pthread'],
     'rbox_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],   # same single-operation sequence as rbox.hip: bit-identical decisions
+    'vsa_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],    # same for vsa.hip: idx, cnt, mask and FPS picks bit-identical
 }
 HOST_COMMON = ['-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 
