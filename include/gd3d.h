@@ -698,6 +698,67 @@ int gd3d_vsa_fps_cpu(const float* xyz, int32_t B, int32_t n, int32_t npoint, int
 int gd3d_vsa_fps_stacked_cpu(const float* xyz, const int32_t* xyz_batch_cnt, int32_t B, int64_t N, int32_t npoint,
                              int64_t* out, int32_t nthreads);
 
+/* ------------------------------------------------------------------------------------
+ * Point-in-rotated-box ops (an addition inside ABI 6): mmdet3d 1.0's roiaware_pool3d `points_in_boxes_part` and
+ * `points_in_boxes_all` (third party, CUDA only), PointwiseMaskHead.get_targets
+ * (models/roi_heads/mask_heads/pointwise_mask_head.py:62-92) for a whole batch in one launch, and the dense RoI grid points of
+ * Batch3DRoIGridExtractor.get_dense_grid_points (models/roi_heads/roi_extractors/batch_roigrid_extractor.py:56-71).
+ *
+ * Data: points (N,3) fp32 = the points of B samples one after another with pts_batch_cnt (B) int32; boxes (B,T,7) fp32 dense,
+ * a box [x, y, z, dx, dy, dz, rz] with (x, y, z) the BOTTOM centre; box_cnt (B) int32 nullable: rows t >= box_cnt[b] of sample
+ * b are ignored, NULL tests all T.  The kernels find the samples' start offsets from the count array themselves (no host
+ * prefix sum, no host read).  Nothing validates counts on the host: every point count is clamped to [0, rows left in the
+ * array] and every box count to [0, T].  Point rows beyond the counts' sum belong to no sample: they are in no box.
+ *
+ * Membership (mmdet3d's check_pt_in_box3d), every step ONE fp32 operation in this order, no fma contraction:
+ *   hz = dz * 0.5f;  czm = z + hz;   |pz - czm| <= hz            (z faces INCLUSIVE)
+ *   (s, c) = fixed-sequence sincos of -rz (the polynomial of the rotated NMS, no libm)
+ *   sx = px - x;  sy = py - y;   lx = sx * c + sy * (-s);   ly = sx * s + sy * c
+ *   lx > -hx && lx < hx && ly > -hy && ly < hy                   (hx = dx * 0.5f, hy = dy * 0.5f; x / y faces STRICT)
+ * As the comparisons are written: zero or negative dx or dy, or negative dz, contain nothing (so do zero-padded rows); a
+ * point with a NaN coordinate is in no box; boxes as tall as z = -1e8, dz = 2e8 work.
+ *
+ * gd3d_pib_part : box_idx (N) int32 = the LOWEST box index of the point's sample that contains it, -1 if none.
+ * gd3d_pib_all  : flags (N,T) row-major, elem_size 1 (bytes 0 / 1) or 4 (int32 0 / 1); columns t >= box_cnt[b] are written
+ *                 0: the call leaves no element unwritten.
+ * gd3d_pib_mask_targets : per point i = first of the gt_boxes that contains it, e = first of the ENLARGED boxes
+ *                 (z - extra_width, dx + 2 extra_width, dy + .., dz + .., each one fp32 operation) that does;
+ *                 seg_targets (N) int64 = i >= 0 ? gt_labels[b, i] : num_classes, and -1 where (i >= 0) != (e >= 0) (the
+ *                 reference's xor: a negative extra_width behaves as there).  gt_labels (B,T) int64.  box_idx (N) int32
+ *                 nullable receives i.
+ * gd3d_roi_grid_points : rois = R rows of roi_stride floats, the box at column first_col (as coder_roi_decode takes them);
+ *                 out (R, G^3, 3) fp32, 1 <= G <= 16; point (i, j, k), k fastest:
+ *                   u = (i + 0.5f) / G - 0.5f, v = (j + 0.5f) / G - 0.5f, w = (k + 0.5f) / G;  l = (u dx, v dy, w dz);
+ *                   x' = lx c - ly s, y' = lx s + ly c  (sincos of rz; clockwise != 0: x' = lx c + ly s, y' = ly c - lx s,
+ *                   the same sense and flag as coder_roi_decode);  out = (x' + x, y' + y, lz + z).
+ * gd3d_pib_box_tile / gd3d_pib_workgroup_points : boxes per LDS tile and points per workgroup of the kernels (the sizes at
+ *                 which they change path; for tests).
+ * All stream-ordered, caller-allocated outputs.  `_cpu` twins (csrc/pib_cpu.cpp): the same contracts on HOST memory over the
+ * same operation sequence, BIT-IDENTICAL results.  nthreads <= 0: std::thread::hardware_concurrency().
+ * ---------------------------------------------------------------------------------- */
+int gd3d_pib_box_tile(void);
+int gd3d_pib_workgroup_points(void);
+int gd3d_pib_part(const float* points, const int32_t* pts_batch_cnt, const float* boxes, const int32_t* box_cnt,
+                  int32_t B, int64_t N, int32_t T, int32_t* box_idx, void* stream);
+int gd3d_pib_all(const float* points, const int32_t* pts_batch_cnt, const float* boxes, const int32_t* box_cnt,
+                 int32_t B, int64_t N, int32_t T, void* flags, int32_t elem_size, void* stream);
+int gd3d_pib_mask_targets(const float* points, const int32_t* pts_batch_cnt, const float* gt_boxes,
+                          const int64_t* gt_labels, const int32_t* box_cnt, int32_t B, int64_t N, int32_t T,
+                          float extra_width, int32_t num_classes, int64_t* seg_targets, int32_t* box_idx,
+                          void* stream);
+int gd3d_roi_grid_points(const float* rois, int32_t roi_stride, int32_t first_col, int64_t R, int32_t G,
+                         int32_t clockwise, float* out, void* stream);
+int gd3d_pib_part_cpu(const float* points, const int32_t* pts_batch_cnt, const float* boxes, const int32_t* box_cnt,
+                      int32_t B, int64_t N, int32_t T, int32_t* box_idx, int32_t nthreads);
+int gd3d_pib_all_cpu(const float* points, const int32_t* pts_batch_cnt, const float* boxes, const int32_t* box_cnt,
+                     int32_t B, int64_t N, int32_t T, void* flags, int32_t elem_size, int32_t nthreads);
+int gd3d_pib_mask_targets_cpu(const float* points, const int32_t* pts_batch_cnt, const float* gt_boxes,
+                              const int64_t* gt_labels, const int32_t* box_cnt, int32_t B, int64_t N, int32_t T,
+                              float extra_width, int32_t num_classes, int64_t* seg_targets, int32_t* box_idx,
+                              int32_t nthreads);
+int gd3d_roi_grid_points_cpu(const float* rois, int32_t roi_stride, int32_t first_col, int64_t R, int32_t G,
+                             int32_t clockwise, float* out, int32_t nthreads);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

@@ -226,6 +226,16 @@ SYMBOLS = {
     'gd3d_vsa_query_and_group_backward_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp]),
     'gd3d_vsa_fps_cpu': (_int, [_vp, _i32, _i32, _i32, _vp, _i32]),
     'gd3d_vsa_fps_stacked_cpu': (_int, [_vp, _vp, _i32, _i64, _i32, _vp, _i32]),
+    'gd3d_pib_box_tile': (_int, []),
+    'gd3d_pib_workgroup_points': (_int, []),
+    'gd3d_pib_part': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp]),
+    'gd3d_pib_all': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp]),
+    'gd3d_pib_mask_targets': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _i32, _vp, _vp, _vp]),
+    'gd3d_roi_grid_points': (_int, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _vp]),
+    'gd3d_pib_part_cpu': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32]),
+    'gd3d_pib_all_cpu': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _i32]),
+    'gd3d_pib_mask_targets_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _i32, _vp, _vp, _i32]),
+    'gd3d_roi_grid_points_cpu': (_int, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _i32]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 
