@@ -395,11 +395,37 @@ static int channels_per_pass(int C, int nsample) {
   return cc > C ? (C > 0 ? C : 1) : cc;
 }
 
+// Dynamic LDS of a qag_kernel<MODE> launch: the point tile (scanning modes, 12288 B), the waves' idx rows (32 * nsample B) and
+// the waves' transpose buffers (grouping modes, 34816 B):
+//   MODE_QUERY        12288 + 32 * nsample  <= 45056 B
+//   MODE_QUERY_GROUP  47104 + 32 * nsample  >  64 KiB from nsample 577 on, 79872 B at MAX_NSAMPLE
+//   MODE_GROUP        34816 + 32 * nsample  >  64 KiB from nsample 961 on, 67584 B at MAX_NSAMPLE
+// (the backward: 17408 + 16 * nsample <= 33792 B).
+template <int MODE>
+constexpr size_t qag_lds_bytes(int nsample) {
+  return ((MODE != MODE_GROUP ? 3 * TILE : 0) + (size_t)QW * nsample + (MODE != MODE_QUERY ? (size_t)QW * XP : 0)) * 4;
+}
+static_assert(qag_lds_bytes<MODE_QUERY>(MAX_NSAMPLE) <= 65536, "the stand-alone query needs no raised dynamic-LDS limit");
+static_assert(qag_lds_bytes<MODE_QUERY_GROUP>(MAX_NSAMPLE) <= 160 * 1024 && qag_lds_bytes<MODE_GROUP>(MAX_NSAMPLE) <= 160 * 1024,
+              "the largest request must fit the 160 KiB LDS of a gfx950 CU");
+
 template <int MODE>
 static int launch_qag(const QagArgs& a, hipStream_t s) {
   const long long blocks = (a.M + QW - 1) / QW + a.B + 1;   // sum over samples of ceil(M_b / QW), bounded without reading the counts
   if (blocks > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  const size_t lds = ((MODE != MODE_GROUP ? 3 * TILE : 0) + (size_t)QW * a.nsample + (MODE != MODE_QUERY ? (size_t)QW * XP : 0)) * 4;
+  const size_t lds = qag_lds_bytes<MODE>(a.nsample);
+  if (lds > 65536) {   // beyond the default limit: raised once per device and instance, sized for MAX_NSAMPLE (a captured launch
+                       // never calls it: the warm-up did)
+    static bool attr_set[64] = {};
+    int devid = 0;
+    if (hipGetDevice(&devid) != hipSuccess) return GD3D_E_BADARG;
+    if (devid < 0 || devid >= 64 || !attr_set[devid]) {
+      const hipError_t e = hipFuncSetAttribute((const void*)qag_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)qag_lds_bytes<MODE>(MAX_NSAMPLE));
+      if (e != hipSuccess) return (int)e;
+      if (devid >= 0 && devid < 64) attr_set[devid] = true;
+    }
+  }
   hipLaunchKernelGGL((qag_kernel<MODE>), dim3((unsigned)blocks), dim3(QTHREADS), lds, s, a);
   return (int)hipGetLastError();
 }

@@ -23,7 +23,7 @@ def _forward(xyz, pc, new_xyz, qc, feats, radius, nsample, c, use_xyz):
 
 
 def _check_forward(kind, name, radius, nsample, c, use_xyz):
-    xyz, pc, new_xyz, qc, feats = _t(*(cases.crafted() if kind == 'crafted' else cases.stack(name)))
+    xyz, pc, new_xyz, qc, feats = _t(*cases.inputs(kind, name))
     out, idx, cnt, mask = _forward(xyz, pc, new_xyz, qc, feats, radius, nsample, c, use_xyz)
     r_out, r_idx, r_cnt, r_mask = cases.reference(kind, name, radius, nsample, c, use_xyz)
     assert idx.dtype == torch.int32 and mask.dtype == torch.bool and cnt.dtype == torch.int32 and out.dtype == torch.float32
@@ -62,6 +62,23 @@ def test_exactly_nsample_members_and_boundary_straddlers(members, nsample):
     the tile boundary: stopping early must not change idx, cnt or the tail"""
     cnt = _check_forward('crafted', '', cases.crafted_radius(members), nsample, 16, True)
     assert cnt[0] == min(members, nsample) and cnt[-1] == 0
+
+
+@pytest.mark.parametrize('nsample', cases.WIDE_NSAMPLE)
+def test_twin_matches_oracle_above_one_wave_of_slots(nsample):
+    """nsample 33 to 1024 (vsa_cases.WIDE_NSAMPLE) on 2300, 700 and 0 points: balls that fill two tiles after their first member,
+    padded tails of 1 to 990 slots, empty balls"""
+    for radius in (cases.R_ALL, cases.R_MID):
+        want = cases.wide_conditions(radius, nsample)
+        assert np.array_equal(_check_forward('wide', '', radius, nsample, 3, True), want)
+
+
+@pytest.mark.parametrize('c,use_xyz', [(0, True)] + [(c, u) for c in (1, 17, 67) for u in (True, False)])
+@pytest.mark.parametrize('nsample', [64, 128, 1024])
+def test_twin_matches_oracle_over_channel_counts_at_large_nsample(nsample, c, use_xyz):
+    for radius in (cases.R_ALL, cases.R_MID):
+        cases.wide_conditions(radius, nsample)
+        _check_forward('wide', '', radius, nsample, c, use_xyz)
 
 
 def test_point_at_exactly_the_radius_is_excluded():
@@ -122,6 +139,72 @@ def test_grouping_autograd_on_cpu():
                                     nondet_tol=0.0, fast_mode=True)
 
 
+@pytest.mark.parametrize('c', [1, 17])
+@pytest.mark.parametrize('nsample', [65, 128, 701, 1024])
+def test_backward_is_exact_on_integer_gradients_at_large_nsample(nsample, c):
+    """every point of the sample a member: full balls of up to 1024 slots in sample 0, in sample 1 (700 points) a tail of 1 slot at
+    nsample 701 and of 324 at 1024.  At most 12 * 1024 integers of magnitude <= 8 meet in one sum: exact in fp32 in any order."""
+    want_cnt = cases.wide_conditions(cases.R_ALL, nsample)
+    assert (want_cnt[7:10] == min(700, nsample)).all()
+    xyz, pc, new_xyz, qc, feats = _t(*cases.wide())
+    _, r_idx, _, r_mask = cases.reference('wide', '', cases.R_ALL, nsample, 0, True)
+    gout = np.random.RandomState(1000 * c + nsample).randint(-8, 9, (new_xyz.shape[0], 3 + c, nsample)).astype(np.float32)
+    f = feats[:, :c].contiguous().requires_grad_()
+    out, idx = amd.QueryAndGroup(cases.R_ALL, nsample)(xyz, pc, new_xyz, qc, f)
+    assert np.array_equal(idx.numpy(), r_idx)
+    grad, = torch.autograd.grad(out, f, torch.from_numpy(gout))
+    n = xyz.shape[0]
+    want, _, _ = vsa_ref.grouping_backward(gout[:, 3:], r_idx, qc.numpy(), pc.numpy(), n, ~r_mask)
+    assert np.abs(want).max() > 8 and np.array_equal(grad.numpy().astype(np.float64), want)
+    f2 = f.detach().clone().requires_grad_()
+    g2, = torch.autograd.grad(amd.grouping(f2, pc, idx, qc), f2, torch.from_numpy(gout[:, 3:].copy()))
+    want2, _, _ = vsa_ref.grouping_backward(gout[:, 3:], r_idx, qc.numpy(), pc.numpy(), n)
+    assert not np.array_equal(want2, want) and np.array_equal(g2.numpy().astype(np.float64), want2)
+
+
+def test_backward_with_normal_gradients_stays_inside_the_rounding_bound_at_nsample_128():
+    """An fp32 sum of k terms taken in any order differs from the exact sum by at most k * 2^-24 * sum|terms|; k and the sum come
+    from the oracle, nothing is measured.  Full balls, and tails of 3 to 94 slots."""
+    xyz, pc, new_xyz, qc, feats = _t(*cases.wide())
+    for radius in (cases.R_MID, cases.R_ALL):
+        cases.wide_conditions(radius, 128)
+        _, r_idx, _, r_mask = cases.reference('wide', '', radius, 128, 0, True)
+        gout = np.random.RandomState(17128).standard_normal((new_xyz.shape[0], 20, 128)).astype(np.float32)
+        f = feats[:, :17].contiguous().requires_grad_()
+        out, _ = amd.QueryAndGroup(radius, 128)(xyz, pc, new_xyz, qc, f)
+        grad, = torch.autograd.grad(out, f, torch.from_numpy(gout))
+        want, num, mag = vsa_ref.grouping_backward(gout[:, 3:], r_idx, qc.numpy(), pc.numpy(), xyz.shape[0], ~r_mask)
+        err = np.abs(grad.numpy().astype(np.float64) - want)
+        assert num.max() >= 6 and (err <= num[:, None] * 2.0 ** -24 * mag).all()
+        assert (grad.numpy()[num == 0] == 0).all()
+
+
+def test_nsample_above_the_limit_is_refused_by_the_twins():
+    """GD3D_E_TOOLARGE from every `_cpu` entry point that takes nsample, as from its device twin"""
+    from mmdet3d_gaussian_amd import _lib
+    xyz, pc, new_xyz, qc, feats = _t(*cases.stack('small_1_64_65'))
+    with pytest.raises(RuntimeError, match='nsample'):
+        amd.QueryAndGroup(0.5, 1025)
+    with pytest.raises(RuntimeError, match='nsample'):
+        amd.ball_query(0.5, 1025, xyz, pc, new_xyz, qc)
+    with pytest.raises(RuntimeError, match='nsample'):
+        amd.grouping(feats, pc, torch.zeros((new_xyz.shape[0], 1025), dtype=torch.int32), qc)
+    lib = _lib.load()
+    n, m, c, ns, b = xyz.shape[0], new_xyz.shape[0], 2, 1025, 3
+    f = feats[:, :c].contiguous()
+    out, idx = torch.zeros((m, 3 + c, ns)), torch.zeros((m, ns), dtype=torch.int32)
+    cnt, mask, grad = torch.zeros((m,), dtype=torch.int32), torch.zeros((m,), dtype=torch.bool), torch.zeros((n, c))
+    p = lambda t: t.data_ptr()
+    too_large = 10002
+    assert lib.gd3d_vsa_query_and_group_cpu(p(xyz), p(pc), p(new_xyz), p(qc), p(f), b, n, m, c, 0.5, ns, 1, p(out), p(idx), p(cnt),
+                                            p(mask), 0) == too_large
+    assert lib.gd3d_vsa_ball_query_cpu(p(xyz), p(pc), p(new_xyz), p(qc), b, n, m, 0.5, ns, p(idx), p(cnt), p(mask), 0) == too_large
+    assert lib.gd3d_vsa_group_cpu(p(f), p(pc), p(idx), p(qc), b, n, m, c, ns, p(out), 0) == too_large
+    assert lib.gd3d_vsa_group_backward_cpu(p(out), p(idx), p(qc), p(pc), b, n, m, c, ns, p(grad)) == too_large
+    assert lib.gd3d_vsa_query_and_group_backward_cpu(p(out), p(idx), p(cnt), p(qc), p(pc), b, n, m, c, ns, 3, p(grad)) == too_large
+    assert not out.any() and not idx.any() and not grad.any()
+
+
 def test_other_dtypes_are_evaluated_in_fp32_and_cast_back():
     xyz, pc, new_xyz, qc, feats = _t(*cases.stack('63_tile-1_noqueries'))
     f16 = feats[:, :3].half()
@@ -152,6 +235,29 @@ def test_fps_lowest_index_wins_exact_ties():
     lat = xyz[:729].reshape(1, 729, 3).repeat(2, 1, 1).contiguous()
     b = amd.furthest_point_sample(lat, 40)
     assert b.dtype == torch.int32 and torch.equal(b[0].long(), got[0]) and torch.equal(b[1], b[0])
+
+
+@pytest.mark.parametrize('npoint', cases.FPS_DEEP_NPOINT)
+def test_fps_twin_matches_oracle_beyond_the_register_capacity(npoint):
+    """the sizes at which the kernel's threads visit one and two points beyond their registers; npoint 19000 wraps around in four
+    samples and not in the fifth"""
+    xyz, cnt = _t(*cases.fps_deep())
+    got = amd.furthest_point_sample_stacked(xyz, cnt, npoint)
+    assert got.dtype == torch.int64 and np.array_equal(got.numpy(), cases.fps_deep_reference(npoint))
+
+
+def test_fps_twin_ties_and_batched_form_on_large_samples():
+    xyz, cnt = _t(*cases.fps_deep_ties())
+    got = amd.furthest_point_sample_stacked(xyz, cnt, 800)
+    want = cases.fps_deep_ties_reference(800)
+    assert len(np.unique(want)) == 729 and want.max() < 729      # every later copy of the lattice ties with the first and loses
+    assert np.array_equal(got.numpy(), want)
+    x, want = cases.fps_batched()
+    x = torch.from_numpy(np.array(x))
+    b = amd.furthest_point_sample(x, cases.FPS_BATCHED_NPOINT)
+    assert b.dtype == torch.int32 and np.array_equal(b.numpy(), want)
+    s = amd.furthest_point_sample_stacked(x.reshape(-1, 3), torch.full((x.shape[0],), x.shape[1], dtype=torch.int32), cases.FPS_BATCHED_NPOINT)
+    assert torch.equal(b.long(), s)
 
 
 def test_argument_errors():

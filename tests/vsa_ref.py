@@ -23,6 +23,11 @@ def sample_of_rows(cnt):
     return np.repeat(np.arange(len(cnt)), np.asarray(cnt, dtype=np.int64))
 
 
+def has_points(features_cnt, idx_cnt):
+    """(rows,) bool: the row's sample has at least one point"""
+    return (np.asarray(features_cnt, dtype=np.int64) > 0)[sample_of_rows(idx_cnt)]
+
+
 def dist2(c, pts):
     """fp32: (cx-x)*(cx-x) + (cy-y)*(cy-y) + (cz-z)*(cz-z), left to right"""
     c = _f32(c)
@@ -52,20 +57,25 @@ def ball_query(radius, nsample, xyz, xyz_cnt, new_xyz, new_cnt):
 
 
 def grouping(features, features_cnt, idx, idx_cnt):
-    """out[m, c, s] = features[start_b + idx[m, s], c] -> (M, C, nsample)"""
+    """out[m, c, s] = features[start_b + idx[m, s], c] -> (M, C, nsample); a sample without points has no row to name: zeros"""
     features = np.asarray(features)
     rows = starts(features_cnt)[sample_of_rows(idx_cnt)][:, None] + np.asarray(idx, dtype=np.int64)      # (M, nsample) global rows
-    return np.ascontiguousarray(features[rows].transpose(0, 2, 1))
+    has = has_points(features_cnt, idx_cnt)
+    out = np.zeros((rows.shape[0], features.shape[1], rows.shape[1]), features.dtype)
+    out[has] = features[rows[has]].transpose(0, 2, 1)
+    return out
 
 
 def grouping_backward(grad_out, idx, idx_cnt, features_cnt, n, live=None):
     """fp64 grad_features (n, C), and per element the number of contributions and the sum of their magnitudes (what the
-    rounding bound of an fp32 sum in any order is made of).  `live` (M,) bool: rows that pass a gradient (default all)."""
+    rounding bound of an fp32 sum in any order is made of).  `live` (M,) bool: rows that pass a gradient (default all); the rows
+    of a sample without points never do."""
     g = np.asarray(grad_out, dtype=np.float64)                     # (M, C, nsample)
     m, c, ns = g.shape
     rows = starts(features_cnt)[sample_of_rows(idx_cnt)][:, None] + np.asarray(idx, dtype=np.int64)
     if live is None:
         live = np.ones((m,), bool)
+    live = live & has_points(features_cnt, idx_cnt)
     rows, g = rows[live], g[live]
     grad = np.zeros((n, c))
     mag = np.zeros((n, c))
@@ -105,9 +115,18 @@ def fps(xyz, npoint):
     t = np.full((n,), 1e10, np.float32)
     picks = min(n, npoint)
     old = 0
+    x, y, z = (np.ascontiguousarray(xyz[:, k]) for k in range(3))   # dist2's arithmetic on contiguous columns, in place
+    dx, dy, dz = (np.empty((n,), np.float32) for _ in range(3))
     for p in range(1, picks):
-        d = dist2(xyz[old], xyz)
-        t = np.where(d < t, d, t)
+        np.subtract(x[old], x, out=dx)
+        np.subtract(y[old], y, out=dy)
+        np.subtract(z[old], z, out=dz)
+        np.multiply(dx, dx, out=dx)
+        np.multiply(dy, dy, out=dy)
+        np.multiply(dz, dz, out=dz)
+        np.add(dx, dy, out=dx)
+        np.add(dx, dz, out=dx)                                      # (dx * dx + dy * dy) + dz * dz
+        np.copyto(t, dx, where=dx < t)                              # d < t ? d : t
         old = int(np.argmax(t))
         out[p] = old
     for j in range(picks, npoint):
