@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import oracle
+import match_cases
 import nms_ref
 from rbox_inputs import eval_boxes, nms_boxes
 
@@ -138,3 +139,68 @@ def test_match_coco_cpu_entry_argument_rules():
     assert call(one.ctypes.data, one.ctypes.data, flags.ctypes.data, flags.ctypes.data, 1, 1, 1, None, 1) == 10001
     assert call(one.ctypes.data, one.ctypes.data, flags.ctypes.data, flags.ctypes.data, 1, (1 << 20) + 1, 1, out.ctypes.data, 1) == 10002
     assert call(None, one.ctypes.data, None, None, 0, 0, 0, None, 1) == 0      # nothing to do
+
+
+def test_match_case_table_covers_every_kernel_path_and_size_boundary():
+    """The shapes of tests/match_cases.py: every G of a kernel path with two D and two kinds at least, every D of the path somewhere,
+    `sparse` and `dist` costs and one threshold list with +inf, -inf and NaN on every path, and the three large sizes."""
+    assert len({c.id for c in match_cases.CASES + match_cases.LARGE_CASES}) == len(match_cases.CASES) + len(match_cases.LARGE_CASES)
+    for path, (gs, ds) in match_cases.PATH_SHAPES.items():
+        cases = [c for c in match_cases.CASES if c.path == path]
+        assert {c.G for c in cases} == set(gs) and {c.D for c in cases} == set(ds), path
+        for g in gs:
+            assert len({c.D for c in cases if c.G == g}) >= 2 and len({c.kind for c in cases if c.G == g}) >= 2, (path, g)
+        assert {c.kind for c in cases} == set(match_cases.KINDS) and all(1 <= c.T <= 4 for c in cases)
+        special = [c for c in cases if c.special]
+        assert special and all(c.D >= 3 for c in special)
+        for c in special:
+            thrs = match_cases.inputs(c)[1]
+            assert np.isposinf(thrs).any() and np.isneginf(thrs).any() and np.isnan(thrs).any() and np.isfinite(thrs).any()
+    assert [(c.G, c.D, c.T, c.kind) for c in match_cases.LARGE_CASES] == [(393184, 70, 2, 'dense'), (393185, 70, 2, 'dense'),
+                                                                          (1 << 20, 3, 2, 'dense')]
+    for c in match_cases.CASES:     # what every kind carries (from 64 entries on; about 1 % NaN from 100)
+        cost, _, ign, crowd = match_cases.inputs(c)
+        if c.D * c.G >= 100:
+            assert np.isnan(cost).any() and np.isposinf(cost).any() and (np.signbit(cost) & (cost == 0)).any(), c.id
+        if c.G >= 2:
+            assert not (ign[0] or ign[-1] or crowd[0] or crowd[-1]) and cost[0, -1] == cost[np.isfinite(cost)].min(), c.id
+            assert (cost[3:] > cost[0, -1]).sum() + np.isnan(cost[3:]).sum() + np.isneginf(cost[3:]).sum() == cost[3:].size, c.id
+    assert any(np.isneginf(match_cases.inputs(c)[0]).any() for c in match_cases.CASES if c.special)
+
+
+def test_match_case_table_exercises_what_it_claims():
+    """Conditions on the ORACLE's answers, per kernel path over its non-large cases: matches to ignore gts, crowd gts matched more than
+    once under one threshold, exact ties inside an ignore class, matched and unmatched detections; every 64-gt chunk of a case at the
+    largest G of the two paths that keep taken bits per chunk; and the plant (see match_cases.make) in every case with G >= 2."""
+    wit = {c: match_cases.witnesses(c, match_cases.expected(c)) for c in match_cases.CASES}
+    for path in match_cases.PATHS:
+        ws = [w for c, w in wit.items() if c.path == path]
+        assert sum(w['ignore_matches'] for w in ws) > 0, path
+        assert sum(w['crowd_repeats'] for w in ws) > 0, path
+        assert sum(w['ties'] for w in ws) > 0, path
+        assert 0 < sum(w['unmatched'] * w['n'] for w in ws) < sum(w['n'] for w in ws), path
+    for path, g in (('small4', 256), ('reg', 2048)):
+        assert any(w['chunks'] == w['all_chunks'] == g // 64 for c, w in wit.items() if c.path == path and c.G == g), path
+    for c, w in wit.items():
+        if c.G >= 2:
+            assert w['plant'] and w['last'] and (c.D < 3 or w['first']), c.id
+            m = match_cases.expected(c)
+            rows = m[:, 0] == c.G - 1
+            assert rows.any() and (c.D < 2 or (m[rows, 1] != c.G - 1).all()), c.id
+
+
+@pytest.mark.parametrize('case', match_cases.CASES + match_cases.LARGE_CASES, ids=lambda c: c.id)
+def test_match_coco_cpu_twin_vs_oracle_on_the_case_table(case):
+    args = match_cases.build(case) if case.large else match_cases.inputs(case)
+    want = oracle.match_coco(*args) if case.large else match_cases.expected(case)
+    cost, thrs, ign, crowd = args
+    got = amd.match_coco(*[torch.tensor(x) for x in args])       # copies: the table's arrays are read-only
+    assert got.dtype == torch.int32 and got.shape == (case.T, case.D) and np.array_equal(got.numpy(), want)
+    lib = amd.load_library()
+    out = np.empty((case.T, case.D), np.int32)
+    c8, i8 = crowd.astype(np.uint8), ign.astype(np.uint8)
+    for threads in (1, 3):
+        out.fill(7)
+        assert lib.eval_match_coco_cpu(cost.ctypes.data, thrs.ctypes.data, i8.ctypes.data, c8.ctypes.data, case.D, case.G, case.T,
+                                       out.ctypes.data, threads) == 0
+        assert np.array_equal(out, want), threads
