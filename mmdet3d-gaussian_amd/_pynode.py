@@ -18,18 +18,15 @@ Surface (argument for argument that of csrc/torch_node.cpp):
   set_unit_grad / finish_calls / bind: bookkeeping the C++ module also exports.
 """
 import ctypes
-import threading
-import time
 
 import torch
 
-from . import _lib
+from . import _host, _lib
 
 IMPLEMENTATION = 'python'
 
-_raw_stream = torch._C._cuda_getCurrentRawStream
-_get_device = torch._C._cuda_getDevice
-_set_device = torch._C._cuda_setDevice
+_on_device = _host.on_device
+_ptr = _host.ptr
 
 _FINISH_CALLS = 0          # gd3d_grad_finish launches made by backward so far (tests: unit_grad must make none)
 _UNIT_GRAD = {}            # device index (-1: the CPU) -> address of the library's constant 1.0
@@ -63,25 +60,6 @@ def guard_double_backward(impl):
     return backward
 
 
-class _on_device:
-    """Minimal device guard (raw accessors: no Python-level bookkeeping on the per-call path); yields the raw current stream."""
-    __slots__ = ('idx', 'prev')
-
-    def __init__(self, dev):
-        self.idx = dev.index
-
-    def __enter__(self):
-        self.prev = _get_device()
-        if self.prev != self.idx:
-            _set_device(self.idx)
-        return _raw_stream(self.idx)
-
-    def __exit__(self, *exc):
-        if self.prev != self.idx:
-            _set_device(self.prev)
-        return False
-
-
 def bind(path):
     """The C++ module resolves the C ABI from `path` here; the Python glue calls through the ctypes binding `_lib.load()`
     made of the same image.  Returns the ABI version."""
@@ -102,10 +80,6 @@ def finish_calls():
 def _is_unit_grad(g):
     a = _UNIT_GRAD.get(g.device.index if g.is_cuda else -1)
     return a is not None and g.dim() == 0 and g.dtype == torch.float32 and g.data_ptr() == a
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _copy_struct(cls, addr):
@@ -394,43 +368,7 @@ def scatter_reduce(feats, point2voxel_map, voxel_points_count, reduce, order, se
 
 # ---- nms_gpu's scored path --------------------------------------------------------------------------------------------------------------
 
-_NMS_WS = {}
-_PENDING = -(1 << 62)
-_MAILBOX = threading.local()
-
-
-def count_mailbox(g):
-    """This thread's mailbox: (pinned int64 tensor, its numpy view) of at least g words.  nms_gpu's result length is data
-    dependent; instead of a blocking 8-byte device-to-host copy (a copy call + a stream synchronisation, ~10 us on this stack) the
-    scan kernel writes its count straight into pinned host memory — every NMS entry point takes `num_keep` as a plain pointer —
-    and the host polls the word: 55.0 -> 49.8 us per nms_gpu-sized call (n = 4096; profiles/r06_nms_batched.txt).  The kept
-    ids stay on the device, stream-ordered as before.  One mailbox per thread: a call blocks until its words arrive."""
-    cur = getattr(_MAILBOX, 'box', None)
-    if cur is None or cur[0].numel() < g:
-        t = torch.empty(max(64, g), dtype=torch.int64).pin_memory()
-        cur = _MAILBOX.box = (t, t.numpy())
-    return cur
-
-
-def wait_counts(words, g, dev):
-    """Poll the first g mailbox words until the kernels have written them all; returns them as ints.  After 0.2 s without them
-    the device is synchronised and the words are read once more (a word still pending then raises)."""
-    spins, deadline = 0, None
-    while True:
-        vals = [int(words[i]) for i in range(g)]
-        if _PENDING not in vals:
-            return vals
-        spins += 1
-        if (spins & 0x3ff) == 0:
-            now = time.perf_counter()
-            if deadline is None:
-                deadline = now + 0.2
-            elif now > deadline:
-                torch.cuda.synchronize(dev)
-                vals = [int(words[i]) for i in range(g)]
-                if _PENDING in vals:
-                    raise RuntimeError('nms_gpu: the NMS kernels finished without reporting a count')
-                return vals
+_scored_ws_bytes = _host.memo(lambda n_all, n_keep: int(_lib.load().rnms_scored_workspace_bytes(n_all, n_keep)))
 
 
 def nms_scored(boxes, scores, thresh, n_keep, normal, padded, post_max):
@@ -444,31 +382,24 @@ def nms_scored(boxes, scores, thresh, n_keep, normal, padded, post_max):
         raise RuntimeError('gd3d node: nms_scored takes contiguous fp32 (N,5) boxes and (N) scores on one GPU and 0 < n_keep <= N')
     lib = _lib.load()
     n_all = boxes.shape[0]
-    nbytes = _NMS_WS.get((n_all, n_keep))
-    if nbytes is None:
-        if len(_NMS_WS) > 4096:
-            _NMS_WS.clear()
-        nbytes = _NMS_WS[(n_all, n_keep)] = int(lib.rnms_scored_workspace_bytes(n_all, n_keep))
     dev = boxes.device
-    with _on_device(dev) as stream:
-        keep = torch.empty(n_keep, dtype=torch.int64, device=dev)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        if padded:
-            num = torch.empty(1, dtype=torch.int64, device=dev)
-            dst = num.data_ptr()
-        else:   # the count goes straight into pinned host memory and is polled there (see count_mailbox)
-            box, words = count_mailbox(1)
-            words[0] = _PENDING
-            dst = box.data_ptr()
-        rc = lib.rnms_scored(int(normal), boxes.data_ptr(), scores.data_ptr(), n_all, n_keep, float(thresh), keep.data_ptr(),
-                             dst, ws.data_ptr(), stream)
-    if rc != 0:
-        _lib.check(rc, 'nms_normal_gpu' if normal else 'nms_gpu')
+    name = 'nms_normal_gpu' if normal else 'nms_gpu'
+    keep = torch.empty(n_keep, dtype=torch.int64, device=dev)
+    ws = torch.empty(_scored_ws_bytes(n_all, n_keep), dtype=torch.uint8, device=dev)
+
+    def launch(num_keep, stream):
+        return lib.rnms_scored(int(normal), boxes.data_ptr(), scores.data_ptr(), n_all, n_keep, float(thresh), keep.data_ptr(),
+                               num_keep, ws.data_ptr(), stream)
     if padded:
+        num = torch.empty(1, dtype=torch.int64, device=dev)
+        with _on_device(dev) as stream:
+            rc = launch(num.data_ptr(), stream)
+        if rc != 0:
+            _lib.check(rc, name)
         return keep, num
-    k = wait_counts(words, 1, dev)[0]   # the one unavoidable wait: the result length is data dependent
-    if k < 0:             # the scan kernel's failure mark (a bounded polling loop gave up: never observed)
-        raise RuntimeError(f'nms_gpu: the device-side NMS scan gave up (num_keep = {k}); the result is void')
+    # the one unavoidable wait: the result length is data dependent; the count goes straight into pinned host memory and is
+    # polled there (_host.launch_counted)
+    k = _host.launch_counted(1, dev, name, launch)[0]
     if post_max >= 0 and k > post_max:
         k = post_max
     return keep[:k], None

@@ -21,6 +21,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._host import on_device
 
 
 def _coder_struct(c):
@@ -54,10 +55,9 @@ class _CenterDecode(torch.autograd.Function):
         out = torch.empty((n, co), dtype=torch.float32, device=preds.device)
         need = ctx.needs_input_grad[0]
         parity = torch.empty(n, dtype=torch.int32, device=preds.device) if (need and correct_yaw) else None
-        with torch.cuda.device(preds.device):
+        with on_device(preds.device) as stream:
             rc = lib.coder_center_decode(cs, l2.data_ptr(), p2.data_ptr(), n, c, int(bool(correct_yaw)), out.data_ptr(),
-                                         None if parity is None else parity.data_ptr(),
-                                         torch.cuda.current_stream().cuda_stream)
+                                         None if parity is None else parity.data_ptr(), stream)
         _lib.check(rc, 'coder_center_decode')
         ctx.cs, ctx.meta = cs, (n, c, lead, preds.dtype)
         if need:
@@ -72,10 +72,9 @@ class _CenterDecode(torch.autograd.Function):
         n, c, lead, dtype = ctx.meta
         go = _rows32(grad_out, out.shape[1])
         gp = torch.empty((n, c), dtype=torch.float32, device=go.device)
-        with torch.cuda.device(go.device):
+        with on_device(go.device) as stream:
             rc = lib.coder_center_decode_backward(ctx.cs, go.data_ptr(), out.data_ptr(),
-                                                  None if parity is None else parity.data_ptr(), n, c, gp.data_ptr(),
-                                                  torch.cuda.current_stream().cuda_stream)
+                                                  None if parity is None else parity.data_ptr(), n, c, gp.data_ptr(), stream)
         _lib.check(rc, 'coder_center_decode_backward')
         gp = gp.reshape(lead + (c,))
         return (gp if dtype == torch.float32 else gp.to(dtype)), None, None, None
@@ -115,9 +114,8 @@ class CenterPointBBoxCoderRev:
         lead, c = preds.shape[:-1], preds.shape[-1]
         p2, l2 = _rows32(preds.detach(), c), _rows32(locs.to(preds.device), 2)
         out = torch.empty((p2.shape[0], c - 1), dtype=torch.float32, device=p2.device)
-        with torch.cuda.device(p2.device):
-            rc = lib.coder_center_decode(_coder_struct(self), l2.data_ptr(), p2.data_ptr(), p2.shape[0], c, 2, out.data_ptr(), None,
-                                         torch.cuda.current_stream().cuda_stream)
+        with on_device(p2.device) as stream:
+            rc = lib.coder_center_decode(_coder_struct(self), l2.data_ptr(), p2.data_ptr(), p2.shape[0], c, 2, out.data_ptr(), None, stream)
         _lib.check(rc, 'coder_center_decode')
         out = out.reshape(lead + (c - 1,))
         return out if preds.dtype == torch.float32 else out.to(preds.dtype)
@@ -135,8 +133,8 @@ class CenterPointBBoxYawCoder(CenterPointBBoxCoderRev):
         lead, c = target_boxes.shape[:-1], target_boxes.shape[-1]
         b2 = _rows32(target_boxes.detach(), c)
         out = torch.empty((b2.shape[0], c + 2), dtype=torch.float32, device=b2.device)
-        with torch.cuda.device(b2.device):
-            rc = lib.coder_center_encode(b2.data_ptr(), b2.shape[0], c, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        with on_device(b2.device) as stream:
+            rc = lib.coder_center_encode(b2.data_ptr(), b2.shape[0], c, out.data_ptr(), stream)
         _lib.check(rc, 'coder_center_encode')
         out = out.reshape(lead + (c + 2,))
         return out if target_boxes.dtype == torch.float32 else out.to(target_boxes.dtype)
@@ -163,9 +161,9 @@ class _PointDecode(torch.autograd.Function):
         out = torch.empty((n, co), dtype=torch.float32, device=preds.device)
         need = ctx.needs_input_grad[0]
         parity = torch.empty(n, dtype=torch.int32, device=preds.device) if (need and correct_yaw) else None
-        with torch.cuda.device(preds.device):
+        with on_device(preds.device) as stream:
             rc = lib.coder_point_decode(q2.data_ptr(), p2.data_ptr(), n, c, int(bool(correct_yaw)), out.data_ptr(),
-                                        None if parity is None else parity.data_ptr(), torch.cuda.current_stream().cuda_stream)
+                                        None if parity is None else parity.data_ptr(), stream)
         _lib.check(rc, 'coder_point_decode')
         ctx.meta = (n, c, lead, preds.dtype)
         if need:
@@ -180,9 +178,9 @@ class _PointDecode(torch.autograd.Function):
         n, c, lead, dtype = ctx.meta
         go = _rows32(grad_out, out.shape[1])
         gp = torch.empty((n, c), dtype=torch.float32, device=go.device)
-        with torch.cuda.device(go.device):
+        with on_device(go.device) as stream:
             rc = lib.coder_point_decode_backward(q2.data_ptr(), go.data_ptr(), out.data_ptr(), None if parity is None else parity.data_ptr(),
-                                                 n, c, gp.data_ptr(), torch.cuda.current_stream().cuda_stream)
+                                                 n, c, gp.data_ptr(), stream)
         _lib.check(rc, 'coder_point_decode_backward')
         gp = gp.reshape(lead + (c,))
         return (gp if dtype == torch.float32 else gp.to(dtype)), None, None

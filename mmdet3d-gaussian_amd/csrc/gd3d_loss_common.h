@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gd3d_device.h"
+#include "gd3d_fill.h"
 #include "gd3d_instances.h"
 
 namespace gd3d {
@@ -56,8 +57,7 @@ GD_DEV float wave_sum(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
-// defined in gd3d_loss.hip
-int fill_words(void* p, size_t bytes, unsigned value, hipStream_t s);   // fill_words_kernel; bytes: a multiple of 4
+// defined in gd3d_loss.hip (fill_words: gd3d_fill.h)
 int reduce_partials(const float* partials, long long nb, float* out, hipStream_t s);   // reduce_partials_kernel
 
 }  // namespace gd3d

@@ -22,13 +22,14 @@
 //      nms_scan_kernel (classic; also beyond 16384 boxes, two-level with nms_propagate_kernel): a resolver wave solves each block
 //      from an LDS ring, three phase-shifted groups of row waves OR the mask rows of the boxes just kept into the removed-set (LDS);
 //      one LDS-only barrier per block.
-// ONE translation unit: the headers hold their stages' kernels, rbox_nms_common.h what they share; this file keeps the IoU kernels,
-// fill_words and the NMS host side — workspace view (NmsWorkspace), launch plan (nms_plan), runner (nms_run) — behind the C ABI.
+// ONE translation unit: the headers hold their stages' kernels, rbox_nms_common.h what they share; this file keeps the IoU kernels
+// and the NMS host side — workspace view (NmsWorkspace), launch plan (nms_plan), runner (nms_run) — behind the C ABI.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdlib.h>
 
 #include "../../include/gd3d.h"
+#include "gd3d_fill.h"
 #include "rbox_rank.h"
 #include "rbox_mask.h"
 #include "rbox_scan.h"
@@ -75,30 +76,6 @@ __global__ __launch_bounds__(EVAL_T) void riou_eval_kernel(const float* __restri
   out[idx] = eval_iou<IS3D, EVAL_T>(d, g, z_offset, hs, threadIdx.x);
 }
 
-// Clears (or fills) small or large device buffers from a KERNEL.  Not hipMemsetAsync: inside a captured hipGraph a memset node was
-// found not to be reliably ordered against the kernels around it on this ROCm (profiles/r04_nms_queue_ab.txt) —
-// rule of this library: no memset nodes in paths a caller may capture.
-__global__ __launch_bounds__(256) void fill_words_kernel(unsigned* __restrict__ p, long long nwords, unsigned value) {
-  const long long stride = (long long)gridDim.x * 256;
-  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if ((((uintptr_t)p) & 15) == 0) {
-    uint4* p4 = reinterpret_cast<uint4*>(p);
-    const long long nv = nwords >> 2;
-    const uint4 v4 = make_uint4(value, value, value, value);
-    for (long long k = i; k < nv; k += stride) p4[k] = v4;
-    for (long long k = (nv << 2) + i; k < nwords; k += stride) p[k] = value;
-    return;
-  }
-  for (; i < nwords; i += stride) p[i] = value;
-}
-static int fill_words(void* p, size_t bytes, unsigned value, hipStream_t s) {   // bytes: a multiple of 4
-  const long long nwords = (long long)(bytes / 4);
-  if (nwords == 0) return 0;
-  long long blocks = (nwords / 4 + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-  hipLaunchKernelGGL(fill_words_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (unsigned*)p, nwords, value);
-  return (int)hipGetLastError();
-}
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -320,7 +297,7 @@ size_t rnms_workspace_bytes(int64_t n) { return rnms_batched_workspace_bytes(1, 
 static int rnms_impl(int mode, const float* boxes, const int64_t* order, int64_t n, float thresh, double thresh_d,
                      int64_t* keep, int64_t* num_keep, void* workspace, void* stream) {
   if (n < 0 || num_keep == nullptr) return GD3D_E_BADARG;
-  if (n == 0) return fill_words(num_keep, sizeof(int64_t), 0u, (hipStream_t)stream);
+  if (n == 0) return gd3d::fill_words(num_keep, sizeof(int64_t), 0u, (hipStream_t)stream);
   if (boxes == nullptr || keep == nullptr || workspace == nullptr) return GD3D_E_BADARG;
   return ordered_nms(mode, 1, n, nms_args(boxes, order, nullptr, n, thresh, thresh_d, nullptr), PREPARED_NOTHING, keep, num_keep,
                      workspace, stream);
@@ -330,7 +307,7 @@ static int rnms_batched_impl(int mode, const float* boxes, const int64_t* order,
                              const float* thresh, NmsPrepared done, int64_t* keep, int64_t* num_keep, void* workspace, void* stream) {
   if (groups == 0) return 0;
   if (num_keep == nullptr) return GD3D_E_BADARG;
-  if (cap == 0) return fill_words(num_keep, sizeof(int64_t) * (size_t)groups, 0u, (hipStream_t)stream);
+  if (cap == 0) return gd3d::fill_words(num_keep, sizeof(int64_t) * (size_t)groups, 0u, (hipStream_t)stream);
   if (boxes == nullptr || order == nullptr || counts == nullptr || thresh == nullptr || keep == nullptr ||
       workspace == nullptr)
     return GD3D_E_BADARG;
@@ -371,7 +348,7 @@ int rnms_scored(int32_t normal, const float* boxes, const float* scores, int64_t
   if (n_all < 0 || num_keep == nullptr) return GD3D_E_BADARG;
   if (n_all > RANK_MAX) return GD3D_E_TOOLARGE;
   const int64_t n = (pre_max >= 0 && pre_max < n_all) ? pre_max : n_all;
-  if (n == 0) return fill_words(num_keep, sizeof(int64_t), 0u, (hipStream_t)stream);
+  if (n == 0) return gd3d::fill_words(num_keep, sizeof(int64_t), 0u, (hipStream_t)stream);
   if (boxes == nullptr || scores == nullptr || keep == nullptr || workspace == nullptr) return GD3D_E_BADARG;
   return ranked_nms(normal ? MODE_NORMAL : MODE_ROT, boxes, scores, nullptr, nullptr, 1, n_all, n, /*counts=*/false, 0, thresh,
                     nullptr, keep, num_keep, workspace, stream);
@@ -389,7 +366,7 @@ static int batched_scored_impl(int32_t mode, const float* boxes, const float* sc
   if (num_keep == nullptr) return GD3D_E_BADARG;
   if (n > RANK_MAX || groups > 65535) return GD3D_E_TOOLARGE;
   const int64_t cap = (pre_max >= 0 && pre_max < n) ? pre_max : n;
-  if (cap == 0) return fill_words(num_keep, sizeof(int64_t) * (size_t)groups, 0u, (hipStream_t)stream);
+  if (cap == 0) return gd3d::fill_words(num_keep, sizeof(int64_t) * (size_t)groups, 0u, (hipStream_t)stream);
   if (boxes == nullptr || scores == nullptr || thresh == nullptr || keep == nullptr || workspace == nullptr) return GD3D_E_BADARG;
   return ranked_nms(mode, boxes, scores, valid, seg, groups, n, cap, /*counts=*/true, gps, 0.0f, thresh, keep, num_keep, workspace,
                     stream);

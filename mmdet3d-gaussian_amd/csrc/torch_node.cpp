@@ -587,9 +587,14 @@ std::tuple<Tensor, Tensor> nms_scored(const Tensor& boxes, const Tensor& scores,
     word = mailbox.data_ptr<int64_t>();
     *word = PENDING;
   }
-  fail(abi.nms_scored(normal ? 1 : 0, boxes.data_ptr<float>(), scores.data_ptr<float>(), n_all, n_keep, (float)thresh,
-                      keep.data_ptr<int64_t>(), padded ? num.data_ptr<int64_t>() : (int64_t*)word, ws.data_ptr(), current_stream(boxes)),
-       normal ? "nms_normal_gpu" : "nms_gpu");
+  const int rc = abi.nms_scored(normal ? 1 : 0, boxes.data_ptr<float>(), scores.data_ptr<float>(), n_all, n_keep, (float)thresh,
+                                keep.data_ptr<int64_t>(), padded ? num.data_ptr<int64_t>() : (int64_t*)word, ws.data_ptr(),
+                                current_stream(boxes));
+  // The mailbox word is reused by this thread's next call: a call must not leave while a kernel of its own may still write it (a
+  // late write would land after the next call has marked the word pending and hand that call a wrong count).  The only early exit
+  // is a failed, possibly partial, launch — the poll below cannot be interrupted and ends with the word read or the stream drained.
+  if (rc != 0 && !padded) c10::hip::getCurrentHIPStream(boxes.device().index()).synchronize();
+  fail(rc, normal ? "nms_normal_gpu" : "nms_gpu");
   if (padded) return {keep, num};
   int64_t k = PENDING;
   {

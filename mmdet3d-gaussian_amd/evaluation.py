@@ -15,7 +15,7 @@ CPU tensors (and numpy inputs on a machine without a GPU) take the library's `_c
 import numpy as np
 import torch
 
-from . import _lib
+from . import _host
 from .iou3d import iou_3d, iou_bev
 
 
@@ -42,14 +42,9 @@ def trans_bev(det_bboxes, gt_bboxes):
     if d.dim() != 2 or g.dim() != 2 or d.shape[1] < 2 or g.shape[1] < 2:
         raise RuntimeError(f'trans_bev: expected (D,>=2) and (G,>=2), got {tuple(d.shape)} and {tuple(g.shape)}')
     out = torch.empty((d.shape[0], g.shape[0]), dtype=torch.float32, device=d.device)
-    if not d.is_cuda:   # the reference's own helper is CPU code (affinity.cpp:83-105): the `_cpu` twin
-        _lib.check(_lib.load().riou_eval_trans_bev_cpu(d.data_ptr(), d.shape[0], d.shape[1], g.data_ptr(), g.shape[0], g.shape[1],
-                                                       out.data_ptr(), torch.get_num_threads()), 'riou_eval_trans_bev_cpu')
-        return out
-    with torch.cuda.device(d.device):
-        _lib.check(_lib.load().riou_eval_trans_bev(d.data_ptr(), d.shape[0], d.shape[1], g.data_ptr(), g.shape[0],
-                                                   g.shape[1], out.data_ptr(),
-                                                   torch.cuda.current_stream().cuda_stream), 'riou_eval_trans_bev')
+    # (the reference's own helper is CPU code, affinity.cpp:83-105: CPU tensors take the `_cpu` twin)
+    _host.call('riou_eval_trans_bev', d.device, (d.data_ptr(), d.shape[0], d.shape[1], g.data_ptr(), g.shape[0], g.shape[1],
+                                                 out.data_ptr()), (torch.get_num_threads(),))
     return out
 
 
@@ -67,12 +62,7 @@ def match_coco(cost_mat, cost_thrs, is_ignore, is_crowd):
         raise RuntimeError(f'match_coco: {G} gts but {ign.numel()} ignore / {crowd.numel()} crowd flags')
     T = thrs.numel()
     out = torch.empty((T, D), dtype=torch.int32, device=dev)
-    if not cost.is_cuda:   # the reference's matcher is CPU code (matcher.cpp:8-74): the `_cpu` twin
-        _lib.check(_lib.load().eval_match_coco_cpu(cost.data_ptr(), thrs.data_ptr(), ign.data_ptr(), crowd.data_ptr(), D, G, T,
-                                                   out.data_ptr(), torch.get_num_threads()), 'eval_match_coco_cpu')
-        return out
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().eval_match_coco(cost.data_ptr(), thrs.data_ptr(), ign.data_ptr(), crowd.data_ptr(), D, G, T,
-                                               out.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                   'eval_match_coco')
+    # (the reference's matcher is CPU code, matcher.cpp:8-74: CPU tensors take the `_cpu` twin)
+    _host.call('eval_match_coco', dev, (cost.data_ptr(), thrs.data_ptr(), ign.data_ptr(), crowd.data_ptr(), D, G, T, out.data_ptr()),
+               (torch.get_num_threads(),))
     return out

@@ -19,7 +19,7 @@ from copy import deepcopy
 
 import torch
 from torch import nn
-from . import _lib
+from . import _host, _lib
 from ._pynode import guard_double_backward  # noqa: F401  (head_loss / heat_loss / anchor_cls import it from here)
 from .registry import LOSSES, register_with_mmdet
 
@@ -83,15 +83,12 @@ def make_params(loss_type, fun, tau, alpha, center_offset, kwargs):
     return p
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 _LIB = None
+_ptr = _host.ptr
 # raw-handle accessors (no Python-level device bookkeeping on the per-call path)
-_raw_stream = torch._C._cuda_getCurrentRawStream
-_get_device = torch._C._cuda_getDevice
-_set_device = torch._C._cuda_setDevice
+_raw_stream = _host.raw_stream
+_get_device = _host.get_device
+_set_device = _host.set_device
 
 
 def _library():
@@ -118,7 +115,6 @@ def _rows(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
-_WS_FLOATS = {}
 _ONE_MAX = None
 _TICKETS = {}
 _GRAPH_TICKETS = {}      # device index -> [int32 pool, slots handed out]
@@ -155,14 +151,8 @@ def _ticket(dev_index, stream):
     return t.data_ptr()
 
 
-def _ws_floats(n):
-    """gd3d_loss_workspace_bytes(n) / 4, memoised (one ctypes call less per forward)."""
-    k = _WS_FLOATS.get(n)
-    if k is None:
-        if len(_WS_FLOATS) > 4096:
-            _WS_FLOATS.clear()
-        k = _WS_FLOATS[n] = _library().gd3d_loss_workspace_bytes(n) // 4
-    return k
+# gd3d_loss_workspace_bytes(n) / 4, memoised (one ctypes call less per forward)
+_ws_floats = _host.memo(lambda n: _library().gd3d_loss_workspace_bytes(n) // 4)
 
 
 _UNIT_GRAD = {}

@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._host import on_device
 from .gd_loss import _is_unit_grad, guard_double_backward
 
 
@@ -297,8 +298,7 @@ def _center_head_launch(meta, maps, need):
     losses = torch.empty((T, 2), dtype=torch.float32, device=dev)
     ws = torch.empty(lib.gd3d_center_head_workspace_bytes(T, max_n) // 4, dtype=torch.float32, device=dev)
     cwp = (ctypes.c_float * max(n_l1, 1))(*[float(x) for x in cw[:n_l1]])
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
+    with on_device(dev) as stream:
         if any(need) and max_n > CENTER_SORT_MIN_N:
             # many objects: the per-cell accumulation walks the keys in SORTED order (one stable batched sort of the
             # tasks' key rows between the two launches) instead of scanning them once per shared-cell object
@@ -339,8 +339,8 @@ class _CenterHeadFused(torch.autograd.Function):
             ctx.grads = ctx.tasks = None
         go = grad_losses.contiguous().float()
         dev = go.device
-        with torch.cuda.device(dev):
-            rc = lib.gd3d_center_head_scale(tasks, len(tasks), go.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        with on_device(dev) as stream:
+            rc = lib.gd3d_center_head_scale(tasks, len(tasks), go.data_ptr(), stream)
         _lib.check(rc, 'gd3d_center_head_scale')
         return (None,) + tuple(grads)
 

@@ -16,19 +16,9 @@ Device follows the tensors: CPU tensors take the library's `_cpu` twins (csrc/rb
 compiled for the host, bit-identical results) in ``nms_gpu`` / ``nms_normal_gpu`` / ``boxes_iou_bev`` / ``iou_bev`` / ``iou_3d``;
 the batched, segmented and scored forms are GPU-only.
 """
-import ctypes
-
 import torch
 
-from . import _lib, _pynode
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+from . import _host, _lib
 
 
 def _check_boxes(boxes, cols, name, cpu_ok=False):
@@ -37,11 +27,6 @@ def _check_boxes(boxes, cols, name, cpu_ok=False):
     if boxes.dim() != 2 or boxes.shape[1] != cols:
         raise RuntimeError(f'{name}: expected (N,{cols}) boxes, got {tuple(boxes.shape)}')
     return boxes.to(torch.float32).contiguous()
-
-
-def _same_device(a, b, name):
-    if a.device != b.device:
-        raise RuntimeError(f'{name}: operands live on different devices ({a.device}, {b.device})')
 
 
 def _nms_cpu(lib, boxes, scores, thresh, n, post_max_size, normal, padded):
@@ -64,6 +49,13 @@ def _nms_cpu(lib, boxes, scores, thresh, n, post_max_size, normal, padded):
     return keep if post_max_size is None else keep[:post_max_size]
 
 
+def _cut_padded(keep, num, post_max_size):
+    """padded=True: nothing is read back — (kept indices padded to n rows, count on the device); the post_max_size cut applies to both"""
+    if post_max_size is not None:
+        keep, num = keep[:post_max_size], num.clamp(max=max(int(post_max_size), 0))
+    return keep, num
+
+
 def _nms(boxes, scores, thresh, pre_max_size, post_max_size, normal, padded=False):
     name = 'nms_normal_gpu' if normal else 'nms_gpu'
     boxes = _check_boxes(boxes, 5, name, cpu_ok=True)
@@ -84,85 +76,35 @@ def _nms(boxes, scores, thresh, pre_max_size, post_max_size, normal, padded=Fals
         return _nms_cpu(lib, boxes, scores, thresh, n, post_max_size, normal, padded)
     # up to 16384 candidates (the heads cut to nms_pre first) the library orders the scores itself (rank by counting, prep
     # scattered to the rank: no torch.sort); float64 scores keep torch.sort (their order may differ after rounding to fp32)
-    fused_sort = n_all <= _scored_max(lib) and scores.dim() == 1 and scores.dtype in (torch.float32, torch.float16,
-                                                                                     torch.bfloat16)
-    if fused_sort and scores.dtype == torch.float32 and scores.is_contiguous():
-        # the usual call: allocations, launch, count read-back and cut in the host glue (`nms_scored` of _pynode.py or of its
-        # C++ twin csrc/torch_node.cpp: _lib.load_node())
+    if n_all <= _scored_max(lib) and scores.dim() == 1 and scores.dtype in (torch.float32, torch.float16, torch.bfloat16):
+        # allocations, launch, count read-back and cut in the host glue (`nms_scored` of the Python glue or of its C++ twin
+        # csrc/torch_node.cpp: _lib.load_node()), which takes contiguous fp32 scores
+        if scores.dtype != torch.float32 or not scores.is_contiguous():
+            scores = scores.float().contiguous()
         post = int(post_max_size) if (post_max_size is not None and post_max_size >= 0 and not padded) else -1
         keep, num = _lib.load_node().nms_scored(boxes, scores, float(thresh), n, bool(normal), bool(padded), post)
         if padded:
-            if post_max_size is not None:
-                keep, num = keep[:post_max_size], num.clamp(max=max(int(post_max_size), 0))
-            return keep, num
+            return _cut_padded(keep, num, post_max_size)
         return keep if (post_max_size is None or post_max_size >= 0) else keep[:post_max_size]   # a negative bound: Python slicing
-    # raw device / stream accessors and a memoised workspace size: the call is a handful of launches (30-70 us of device time at
-    # inference sizes) and the Python around it was a third of nms_gpu's end-to-end time
-    prev = _get_device()
-    if prev != dev.index:
-        _set_device(dev.index)
-    try:
+    with _host.on_device(dev) as stream:
         keep = torch.empty(n, dtype=torch.int64, device=dev)
         num = torch.empty(1, dtype=torch.int64, device=dev)
-        stream = _raw_stream(dev.index)
-        if fused_sort:
-            sc = scores if scores.dtype == torch.float32 else scores.float()
-            sc = sc if sc.is_contiguous() else sc.contiguous()
-            ws = torch.empty(_ws_bytes(lib, True, n_all, n), dtype=torch.uint8, device=dev)
-            rc = lib.rnms_scored(int(normal), boxes.data_ptr(), sc.data_ptr(), n_all, n, float(thresh), keep.data_ptr(),
-                                 num.data_ptr(), ws.data_ptr(), stream)
-        else:
-            order = scores.sort(dim=0, descending=True, stable=True)[1]   # ties: lower index first
-            order = order[:n].contiguous()
-            ws = torch.empty(_ws_bytes(lib, False, n, n), dtype=torch.uint8, device=dev)
-            # the kernels read boxes[order[i]] themselves and emit kept indices in the caller's numbering
-            fn = lib.rnms_normal_bev_ordered if normal else lib.rnms_bev_ordered
-            rc = fn(boxes.data_ptr(), order.data_ptr(), n, float(thresh), keep.data_ptr(), num.data_ptr(), ws.data_ptr(), stream)
-    finally:
-        if prev != dev.index:
-            _set_device(prev)
-    if rc != 0:
-        _lib.check(rc, name)
-    if padded:   # nothing read back: (kept indices padded to n rows, count on the device); the post_max_size cut applies to both
-        if post_max_size is not None:
-            keep, num = keep[:post_max_size], num.clamp(max=max(int(post_max_size), 0))
-        return keep, num
-    k = _kept_count(int(num.item()), 'nms_gpu')  # the one unavoidable sync: the result length is data dependent
-    keep = keep[:k]
-    if post_max_size is not None:
-        keep = keep[:post_max_size]
-    return keep
+        order = scores.sort(dim=0, descending=True, stable=True)[1]   # ties: lower index first
+        order = order[:n].contiguous()
+        ws = torch.empty(_ws_bytes(n), dtype=torch.uint8, device=dev)
+        # the kernels read boxes[order[i]] themselves and emit kept indices in the caller's numbering
+        fn = lib.rnms_normal_bev_ordered if normal else lib.rnms_bev_ordered
+        rc = fn(boxes.data_ptr(), order.data_ptr(), n, float(thresh), keep.data_ptr(), num.data_ptr(), ws.data_ptr(), stream)
+    _lib.check(rc, name)
+    if padded:
+        return _cut_padded(keep, num, post_max_size)
+    keep = keep[:_read_counts(num, name)[0]]  # the one unavoidable sync: the result length is data dependent
+    return keep if post_max_size is None else keep[:post_max_size]
 
 
 _SCORED_MAX = None
-_WS_BYTES = {}
-_raw_stream = torch._C._cuda_getCurrentRawStream
-_get_device = torch._C._cuda_getDevice
-_set_device = torch._C._cuda_setDevice
-
-
-def _ws_bytes(lib, scored, n_all, n):
-    """rnms_scored_workspace_bytes(n_all, n) / rnms_workspace_bytes(n), memoised (one ctypes call less per NMS)."""
-    key = (scored, n_all, n)
-    b = _WS_BYTES.get(key)
-    if b is None:
-        if len(_WS_BYTES) > 4096:
-            _WS_BYTES.clear()
-        b = _WS_BYTES[key] = int(lib.rnms_scored_workspace_bytes(n_all, n) if scored else lib.rnms_workspace_bytes(n))
-    return b
-
-
-_BATCHED_WS = {}
-
-
-def _batched_ws_bytes(lib, G, N, cap):
-    key = (G, N, cap)
-    b = _BATCHED_WS.get(key)
-    if b is None:
-        if len(_BATCHED_WS) > 4096:
-            _BATCHED_WS.clear()
-        b = _BATCHED_WS[key] = int(lib.rnms_batched_scored_workspace_bytes(G, N, cap))
-    return b
+_ws_bytes = _host.memo(lambda n: int(_lib.load().rnms_workspace_bytes(n)))
+_batched_ws_bytes = _host.memo(lambda G, N, cap: int(_lib.load().rnms_batched_scored_workspace_bytes(G, N, cap)))
 
 
 def _scored_max(lib):
@@ -170,6 +112,21 @@ def _scored_max(lib):
     if _SCORED_MAX is None:
         _SCORED_MAX = int(lib.rnms_scored_max_n())
     return _SCORED_MAX
+
+
+def _read_counts(num, name):
+    """The device-resident counts of the ordered, segmented and circle forms as ints: one copy, one sync."""
+    return [_host.kept_count(k, name) for k in num.tolist()]
+
+
+def _no_groups(G, dev):
+    return [torch.zeros((0,), dtype=torch.int64, device=dev) for _ in range(G)]
+
+
+def _cut_groups(keep, nums, post_max_size):
+    """keep (G, cap) -> per group its first nums[g] entries, then at most post_max_size of them (a slice bound: None, negative)"""
+    out = [keep[g, :k] for g, k in enumerate(nums)]
+    return out if post_max_size is None else [k[:post_max_size] for k in out]
 
 
 def nms_gpu(boxes, scores, thresh, pre_max_size=None, post_max_size=None, pre_maxsize=None, padded=False):
@@ -186,14 +143,6 @@ def nms_gpu(boxes, scores, thresh, pre_max_size=None, post_max_size=None, pre_ma
 def nms_normal_gpu(boxes, scores, thresh):
     """Axis-aligned BEV NMS (angle ignored), mmdet3d `nms_normal_gpu`."""
     return _nms(boxes, scores, thresh, None, None, normal=True)
-
-
-def _kept_count(k, name):
-    """A negative count is the scan kernel's failure mark (a wave of the list scan stopped making progress and its bounded polling
-    loop gave up: never observed; a bug must surface as an error, not as a hang or a wrong list)."""
-    if k < 0:
-        raise RuntimeError(f'{name}: the device-side NMS scan gave up (num_keep = {k}); the result is void')
-    return k
 
 
 _THRESH_CACHE = {}
@@ -235,7 +184,7 @@ def nms_gpu_batched(boxes, scores, thresh, valid=None, pre_max_size=None, post_m
     if G == 0:
         return []
     if N == 0:
-        return [torch.zeros((0,), dtype=torch.int64, device=dev) for _ in range(G)]
+        return _no_groups(G, dev)
     if pre_max_size is not None and pre_max_size < 0:
         # `order[:pre_max_size]` with a negative bound keeps (group size + bound) boxes: a different cut per group, so the
         # promise "equal to nms_gpu per group" is kept by making exactly those calls
@@ -255,27 +204,19 @@ def nms_gpu_batched(boxes, scores, thresh, valid=None, pre_max_size=None, post_m
         # the library takes the score order itself (rank by counting per group): no masked_fill / sum / sort passes here
         cap = N if pre_max_size is None else max(min(N, int(pre_max_size)), 0)
         if cap == 0:
-            return [torch.zeros((0,), dtype=torch.int64, device=dev) for _ in range(G)]
-        with torch.cuda.device(dev):
-            sc = (scores if scores.dtype == torch.float32 else scores.float()).contiguous()
-            vb = None if valid is None else valid.to(torch.bool).contiguous()   # 1 byte per flag
-            th = _thresh_tensor(thresh, G, dev)
-            keep = torch.empty((G, cap), dtype=torch.int64, device=dev)
-            ws = torch.empty(_batched_ws_bytes(lib, G, N, cap), dtype=torch.uint8, device=dev)
-            # the G data-dependent result lengths arrive in pinned host memory, written by the scan kernels themselves, and are
-            # polled there: no copy call, no stream synchronisation (_pynode.count_mailbox)
-            box, words = _pynode.count_mailbox(G)
-            words[:G] = _pynode._PENDING
-            _lib.check(lib.rnms_batched_scored(mode, boxes.data_ptr(), sc.data_ptr(), None if vb is None else vb.data_ptr(), G, N,
-                                               cap, th.data_ptr(), keep.data_ptr(), box.data_ptr(), ws.data_ptr(),
-                                               _raw_stream(dev.index)), name)
-        nums = [_kept_count(k, name) for k in _pynode.wait_counts(words, G, dev)]  # the one wait
-        out = []
-        for g in range(G):
-            k = keep[g, :nums[g]]
-            out.append(k if post_max_size is None else k[:post_max_size])
-        return out
-    with torch.cuda.device(dev):
+            return _no_groups(G, dev)
+        sc = (scores if scores.dtype == torch.float32 else scores.float()).contiguous()
+        vb = None if valid is None else valid.to(torch.bool).contiguous()   # 1 byte per flag
+        th = _thresh_tensor(thresh, G, dev)
+        keep = torch.empty((G, cap), dtype=torch.int64, device=dev)
+        ws = torch.empty(_batched_ws_bytes(G, N, cap), dtype=torch.uint8, device=dev)
+        # the G data-dependent result lengths arrive in pinned host memory, written by the scan kernels themselves, and are
+        # polled there: no copy call, no stream synchronisation; the one wait (_host.launch_counted)
+        nums = _host.launch_counted(G, dev, name, lambda num_keep, stream: lib.rnms_batched_scored(
+            mode, boxes.data_ptr(), sc.data_ptr(), _host.ptr(vb), G, N, cap, th.data_ptr(), keep.data_ptr(), num_keep, ws.data_ptr(),
+            stream))
+        return _cut_groups(keep, nums, post_max_size)
+    with _host.on_device(dev) as stream:
         if valid is None:
             key = scores
             counts = torch.full((G,), N, dtype=torch.int32, device=dev)
@@ -290,21 +231,15 @@ def nms_gpu_batched(boxes, scores, thresh, valid=None, pre_max_size=None, post_m
             order = order[:, :cap]
             counts = counts.clamp(max=cap)
         if cap == 0:
-            return [torch.zeros((0,), dtype=torch.int64, device=dev) for _ in range(G)]
+            return _no_groups(G, dev)
         order = order.contiguous()
         th = _thresh_tensor(thresh, G, dev)
         keep = torch.empty((G, cap), dtype=torch.int64, device=dev)
         num = torch.empty(G, dtype=torch.int64, device=dev)
         ws = torch.empty(lib.rnms_batched_workspace_bytes(G, cap), dtype=torch.uint8, device=dev)
         _lib.check(lib.rnms_batched(mode, boxes.data_ptr(), order.data_ptr(), counts.data_ptr(), G, cap, th.data_ptr(),
-                                    keep.data_ptr(), num.data_ptr(), ws.data_ptr(),
-                                    torch.cuda.current_stream().cuda_stream), name)
-    nums = [_kept_count(k, 'nms (batched)') for k in num.tolist()]  # the one sync: G data-dependent result lengths
-    out = []
-    for g in range(G):
-        k = keep[g, :nums[g]]
-        out.append(k if post_max_size is None else k[:post_max_size])
-    return out
+                                    keep.data_ptr(), num.data_ptr(), ws.data_ptr(), stream), name)
+    return _cut_groups(keep, _read_counts(num, name), post_max_size)  # the one sync: G data-dependent result lengths
 
 
 def nms_gpu_multi(boxes_list, scores_list, thresh, pre_max_size=None, post_max_size=None, normal=False):
@@ -329,7 +264,7 @@ def nms_gpu_multi(boxes_list, scores_list, thresh, pre_max_size=None, post_max_s
     dev = boxes_list[0].device
     total, nmax = sum(sizes), max(sizes)
     if total == 0:
-        return [torch.zeros((0,), dtype=torch.int64, device=dev) for _ in range(G)]
+        return _no_groups(G, dev)
     lib = _lib.load()
     ths = list(thresh) if isinstance(thresh, (list, tuple)) else [thresh] * G
     if len(ths) != G:
@@ -340,11 +275,11 @@ def nms_gpu_multi(boxes_list, scores_list, thresh, pre_max_size=None, post_max_s
         return [_nms(b, s2, t, pre_max_size, post_max_size, normal) for b, s2, t in zip(boxes_list, scores_list, ths)]
     cap = nmax if pre_max_size is None else min(nmax, int(pre_max_size))
     if cap == 0:
-        return [torch.zeros((0,), dtype=torch.int64, device=dev) for _ in range(G)]
+        return _no_groups(G, dev)
     offs = [0]
     for n in sizes:
         offs.append(offs[-1] + n)
-    with torch.cuda.device(dev):
+    with _host.on_device(dev) as stream:
         boxes = _check_boxes(torch.cat([b.reshape(-1, 5) for b in boxes_list], dim=0), 5, 'nms_gpu_multi')
         flat = torch.cat([s2.reshape(-1) for s2 in scores_list], dim=0).to(torch.float32).contiguous()
         seg = torch.tensor(offs, dtype=torch.int32, device=dev)
@@ -353,15 +288,10 @@ def nms_gpu_multi(boxes_list, scores_list, thresh, pre_max_size=None, post_max_s
         num = torch.empty(G, dtype=torch.int64, device=dev)
         ws = torch.empty(lib.rnms_batched_scored_workspace_bytes(G, nmax, cap), dtype=torch.uint8, device=dev)
         _lib.check(lib.rnms_segmented_scored(1 if normal else 0, boxes.data_ptr(), flat.data_ptr(), seg.data_ptr(), G, nmax, cap,
-                                             th.data_ptr(), keep.data_ptr(), num.data_ptr(), ws.data_ptr(),
-                                             torch.cuda.current_stream().cuda_stream), 'nms_gpu_multi')
+                                             th.data_ptr(), keep.data_ptr(), num.data_ptr(), ws.data_ptr(), stream),
+                   'nms_gpu_multi')
         keep = keep - seg[:G].to(torch.int64).unsqueeze(1)          # indices local to each entry
-    nums = [_kept_count(k, 'nms (batched)') for k in num.tolist()]  # the one sync: G data-dependent result lengths
-    out = []
-    for g in range(G):
-        k = keep[g, :nums[g]]
-        out.append(k if post_max_size is None else k[:post_max_size])
-    return out
+    return _cut_groups(keep, _read_counts(num, 'nms_gpu_multi'), post_max_size)  # the one sync: G data-dependent result lengths
 
 
 def multi_class_nms(box_probs, boxes_for_nms, score_thr, nms_thr, use_rotate_nms=True):
@@ -448,68 +378,44 @@ def circle_nms(dets, thresh, post_max_size=83):
     if n == 0:
         return torch.zeros((0,), dtype=torch.int64, device=dev)
     lib = _lib.load()
-    with torch.cuda.device(dev):
+    with _host.on_device(dev) as stream:
         order = dets[:, 2].sort(dim=0, descending=True, stable=True)[1].contiguous()
         xy = dets[:, :2].contiguous()
         keep = torch.empty(n, dtype=torch.int64, device=dev)
         num = torch.empty(1, dtype=torch.int64, device=dev)
         ws = torch.empty(lib.rnms_workspace_bytes(n), dtype=torch.uint8, device=dev)
         _lib.check(lib.rnms_circle_ordered(xy.data_ptr(), order.data_ptr(), n, float(thresh), keep.data_ptr(),
-                                           num.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                   'circle_nms')
-    keep = keep[:_kept_count(int(num.item()), 'circle_nms')]
+                                           num.data_ptr(), ws.data_ptr(), stream), 'circle_nms')
+    keep = keep[:_read_counts(num, 'circle_nms')[0]]
     return keep if post_max_size is None else keep[:post_max_size]
+
+
+def _pairwise(entry, name, a, b, cols, extra=()):
+    """One (M,cols) x (N,cols) -> (M,N) fp32 matrix through `entry` (GPU tensors) or `entry`_cpu (CPU tensors: the twin takes
+    torch's intra-op thread count as its team size)."""
+    a = _check_boxes(a, cols, name, cpu_ok=True)
+    b = _check_boxes(b, cols, name, cpu_ok=True)
+    if a.device != b.device:
+        raise RuntimeError(f'{name}: operands live on different devices ({a.device}, {b.device})')
+    out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
+    _host.call(entry, a.device, (a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], *extra, out.data_ptr()), (torch.get_num_threads(),))
+    return out
 
 
 def boxes_iou_bev(boxes_a, boxes_b):
     """Pairwise rotated BEV IoU of [x1,y1,x2,y2,ry] boxes: (M,5),(N,5) -> (M,N) (mmdet3d `boxes_iou_bev`)."""
-    a = _check_boxes(boxes_a, 5, 'boxes_iou_bev', cpu_ok=True)
-    b = _check_boxes(boxes_b, 5, 'boxes_iou_bev', cpu_ok=True)
-    lib = _lib.load()
-    _same_device(a, b, 'boxes_iou_bev')
-    out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
-    if not a.is_cuda:
-        _lib.check(lib.riou_bev_xyxyr_cpu(a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], out.data_ptr(), torch.get_num_threads()),
-                   'riou_bev_xyxyr_cpu')
-        return out
-    with torch.cuda.device(a.device):
-        _lib.check(lib.riou_bev_xyxyr(_ptr(a), a.shape[0], _ptr(b), b.shape[0], _ptr(out), _stream(a.device)),
-                   'riou_bev_xyxyr')
-    return out
+    return _pairwise('riou_bev_xyxyr', 'boxes_iou_bev', boxes_a, boxes_b, 5)
 
 
 def iou_bev(det, gt):
-    """(D,7),(G,7) [x,y,z,w,h,l,yaw] -> (D,G) BEV IoU; GPU counterpart of ops/eval `iou_bev`."""
-    d = _check_boxes(det, 7, 'iou_bev', cpu_ok=True)
-    g = _check_boxes(gt, 7, 'iou_bev', cpu_ok=True)
-    lib = _lib.load()
-    _same_device(d, g, 'iou_bev')
-    out = torch.empty((d.shape[0], g.shape[0]), dtype=torch.float32, device=d.device)
-    if not d.is_cuda:   # the reference's own helper is CPU code (affinity.cpp:51-81): the `_cpu` twin
-        _lib.check(lib.riou_eval_bev_cpu(d.data_ptr(), d.shape[0], g.data_ptr(), g.shape[0], out.data_ptr(), torch.get_num_threads()),
-                   'riou_eval_bev_cpu')
-        return out
-    with torch.cuda.device(d.device):
-        _lib.check(lib.riou_eval_bev(_ptr(d), d.shape[0], _ptr(g), g.shape[0], _ptr(out), _stream(d.device)),
-                   'riou_eval_bev')
-    return out
+    """(D,7),(G,7) [x,y,z,w,h,l,yaw] -> (D,G) BEV IoU; GPU counterpart of ops/eval `iou_bev` (the reference's own helper is CPU
+    code, affinity.cpp:51-81: CPU tensors take the `_cpu` twin)."""
+    return _pairwise('riou_eval_bev', 'iou_bev', det, gt, 7)
 
 
 def iou_3d(det, gt, z_offset=0.5):
     """(D,7),(G,7) -> (D,G) 3D IoU with the reference's `z_offset` convention (affinity.cpp:26-29)."""
-    d = _check_boxes(det, 7, 'iou_3d', cpu_ok=True)
-    g = _check_boxes(gt, 7, 'iou_3d', cpu_ok=True)
-    lib = _lib.load()
-    _same_device(d, g, 'iou_3d')
-    out = torch.empty((d.shape[0], g.shape[0]), dtype=torch.float32, device=d.device)
-    if not d.is_cuda:
-        _lib.check(lib.riou_eval_3d_cpu(d.data_ptr(), d.shape[0], g.data_ptr(), g.shape[0], float(z_offset), out.data_ptr(),
-                                        torch.get_num_threads()), 'riou_eval_3d_cpu')
-        return out
-    with torch.cuda.device(d.device):
-        _lib.check(lib.riou_eval_3d(_ptr(d), d.shape[0], _ptr(g), g.shape[0], float(z_offset), _ptr(out),
-                                    _stream(d.device)), 'riou_eval_3d')
-    return out
+    return _pairwise('riou_eval_3d', 'iou_3d', det, gt, 7, (float(z_offset),))
 
 
 def xywhr2xyxyr(boxes_xywhr):

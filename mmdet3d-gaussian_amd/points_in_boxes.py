@@ -22,23 +22,11 @@ RuntimeError.  Nothing here is differentiable (the reference's versions are not 
 """
 import torch
 
-from . import _lib
-from .scatter import _on_device
-from .vsa import _cnt32, _ptr, _rows
+from ._host import call as _call, counts_i32 as _cnt32, ptr_or_null as _ptr, rows_f32 as _rows
 
 BOX_TILE = 256            # boxes a workgroup holds in LDS at a time (gd3d_pib_box_tile())
 WORKGROUP_POINTS = 256    # points of one sample a workgroup owns (gd3d_pib_workgroup_points())
 MAX_GRID_SIZE = 16
-
-
-def _call(name, dev, args):
-    lib = _lib.load()
-    if dev.type == 'cuda':
-        with _on_device(dev) as stream:
-            rc = getattr(lib, name)(*args, stream)
-    else:
-        rc = getattr(lib, name + '_cpu')(*args, 0)
-    _lib.check(rc, name)
 
 
 def _boxes(boxes, like, name='boxes'):
@@ -69,8 +57,7 @@ def points_in_boxes_part_stacked(xyz, xyz_batch_cnt, boxes, box_cnt=None):
     x, xc, bx, bc = _stacked_args(xyz, xyz_batch_cnt, boxes, box_cnt)
     out = torch.empty((x.size(0),), dtype=torch.int32, device=x.device)
     if x.size(0) > 0:
-        _call('gd3d_pib_part', x.device, (_ptr(x), _ptr(xc), _ptr(bx), _ptr(bc) if bc is not None else None, xc.numel(), x.size(0),
-                                          bx.size(1), _ptr(out)))
+        _call('gd3d_pib_part', x.device, (_ptr(x), _ptr(xc), _ptr(bx), _ptr(bc), xc.numel(), x.size(0), bx.size(1), _ptr(out)), (0,))
     return out
 
 
@@ -82,8 +69,8 @@ def points_in_boxes_all_stacked(xyz, xyz_batch_cnt, boxes, box_cnt=None, dtype=t
     x, xc, bx, bc = _stacked_args(xyz, xyz_batch_cnt, boxes, box_cnt)
     out = torch.empty((x.size(0), bx.size(1)), dtype=dtype, device=x.device)
     if out.numel() > 0:
-        _call('gd3d_pib_all', x.device, (_ptr(x), _ptr(xc), _ptr(bx), _ptr(bc) if bc is not None else None, xc.numel(), x.size(0),
-                                         bx.size(1), _ptr(out), 4 if dtype == torch.int32 else 1))
+        _call('gd3d_pib_all', x.device, (_ptr(x), _ptr(xc), _ptr(bx), _ptr(bc), xc.numel(), x.size(0), bx.size(1), _ptr(out),
+                                         4 if dtype == torch.int32 else 1), (0,))
     return out
 
 
@@ -157,8 +144,8 @@ def pointwise_mask_targets(xyz, xyz_batch_cnt, gt_boxes, gt_labels, extra_width,
     idx = torch.empty((x.size(0),), dtype=torch.int32, device=x.device) if return_box_idx else None
     if x.size(0) > 0:
         _call('gd3d_pib_mask_targets', x.device,
-              (_ptr(x), _ptr(xc), _ptr(bx), _ptr(lb), _ptr(bc) if bc is not None else None, xc.numel(), x.size(0), bx.size(1),
-               float(extra_width), int(num_classes), _ptr(seg), _ptr(idx) if idx is not None else None))
+              (_ptr(x), _ptr(xc), _ptr(bx), _ptr(lb), _ptr(bc), xc.numel(), x.size(0), bx.size(1),
+               float(extra_width), int(num_classes), _ptr(seg), _ptr(idx)), (0,))
     return (seg, idx) if return_box_idx else seg
 
 
@@ -174,7 +161,7 @@ def _grid_points(rows, first, grid_size, clockwise):
     r = rows.detach().to(torch.float32).contiguous()
     out = torch.empty((r.size(0), g ** 3, 3), dtype=torch.float32, device=r.device)
     if r.size(0) > 0:
-        _call('gd3d_roi_grid_points', r.device, (_ptr(r), r.size(1), first, r.size(0), g, 1 if clockwise else 0, _ptr(out)))
+        _call('gd3d_roi_grid_points', r.device, (_ptr(r), r.size(1), first, r.size(0), g, 1 if clockwise else 0, _ptr(out)), (0,))
     return out.to(rows.dtype)
 
 

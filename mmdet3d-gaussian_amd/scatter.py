@@ -9,30 +9,9 @@ the host (`_index_and_grouping`).  `scatter_reduce` keeps the reference's signat
 """
 import torch
 
-from . import _lib
+from . import _host, _lib
 
 REDUCE = {'sum': 0, 'mean': 1, 'max': 2}  # reduce_t, src/voxelization.h:4
-_raw_stream = torch._C._cuda_getCurrentRawStream
-_get_device = torch._C._cuda_getDevice
-_set_device = torch._C._cuda_setDevice
-
-
-class _on_device:
-    """Minimal device guard (raw accessors: no Python-level bookkeeping on the per-call path)."""
-
-    def __init__(self, dev):
-        self.idx = dev.index
-
-    def __enter__(self):
-        self.prev = _get_device()
-        if self.prev != self.idx:
-            _set_device(self.idx)
-        return _raw_stream(self.idx)
-
-    def __exit__(self, *exc):
-        if self.prev != self.idx:
-            _set_device(self.prev)
-        return False
 
 
 def _index_and_grouping(coors):
@@ -68,7 +47,7 @@ def _index_and_grouping(coors):
     if nbytes == 0:
         raise RuntimeError('vox_index_workspace_bytes failed (no usable device for the sort-size query)')
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with _on_device(dev) as stream:
+    with _host.on_device(dev) as stream:
         rc = lib.vox_index_build(c32.data_ptr(), n, ndim, ws.data_ptr(), pmap.data_ptr(), order.data_ptr(), seg.data_ptr(),
                                  counts.data_ptr(), vcoors.data_ptr(), num.data_ptr(), stream)
     _lib.check(rc, 'vox_index_build')

@@ -16,32 +16,10 @@ counts are converted.
 """
 import torch
 
-from . import _lib
-from .scatter import _on_device
+from . import _host, _lib
+from ._host import counts_i32 as _cnt32, ptr_or_null as _ptr, rows_f32 as _rows
 
 MAX_NSAMPLE = 1024
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() > 0 else None
-
-
-def _cnt32(cnt, like, name):
-    if cnt.dim() != 1:
-        raise RuntimeError(f'{name} must be a (batch_size,) integer tensor, got shape {tuple(cnt.shape)}')
-    if cnt.dtype.is_floating_point or cnt.dtype == torch.bool:
-        raise RuntimeError(f'{name} must be an integer tensor, got {cnt.dtype}')
-    if cnt.device != like.device:
-        raise RuntimeError(f'{name} is on {cnt.device}, the points on {like.device}')
-    return cnt.to(torch.int32).contiguous()
-
-
-def _rows(t, cols, name):
-    if t.dim() != 2 or (cols is not None and t.size(1) != cols):
-        raise RuntimeError(f'shape mismatch: {name} must be (rows, {cols if cols is not None else "C"}), got {tuple(t.shape)}')
-    if not t.dtype.is_floating_point:
-        raise RuntimeError(f'{name} must be a floating-point tensor, got {t.dtype}')
-    return t.detach().to(torch.float32).contiguous()
 
 
 def _check_nsample(nsample):
@@ -53,7 +31,6 @@ def _check_nsample(nsample):
 
 def _query_and_group(xyz, xyz_cnt, new_xyz, new_cnt, features, radius, nsample, use_xyz, group):
     """The one forward launch: (out | None, idx, cnt, mask); every argument already fp32 / int32 / contiguous."""
-    lib = _lib.load()
     dev = new_xyz.device
     n, m, b = xyz.size(0), new_xyz.size(0), xyz_cnt.numel()
     c = features.size(1) if features is not None else 0
@@ -63,14 +40,9 @@ def _query_and_group(xyz, xyz_cnt, new_xyz, new_cnt, features, radius, nsample, 
     out = torch.empty((m, (3 if use_xyz else 0) + c, nsample), dtype=torch.float32, device=dev) if group else None
     if m == 0:
         return out, idx, cnt, mask
-    args = (_ptr(xyz), _ptr(xyz_cnt), _ptr(new_xyz), _ptr(new_cnt), _ptr(features), b, n, m, c, float(radius), nsample,
-            1 if use_xyz else 0, _ptr(out), _ptr(idx), _ptr(cnt), _ptr(mask))
-    if dev.type == 'cuda':
-        with _on_device(dev) as stream:
-            rc = lib.gd3d_vsa_query_and_group(*args, stream)
-    else:
-        rc = lib.gd3d_vsa_query_and_group_cpu(*args, 0)
-    _lib.check(rc, 'gd3d_vsa_query_and_group')
+    _host.call('gd3d_vsa_query_and_group', dev,
+               (_ptr(xyz), _ptr(xyz_cnt), _ptr(new_xyz), _ptr(new_cnt), _ptr(features), b, n, m, c, float(radius), nsample,
+                1 if use_xyz else 0, _ptr(out), _ptr(idx), _ptr(cnt), _ptr(mask)), (0,))
     return out, idx, cnt, mask
 
 
@@ -99,33 +71,17 @@ def ball_query(radius, nsample, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, 
     return (idx, mask, cnt) if return_cnt else (idx, mask)
 
 
-def _backward_call(name, dev, args):
-    lib = _lib.load()
-    if dev.type == 'cuda':
-        with _on_device(dev) as stream:
-            rc = getattr(lib, name)(*args, stream)
-    else:
-        rc = getattr(lib, name + '_cpu')(*args)
-    _lib.check(rc, name)
-
-
 class _Grouping(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, features_batch_cnt, idx, idx_batch_cnt):
-        lib = _lib.load()
         f32 = features.detach().to(torch.float32).contiguous()
         n, c = f32.shape
         m, nsample = idx.shape
         b = features_batch_cnt.numel()
         out = torch.empty((m, c, nsample), dtype=torch.float32, device=f32.device)
         if m > 0:
-            args = (_ptr(f32), _ptr(features_batch_cnt), _ptr(idx), _ptr(idx_batch_cnt), b, n, m, c, nsample, _ptr(out))
-            if f32.is_cuda:
-                with _on_device(f32.device) as stream:
-                    rc = lib.gd3d_vsa_group(*args, stream)
-            else:
-                rc = lib.gd3d_vsa_group_cpu(*args, 0)
-            _lib.check(rc, 'gd3d_vsa_group')
+            _host.call('gd3d_vsa_group', f32.device,
+                       (_ptr(f32), _ptr(features_batch_cnt), _ptr(idx), _ptr(idx_batch_cnt), b, n, m, c, nsample, _ptr(out)), (0,))
         ctx.save_for_backward(idx, features_batch_cnt, idx_batch_cnt)
         ctx.shape = (n, c)
         ctx.dtype = features.dtype
@@ -139,9 +95,9 @@ class _Grouping(torch.autograd.Function):
         g = grad_out.detach().to(torch.float32).contiguous()
         grad = torch.empty((n, c), dtype=torch.float32, device=g.device)
         if n > 0:
-            _backward_call('gd3d_vsa_group_backward', g.device,
-                           (_ptr(g), _ptr(idx), _ptr(idx_batch_cnt), _ptr(features_batch_cnt), features_batch_cnt.numel(), n, m, c,
-                            nsample, _ptr(grad)))
+            _host.call('gd3d_vsa_group_backward', g.device,
+                       (_ptr(g), _ptr(idx), _ptr(idx_batch_cnt), _ptr(features_batch_cnt), features_batch_cnt.numel(), n, m, c,
+                        nsample, _ptr(grad)))
         return grad.to(ctx.dtype), None, None, None
 
 
@@ -187,9 +143,9 @@ class _QueryAndGroup(torch.autograd.Function):
         g = grad_out.detach().to(torch.float32).contiguous()
         grad = torch.empty((n, c), dtype=torch.float32, device=g.device)
         if n > 0 and c > 0:
-            _backward_call('gd3d_vsa_query_and_group_backward', g.device,
-                           (_ptr(g), _ptr(idx), _ptr(cnt), _ptr(new_cnt), _ptr(xyz_cnt), xyz_cnt.numel(), n, m, c, nsample, ctx.c_off,
-                            _ptr(grad)))
+            _host.call('gd3d_vsa_query_and_group_backward', g.device,
+                       (_ptr(g), _ptr(idx), _ptr(cnt), _ptr(new_cnt), _ptr(xyz_cnt), xyz_cnt.numel(), n, m, c, nsample, ctx.c_off,
+                        _ptr(grad)))
         return (grad.to(ctx.dtype),) + (None,) * 7
 
 
@@ -251,7 +207,7 @@ def furthest_point_sample(xyz, npoint):
         return out
     if x.is_cuda:
         ws = _fps_workspace(lib, b * n, x.device)
-        with _on_device(x.device) as stream:
+        with _host.on_device(x.device) as stream:
             rc = lib.gd3d_vsa_fps(_ptr(x), b, n, npoint, _ptr(out), ws.data_ptr(), stream)
     else:
         rc = lib.gd3d_vsa_fps_cpu(_ptr(x), b, n, npoint, _ptr(out), 0)
@@ -276,7 +232,7 @@ def furthest_point_sample_stacked(xyz, xyz_batch_cnt, npoint):
         return out
     if x.is_cuda:
         ws = _fps_workspace(lib, n, x.device)
-        with _on_device(x.device) as stream:
+        with _host.on_device(x.device) as stream:
             rc = lib.gd3d_vsa_fps_stacked(_ptr(x), _ptr(xc), b, n, npoint, _ptr(out), ws.data_ptr(), stream)
     else:
         rc = lib.gd3d_vsa_fps_stacked_cpu(_ptr(x), _ptr(xc), b, n, npoint, _ptr(out), 0)

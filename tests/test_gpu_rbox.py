@@ -1135,3 +1135,90 @@ def test_classic_scan_bit_exact_with_the_list_scan_switched_off(amd):
     env = dict(os.environ, RNMS_LIST_MIN_THR='2')
     r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and 'classic ok' in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+@pytest.mark.parametrize('n', [1, 65, 1000])
+def test_nms_scores_of_any_dtype_or_stride_take_the_scored_path(amd, host_glue, monkeypatch, n):
+    """fp16, bf16 and strided fp32 scores are converted to contiguous fp32 and go through the host glue's `nms_scored` like plain
+    fp32 scores (no second call path with a device count word): same keep lists as for `scores.float().contiguous()` and as the
+    `_cpu` twin on the same values, for every padded / normal form and with pre / post cuts.  The scores are multiples of 1/256 in
+    [0, 1]: exact in fp16 and bf16 (8 significant bits), so every dtype orders alike."""
+    import sys
+    import types
+    from mmdet3d_gaussian_amd import _lib
+    iou3d = sys.modules[amd.nms_gpu.__module__]
+    boxes, u = nms_boxes(n, seed=n + 7)
+    s32 = torch.from_numpy((np.round(u * 256) / 256).astype(np.float32))
+    b = torch.from_numpy(boxes).cuda()
+    sg = s32.cuda()
+    wide = torch.zeros(2 * n, dtype=torch.float32, device='cuda')
+    wide[::2] = sg
+    variants = {'fp16': sg.half(), 'bf16': sg.bfloat16(), 'strided': wide[::2]}
+    assert not variants['strided'].is_contiguous() or n == 1
+    for v in variants.values():
+        assert torch.equal(v.float(), sg)
+    node, seen = _lib.load_node(), []
+
+    def spy(boxes_, scores_, *rest):
+        seen.append((scores_.dtype, scores_.is_contiguous()))
+        return node.nms_scored(boxes_, scores_, *rest)
+    monkeypatch.setattr(_lib, '_node', types.SimpleNamespace(nms_scored=spy))
+    cuts = [(None, None)] + ([(40, 7)] if n == 1000 else [])
+    calls = 0
+    for padded in (False, True):
+        for normal in (False, True):
+            for pre, post in cuts:
+                ref = iou3d._nms(b, sg, 0.25, pre, post, normal, padded)
+                twin = iou3d._nms(b.cpu(), s32, 0.25, pre, post, normal, padded)
+                calls += 1
+                if padded:
+                    assert ref[1].is_cuda and ref[1].shape == (1,)
+                    k = int(ref[1])
+                    assert k == int(twin[1]) and torch.equal(ref[0][:k].cpu(), twin[0][:k])
+                else:
+                    assert torch.equal(ref.cpu(), twin)
+                for kind, sv in variants.items():
+                    got = iou3d._nms(b, sv, 0.25, pre, post, normal, padded)
+                    calls += 1
+                    if padded:   # the count stays on the device; entries past it are undefined
+                        assert got[1].is_cuda and torch.equal(got[1], ref[1]), (kind, padded, normal, pre)
+                        assert got[0].shape == ref[0].shape and torch.equal(got[0][:k], ref[0][:k]), (kind, padded, normal, pre)
+                    else:
+                        assert torch.equal(got, ref), (kind, padded, normal, pre)
+    assert seen == [(torch.float32, True)] * calls     # every GPU call above went through nms_scored, on contiguous fp32 scores
+
+
+def test_a_call_that_leaves_early_cannot_hand_its_count_to_the_next(amd, monkeypatch):
+    """A call that has marked its mailbox words pending and launched, and then leaves by an exception (here: the poll fails on its
+    first look), synchronises its stream first — its kernels' counts have arrived when the error reaches the caller, so no late
+    write can land in the words the next call marks pending.  Python glue (the C++ node's poll cannot be interrupted); the
+    injected failure is host-side only."""
+    from mmdet3d_gaussian_amd import _host, _lib
+    b300, s300 = nms_boxes(300, seed=5)
+    b65, s65 = nms_boxes(65, seed=6)
+    sg = np.random.default_rng(4).uniform(0, 1, (3, 300)).astype(np.float32)
+    tb300, ts300, tb65, ts65, tsg = (torch.from_numpy(x) for x in (b300, s300, b65, s65, sg))
+    want300 = amd.nms_gpu(tb300, ts300, 0.25)                      # CPU tensors: the `_cpu` twin
+    want65 = amd.nms_gpu(tb65, ts65, 0.25)
+    want_groups = [amd.nms_gpu(tb300, tsg[g], 0.25) for g in range(3)]
+    assert 0 < len(want65) != len(want300) and len({len(k) for k in want_groups} | {len(want65)}) > 1
+
+    def boom(words, g, dev):
+        raise RuntimeError('injected: the poll failed on its first look')
+    _lib.set_host_glue('python')
+    try:
+        for g, launch, counts in ((1, lambda: amd.nms_gpu(tb300.cuda(), ts300.cuda(), 0.25), [len(want300)]),
+                                  (3, lambda: amd.nms_gpu_batched(tb300.cuda(), tsg.cuda(), 0.25), [len(k) for k in want_groups])):
+            with monkeypatch.context() as m:
+                m.setattr(_host, 'wait_counts', boom)
+                with pytest.raises(RuntimeError, match='injected'):
+                    launch()
+            words = _host.count_mailbox(g)[1]
+            assert [int(words[i]) for i in range(g)] == counts   # nothing pending: the call's real counts, without any wait here
+            got = amd.nms_gpu(tb65.cuda(), ts65.cuda(), 0.25)
+            assert torch.equal(got.cpu(), want65)
+            kept = amd.nms_gpu_batched(tb300.cuda(), tsg.cuda(), 0.25)
+            for x, y in zip(kept, want_groups):
+                assert torch.equal(x.cpu(), y)
+    finally:
+        _lib.set_host_glue(None)
