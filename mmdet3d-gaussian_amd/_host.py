@@ -1,7 +1,9 @@
-"""The per-call plumbing between a torch tensor and an `extern "C"` entry point of libgd3d.so, once: raw stream / device
-accessors and the device guard, the pointer helpers, the GPU-or-`_cpu`-twin dispatch, operand normalisation of the stacked point
-ops, the bounded memo behind the workspace-size queries, and the pinned count mailbox of the NMS calls.  Imports nothing from the
-package but `_lib`; every module above the C ABI takes these from here.
+"""The per-call plumbing between a torch tensor and an `extern "C"` entry point of libgd3d.so / libgd3d_extras.so, once: raw
+stream / device accessors and the device guard, the pointer helpers, the GPU-only refusal, the GPU-or-`_cpu`-twin dispatch and its
+extras counterpart, operand normalisation (contiguous fp32 / int64, the stacked point ops, the device-resident normaliser, the
+threshold tensors), the dict-or-object config lookup, the bounded memo behind the workspace-size queries, the unit-gradient
+registry, the double-backward guard of the autograd nodes, and the pinned count mailbox of the NMS calls.  Imports nothing from
+the package but `_lib`; every module above the C ABI takes these from here.
 """
 import threading
 import time
@@ -46,6 +48,36 @@ def ptr_or_null(t):
     return t.data_ptr() if t is not None and t.numel() > 0 else None
 
 
+def gpu_only(t, who):
+    """The wrappers without a `_cpu` twin refuse a CPU tensor here (a missing kernel is an error, never another path)."""
+    if not t.is_cuda:
+        raise RuntimeError(f'{who}: the MI355X implementation has no CPU path')
+
+
+def f32c(t):
+    """t as contiguous fp32; t itself when it already is."""
+    if t.dtype != torch.float32:
+        t = t.float()
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def i64c(t):
+    """t as contiguous int64; t itself when it already is."""
+    if t.dtype != torch.int64:
+        t = t.long()
+    return t if t.is_contiguous() else t.contiguous()
+
+
+_REQUIRED = object()
+
+
+def cfg_get(cfg, key, default=_REQUIRED):
+    """cfg[key] of a config dict or cfg.key of a config object / loss module; without a default a missing key raises."""
+    if isinstance(cfg, dict):
+        return cfg[key] if default is _REQUIRED else cfg.get(key, default)
+    return getattr(cfg, key) if default is _REQUIRED else getattr(cfg, key, default)
+
+
 def call(name, dev, args, cpu_tail=()):
     """GPU tensors: lib.<name>(*args, current stream of `dev`) under the device guard; CPU tensors: the twin
     lib.<name>_cpu(*args, *cpu_tail) — the twins end differently (a thread count, a reserved 0, nothing), so the caller spells the
@@ -57,6 +89,15 @@ def call(name, dev, args, cpu_tail=()):
     else:
         name += '_cpu'
         rc = getattr(lib, name)(*args, *cpu_tail)
+    _lib.check(rc, name)
+
+
+def call_extras(name, dev, args):
+    """`call` for libgd3d_extras.so: lib.<name>(*args, current stream of `dev`) under the device guard.  GPU tensors only: the
+    extras have no `_cpu` twins."""
+    lib = _lib.load_extras()
+    with on_device(dev) as stream:
+        rc = getattr(lib, name)(*args, stream)
     _lib.check(rc, name)
 
 
@@ -80,6 +121,31 @@ def counts_i32(cnt, like, name):
     return cnt.to(torch.int32).contiguous()
 
 
+def avg_tensor(t, dev, who):
+    """num_total_samples as a device-resident normaliser: one fp32 value on `dev`, detached"""
+    if t.numel() != 1 or t.device != dev:
+        raise RuntimeError(f'{who}: a tensor num_total_samples must hold one value on {dev}, got {tuple(t.shape)} on {t.device}')
+    t = t.detach().reshape(())
+    return t if t.dtype == torch.float32 else t.float()
+
+
+_THRESH_CACHE = {}
+
+
+def thresh_tensor(thresh, groups, dev):
+    """One threshold, or one per group, as a (groups,) fp32 tensor on `dev`; remembered per (values, device)."""
+    vals = tuple(float(t) for t in thresh) if isinstance(thresh, (list, tuple)) else (float(thresh),) * groups
+    if len(vals) != groups:
+        raise RuntimeError(f'{len(vals)} thresholds for {groups} groups')
+    key = (vals, dev)
+    t = _THRESH_CACHE.get(key)
+    if t is None:
+        if len(_THRESH_CACHE) > 64:
+            _THRESH_CACHE.clear()
+        t = _THRESH_CACHE[key] = torch.tensor(vals, dtype=torch.float32, device=dev)
+    return t
+
+
 def memo(fn, limit=4096):
     """fn(*key) remembered per key (the workspace-size queries: one ctypes call less per launch); the table empties itself once
     it holds more than `limit` keys."""
@@ -93,6 +159,74 @@ def memo(fn, limit=4096):
             v = table[key] = fn(*key)
         return v
     return get
+
+
+# ---- the unit gradient ----------------------------------------------------------------------------------------------------------
+
+_UNIT_GRAD = {}     # device index (-1: the CPU) -> (the constant tensor, its address)
+
+
+def unit_grad(device):
+    """The upstream gradient 1.0 as a CONSTANT of this library: one read-only 0-dim fp32 tensor per device.
+
+    `loss.backward()` makes torch fill a fresh ones tensor (one launch) and our backward then has to READ it on the device
+    to learn that nothing needs scaling (one more launch, gd3d_grad_finish's early exit).  A training step that passes this
+    tensor instead -- `torch.autograd.backward([l0, l1, l2], grad_tensors=[unit_grad(dev)] * 3)` -- is recognised by
+    ADDRESS (no read, no sync): the gradients the fused forward launch wrote are already final and backward launches
+    nothing.  Never write to the returned tensor."""
+    dev = torch.device(device)
+    if dev.type == 'cpu':
+        idx = -1
+    elif dev.type == 'cuda':
+        idx = dev.index if dev.index is not None else get_device()
+        dev = torch.device('cuda', idx)
+    else:
+        raise RuntimeError(f'unit_grad: no implementation for device type {dev.type!r}')
+    u = _UNIT_GRAD.get(idx)
+    if u is None:
+        t = torch.ones((), dtype=torch.float32, device=dev)
+        u = _UNIT_GRAD[idx] = (t, t.data_ptr())
+        _lib.register_unit_grad(idx, u[1])     # the C++ node keeps an address table of its own
+    return u[0]
+
+
+def has_unit_grad(t):
+    """Whether the constant of t's device exists yet."""
+    return (t.device.index if t.is_cuda else -1) in _UNIT_GRAD
+
+
+def is_unit_grad(g):
+    """Whether g IS `unit_grad` of its device — by address: no read of the tensor."""
+    u = _UNIT_GRAD.get(g.device.index if g.is_cuda else -1)
+    return u is not None and g.data_ptr() == u[1] and g.dim() == 0 and g.dtype == torch.float32
+
+
+def guard_double_backward(impl):
+    """The backward functions of the package's autograd nodes return gradients that ctypes kernels wrote: no autograd graph hangs
+    off them.  Under `create_graph=True` (the only case in which grad mode is ON inside a backward) the results are put behind
+    torch's DelayedError node, so differentiating them again RAISES instead of silently treating them as constants.  That is what
+    torch.autograd.function.once_differentiable does — except that it only does so when an incoming GRADIENT requires grad,
+    which the ones tensor of a plain `autograd.grad(loss, x, create_graph=True)` does not; the gradients here depend on the
+    saved INPUTS, so the guard is unconditional (as in the C++ twin).  A plain backward pays one flag test."""
+    def backward(ctx, *grads):
+        if not torch.is_grad_enabled():
+            return impl(ctx, *grads)
+        with torch.no_grad():
+            outputs = impl(ctx, *grads)
+        single = not isinstance(outputs, tuple)
+        if single:
+            outputs = (outputs,)
+        err = torch._C._functions.DelayedError(
+            b'trying to differentiate twice a function that was marked with @once_differentiable', len(outputs))
+        alias = []
+        for v in outputs:
+            if v is not None:
+                v = v.detach()
+                v.requires_grad = True
+            alias.append(v)
+        res = err(*alias)
+        return res[0] if single else res
+    return backward
 
 
 # ---- the count mailbox ----------------------------------------------------------------------------------------------------------

@@ -26,6 +26,31 @@ class Prologue(ctypes.Structure):
                 ('pc_range', ctypes.c_float * 2), ('reserved', ctypes.c_float)]
 
 
+def fill_geometry(struct, coder):
+    """The grid geometry of a CenterPoint bbox coder (norm_bbox, out_size_factor, voxel_size, pc_range) into the four fields of
+    that name, which gd3d_prologue and center_infer_desc share."""
+    struct.norm_bbox = int(bool(coder.norm_bbox))
+    struct.out_size_factor = float(coder.out_size_factor)
+    struct.voxel_size = (ctypes.c_float * 2)(float(coder.voxel_size[0]), float(coder.voxel_size[1]))
+    struct.pc_range = (ctypes.c_float * 2)(float(coder.pc_range[0]), float(coder.pc_range[1]))
+
+
+def prologue(kind, aux=None, coder=None):
+    """gd3d_prologue of `kind` (1: anchor-delta decode, aux = the anchors; 2: CenterPoint yaw decode, aux = the cells or None)
+    with `coder`'s geometry (None: the neutral one).  The struct only holds aux's raw address: the tensor rides along."""
+    p = Prologue()
+    p.kind = kind
+    if coder is None:
+        p.out_size_factor = 1.0
+        p.voxel_size = (ctypes.c_float * 2)(1.0, 1.0)
+    else:
+        fill_geometry(p, coder)
+    if aux is not None:
+        p.aux = aux.data_ptr()
+        p._keepalive = aux
+    return p
+
+
 class SmoothL1(ctypes.Structure):
     """gd3d_smooth_l1 (include/gd3d.h)."""
     _fields_ = [('beta', ctypes.c_float), ('scale', ctypes.c_float), ('diff_rad_by_sin', ctypes.c_int32),
@@ -376,12 +401,14 @@ HOST_GLUE_MODES = ('python', 'cpp')
 _node = None
 _glue = None        # the resolved mode of `_node`
 _forced = None      # set_host_glue()
-_unit_grads = {}    # device index (-1: CPU) -> address of gd_loss.unit_grad's constant; pushed into whichever glue is loaded
+_unit_grads = {}    # device index (-1: CPU) -> address of _host.unit_grad's constant, for the C++ node's own table
 
 
 def register_unit_grad(device_index, address):
+    """Called by `_host.unit_grad` alone.  The Python layer asks `_host.is_unit_grad`; this feeds the C++ node, now or when it
+    is loaded."""
     _unit_grads[int(device_index)] = int(address)
-    if _node is not None:
+    if _glue == 'cpp':
         _node.set_unit_grad(int(device_index), int(address))
 
 
@@ -438,8 +465,8 @@ def _requested_glue():
 
 def load_node():
     """The host-glue module GDLoss (reduced forms), nms_gpu (scored path), the anchor-head slice and scatter_reduce call:
-    `reduced`, `nms_scored`, `anchor_head`, `scatter_reduce`, `set_unit_grad`, `finish_calls`, `bind` — from _pynode.py or from
-    _gd3d_node.so (see the table above)."""
+    `reduced`, `nms_scored`, `anchor_head`, `scatter_reduce`, `finish_calls`, `bind` — from _pynode.py or from _gd3d_node.so (see
+    the table above), which also takes the unit gradient's address (`set_unit_grad`)."""
     global _node, _glue
     if _node is not None:
         return _node
@@ -464,8 +491,9 @@ def load_node():
                 'Set GD3D_HOST=python to silence this, GD3D_HOST=cpp to make it an error.', str(e).splitlines()[0][:300])
             from . import _pynode
             _node, _glue = _pynode, 'python'
-    for idx, address in _unit_grads.items():
-        _node.set_unit_grad(idx, address)
+    if _glue == 'cpp':
+        for idx, address in _unit_grads.items():
+            _node.set_unit_grad(idx, address)
     return _node
 
 

@@ -11,11 +11,12 @@ profiles/r04_node_ab.txt); `_lib.load_node()` picks one of the two (`GD3D_HOST=p
 Surface (argument for argument that of csrc/torch_node.cpp):
   reduced(...)        GDLoss's reduced forms ('mean' / 'sum'): one fused launch writes the loss sum AND the final gradients; they
                       wait in the node; backward hands them over (scaled on the device unless the upstream gradient is
-                      gd_loss.unit_grad, known by address); a retain_graph replay recomputes; double backward raises.
+                      gd_loss.unit_grad, known by address: _host.is_unit_grad); a retain_graph replay recomputes; double backward raises.
   anchor_head(...)    the anchor-head regression slice (head_loss.py, gd_anchor3d_head.py:95-161) as one node.
   scatter_reduce(...) dynamic scatter-reduce (scatter.py, ops/voxel/scatter.py:29-72) as one node.
   nms_scored(...)     nms_gpu's scored path: allocate, launch, read the count back, cut.
-  set_unit_grad / finish_calls / bind: bookkeeping the C++ module also exports.
+  finish_calls / bind: bookkeeping the C++ module also exports (its set_unit_grad has no twin here: the Python layer keeps ONE
+                      table of the constant, in _host).
 """
 import ctypes
 
@@ -28,36 +29,9 @@ IMPLEMENTATION = 'python'
 _on_device = _host.on_device
 _ptr = _host.ptr
 
+guard_double_backward = _host.guard_double_backward
+
 _FINISH_CALLS = 0          # gd3d_grad_finish launches made by backward so far (tests: unit_grad must make none)
-_UNIT_GRAD = {}            # device index (-1: the CPU) -> address of the library's constant 1.0
-
-
-def guard_double_backward(impl):
-    """The backward functions here return gradients that ctypes kernels wrote: no autograd graph hangs off them.  Under
-    `create_graph=True` (the only case in which grad mode is ON inside a backward) the results are put behind torch's
-    DelayedError node, so differentiating them again RAISES instead of silently treating them as constants.  That is what
-    torch.autograd.function.once_differentiable does — except that it only does so when an incoming GRADIENT requires grad,
-    which the ones tensor of a plain `autograd.grad(loss, x, create_graph=True)` does not; the gradients here depend on the
-    saved INPUTS, so the guard is unconditional (as in the C++ twin).  A plain backward pays one flag test."""
-    def backward(ctx, *grads):
-        if not torch.is_grad_enabled():
-            return impl(ctx, *grads)
-        with torch.no_grad():
-            outputs = impl(ctx, *grads)
-        single = not isinstance(outputs, tuple)
-        if single:
-            outputs = (outputs,)
-        err = torch._C._functions.DelayedError(
-            b'trying to differentiate twice a function that was marked with @once_differentiable', len(outputs))
-        alias = []
-        for v in outputs:
-            if v is not None:
-                v = v.detach()
-                v.requires_grad = True
-            alias.append(v)
-        res = err(*alias)
-        return res[0] if single else res
-    return backward
 
 
 def bind(path):
@@ -69,17 +43,8 @@ def bind(path):
     return int(_lib.load().gd3d_abi_version(None))
 
 
-def set_unit_grad(device_index, address):
-    _UNIT_GRAD[-1 if device_index < 0 else int(device_index)] = int(address)
-
-
 def finish_calls():
     return _FINISH_CALLS
-
-
-def _is_unit_grad(g):
-    a = _UNIT_GRAD.get(g.device.index if g.is_cuda else -1)
-    return a is not None and g.dim() == 0 and g.dtype == torch.float32 and g.data_ptr() == a
 
 
 def _copy_struct(cls, addr):
@@ -129,7 +94,7 @@ class GDLossReduced(torch.autograd.Function):
             gp, gt = ctx.gp, ctx.gt
             ctx.gp = ctx.gt = None
             ctx.used = True
-        if select or not _is_unit_grad(grad_out):
+        if select or not _host.is_unit_grad(grad_out):
             lib = _lib.load()
             g = grad_out if grad_out.dtype == torch.float32 else grad_out.float()
             if not pred.is_cuda:
@@ -272,7 +237,7 @@ class GDAnchorHead(torch.autograd.Function):
             g = _anchor_head_launch(bbox_pred, *ctx.args, True)[1]
         else:
             g, ctx.grad, ctx.used = ctx.grad, None, True
-        if not _is_unit_grad(grad_out):
+        if not _host.is_unit_grad(grad_out):
             go = grad_out if grad_out.dtype == torch.float32 else grad_out.float()
             with _on_device(g.device) as stream:
                 rc = _lib.load().gd3d_scale_rows(g.data_ptr(), go.data_ptr(), 0, g.numel() // 7, stream)

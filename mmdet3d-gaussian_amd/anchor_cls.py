@@ -7,12 +7,8 @@ CrossEntropyLoss) — both loss modules third party, absent here, restated from 
 """
 import torch
 
-from . import _lib
-from .gd_loss import _is_unit_grad, guard_double_backward
-
-
-def _get(cfg, key, default):
-    return cfg.get(key, default) if isinstance(cfg, dict) else getattr(cfg, key, default)
+from . import _host, _lib
+from ._host import cfg_get as _get, f32c, i64c, ptr
 
 
 def _focal_cfg(loss_cls):
@@ -35,50 +31,37 @@ def _ce_cfg(loss_dir):
     return float(_get(loss_dir, 'loss_weight', 1.0))
 
 
-def _f32c(x):
-    return x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()
-
-
-def _i64c(x):
-    return x if (x.dtype == torch.int64 and x.is_contiguous()) else x.long().contiguous()
-
-
 class _ClsDir(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, targets, cls_score, dir_cls_preds):
-        lib = _lib.load_extras()
         gamma, alpha, cls_scale, dir_scale, C, avg_dev = cfg
         labels, label_weights, dir_targets, dir_weights = targets
         B, AC, H, W = cls_score.shape
         A = AC // C
-        xc = _f32c(cls_score)
-        xd = None if dir_cls_preds is None else _f32c(dir_cls_preds)
+        xc = f32c(cls_score)
+        xd = None if dir_cls_preds is None else f32c(dir_cls_preds)
         dev = xc.device
-        with torch.cuda.device(dev):
-            gc = torch.empty_like(xc) if ctx.needs_input_grad[2] else None
-            gd = torch.empty_like(xd) if (xd is not None and ctx.needs_input_grad[3]) else None
-            out = torch.empty(2, dtype=torch.float32, device=dev)
-            ws = torch.empty(lib.gd3d_anchor_cls_dir_workspace_bytes(B, H, W), dtype=torch.uint8, device=dev)
-            ptr = lambda t: None if t is None else t.data_ptr()
-            if avg_dev is not None:       # cls_scale / dir_scale are the loss weights; the kernels divide by *avg_dev
-                rc = lib.gd3d_anchor_cls_dir_loss_dyn(xc.data_ptr(), ptr(xd), labels.data_ptr(), label_weights.data_ptr(), ptr(dir_targets),
-                                                      ptr(dir_weights), B, A, C, H, W, gamma, alpha, cls_scale, dir_scale, avg_dev.data_ptr(),
-                                                      ptr(gc), ptr(gd), out.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-            else:
-                rc = lib.gd3d_anchor_cls_dir_loss(xc.data_ptr(), ptr(xd), labels.data_ptr(), label_weights.data_ptr(), ptr(dir_targets),
-                                                  ptr(dir_weights), B, A, C, H, W, gamma, alpha, cls_scale, dir_scale, ptr(gc), ptr(gd),
-                                                  out.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, 'gd3d_anchor_cls_dir_loss')
+        gc = torch.empty_like(xc) if ctx.needs_input_grad[2] else None
+        gd = torch.empty_like(xd) if (xd is not None and ctx.needs_input_grad[3]) else None
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.load_extras().gd3d_anchor_cls_dir_workspace_bytes(B, H, W), dtype=torch.uint8, device=dev)
+        head = (xc.data_ptr(), ptr(xd), labels.data_ptr(), label_weights.data_ptr(), ptr(dir_targets), ptr(dir_weights), B, A, C, H, W,
+                gamma, alpha, cls_scale, dir_scale)
+        tail = (ptr(gc), ptr(gd), out.data_ptr(), ws.data_ptr())
+        if avg_dev is not None:       # cls_scale / dir_scale are the loss weights; the kernels divide by *avg_dev
+            _host.call_extras('gd3d_anchor_cls_dir_loss_dyn', dev, head + (avg_dev.data_ptr(),) + tail)
+        else:
+            _host.call_extras('gd3d_anchor_cls_dir_loss', dev, head + tail)
         ctx.state = (gc, gd, cls_score.dtype, None if dir_cls_preds is None else dir_cls_preds.dtype)
         return out[0], out[1]          # two outputs of the node (no select nodes in the caller's graph)
 
     @staticmethod
-    @guard_double_backward
+    @_host.guard_double_backward
     def backward(ctx, grad_cls, grad_dir):
         gc, gd, dtc, dtd = ctx.state
         # the library's own constant 1.0 (gd_loss.unit_grad) is known by address: the stored maps are final, nothing is launched
-        rc = None if gc is None else (gc if _is_unit_grad(grad_cls) else gc * grad_cls).to(dtc)
-        rd = None if gd is None else (gd if _is_unit_grad(grad_dir) else gd * grad_dir).to(dtd)
+        rc = None if gc is None else (gc if _host.is_unit_grad(grad_cls) else gc * grad_cls).to(dtc)
+        rd = None if gd is None else (gd if _host.is_unit_grad(grad_dir) else gd * grad_dir).to(dtd)
         return None, None, rc, rd
 
 
@@ -94,8 +77,7 @@ def anchor_head_cls_dir_loss(loss_cls, loss_dir, cls_score, dir_cls_preds, label
                           reference's fallback `int(cls_score.shape[0])` at :85-86, taken before its permute).
     Returns (loss_cls, loss_dir) 0-dim tensors on the device, differentiable wrt the maps; loss_dir is 0 (still attached to the
     graph) when there is no positive anchor, as `pos_dir_cls_preds.sum()` at :157-158; None without direction classifier."""
-    if not cls_score.is_cuda:
-        raise RuntimeError('anchor_head_cls_dir_loss: the MI355X implementation has no CPU path')
+    _host.gpu_only(cls_score, 'anchor_head_cls_dir_loss')
     if cls_score.dim() != 4 or cls_score.shape[1] % num_classes:
         raise RuntimeError(f'anchor_head_cls_dir_loss: cls_score {tuple(cls_score.shape)} is not (B, A*{num_classes}, H, W)')
     B, AC, H, W = cls_score.shape
@@ -118,14 +100,13 @@ def anchor_head_cls_dir_loss(loss_cls, loss_dir, cls_score, dir_cls_preds, label
         num_total_samples = B
     avg_dev = None
     if isinstance(num_total_samples, torch.Tensor):       # a 0-dim fp32 device tensor: the kernels divide by it (no read-back)
-        from .head_loss import _avg_tensor
-        avg_dev = _avg_tensor(num_total_samples, cls_score.device, 'anchor_head_cls_dir_loss')
+        avg_dev = _host.avg_tensor(num_total_samples, cls_score.device, 'anchor_head_cls_dir_loss')
         avg = 1.0
     else:
         avg = float(num_total_samples)
         if not avg > 0:
             raise RuntimeError(f'anchor_head_cls_dir_loss: num_total_samples = {num_total_samples}')
-    targets = (_i64c(labels.detach()), _f32c(label_weights.detach()),
-               None if dir_cls_preds is None else _i64c(dir_targets.detach()), None if dir_cls_preds is None else _f32c(dir_weights.detach()))
+    targets = (i64c(labels.detach()), f32c(label_weights.detach()),
+               None if dir_cls_preds is None else i64c(dir_targets.detach()), None if dir_cls_preds is None else f32c(dir_weights.detach()))
     l_cls, l_dir = _ClsDir.apply((gamma, alpha, wc / avg, wd / avg, int(num_classes), avg_dev), targets, cls_score, dir_cls_preds)
     return l_cls, (l_dir if dir_cls_preds is not None else None)

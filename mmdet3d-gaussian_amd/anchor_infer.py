@@ -11,13 +11,8 @@ import ctypes
 
 import torch
 
-from . import _lib
-
-
-def _f32c(t):
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t if t.is_contiguous() else t.contiguous()
+from . import _host, _lib
+from ._host import f32c
 
 
 def anchor_head_get_bboxes(cls_scores, bbox_preds, dir_cls_preds, mlvl_anchors, cfg, num_classes, dir_offset=0.0, dir_limit_offset=1.0,
@@ -35,8 +30,7 @@ def anchor_head_get_bboxes(cls_scores, bbox_preds, dir_cls_preds, mlvl_anchors, 
     L = len(cls_scores)
     if not (len(bbox_preds) == len(dir_cls_preds) == len(mlvl_anchors) == L) or L == 0 or L > 4:
         raise RuntimeError('anchor_head_get_bboxes: 1..4 levels, one entry per level in every list')
-    if not cls_scores[0].is_cuda:
-        raise RuntimeError('anchor_head_get_bboxes: the MI355X implementation has no CPU path')
+    _host.gpu_only(cls_scores[0], 'anchor_head_get_bboxes')
     lib = _lib.load_extras()
     dev = cls_scores[0].device
     C = int(num_classes)
@@ -47,16 +41,16 @@ def anchor_head_get_bboxes(cls_scores, bbox_preds, dir_cls_preds, mlvl_anchors, 
     levels = (_lib.AnchorInferLevel * L)()
     keep = []
     for l in range(L):
-        cs, bp, dp = _f32c(cls_scores[l]), _f32c(bbox_preds[l]), _f32c(dir_cls_preds[l])
+        cs, bp, dp = f32c(cls_scores[l]), f32c(bbox_preds[l]), f32c(dir_cls_preds[l])
         H, W = cs.shape[2], cs.shape[3]
-        an = _f32c(mlvl_anchors[l].to(dev).reshape(-1, 7))
+        an = f32c(mlvl_anchors[l].to(dev).reshape(-1, 7))
         if tuple(cs.shape) != (B, A * C, H, W) or tuple(bp.shape) != (B, A * 7, H, W) or tuple(dp.shape) != (B, A * 2, H, W) or an.shape[0] != H * W * A:
             raise RuntimeError(f'level {l}: cls {tuple(cs.shape)}, bbox {tuple(bp.shape)}, dir {tuple(dp.shape)}, anchors {tuple(an.shape)} '
                                f'do not describe B={B}, A={A}, C={C}, H={H}, W={W}')
         keep += [cs, bp, dp, an]
         levels[l].cls_score, levels[l].bbox_pred, levels[l].dir_cls_pred, levels[l].anchors = cs.data_ptr(), bp.data_ptr(), dp.data_ptr(), an.data_ptr()
         levels[l].height, levels[l].width = H, W
-    get = (lambda k, d=None: cfg.get(k, d)) if hasattr(cfg, 'get') else (lambda k, d=None: getattr(cfg, k, d))
+    get = lambda k, d=None: _host.cfg_get(cfg, k, d)
     d = _lib.AnchorInferDesc()
     d.num_levels, d.batch, d.num_anchors, d.num_classes = L, B, A, C
     d.nms_pre = int(get('nms_pre', -1))
@@ -71,14 +65,13 @@ def anchor_head_get_bboxes(cls_scores, bbox_preds, dir_cls_preds, mlvl_anchors, 
         raise RuntimeError('anchor_head_get_bboxes: unsupported configuration (nms_pre above 4096 per level, more than 16384 candidates '
                            'in total, more than 16 classes, or max_num < 1)')
     M = d.max_num
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.anchor_infer_workspace_bytes(ctypes.byref(d)), dtype=torch.uint8, device=dev)
-        boxes = torch.empty((B, M, 7), dtype=torch.float32, device=dev)
-        scores = torch.empty((B, M), dtype=torch.float32, device=dev)
-        labels = torch.empty((B, M), dtype=torch.int64, device=dev)
-        count = torch.empty(B, dtype=torch.int64, device=dev)
-        _lib.check(lib.anchor_infer_bboxes(ctypes.byref(d), ws.data_ptr(), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
-                                           count.data_ptr(), torch.cuda.current_stream().cuda_stream), 'anchor_infer_bboxes')
+    ws = torch.empty(lib.anchor_infer_workspace_bytes(ctypes.byref(d)), dtype=torch.uint8, device=dev)
+    boxes = torch.empty((B, M, 7), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, M), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, M), dtype=torch.int64, device=dev)
+    count = torch.empty(B, dtype=torch.int64, device=dev)
+    _host.call_extras('anchor_infer_bboxes', dev, (ctypes.byref(d), ws.data_ptr(), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
+                                                   count.data_ptr()))
     cands = None
     if return_candidates:
         cands = dict(boxes=ws[offs[0]:offs[0] + 4 * B * K * 7].view(torch.float32).view(B, K, 7),

@@ -10,13 +10,12 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _host, _lib
+from ._host import ptr
 
 
 def _get(cfg, key, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(key, default)
-    return getattr(cfg, key, default)
+    return _host.cfg_get(cfg, key, default)
 
 
 def _assigner(cfg):
@@ -67,8 +66,7 @@ def anchor_head_get_targets(anchors, gt_bboxes, gt_labels, assigner, num_classes
         anchors = anchors.reshape(-1, 1, 1, 1, 7)
     if anchors.dim() != 5 or anchors.shape[-1] != 7:
         raise RuntimeError(f'anchor_head_get_targets: anchors {tuple(anchors.shape)} are not (H, W, sizes, rotations, 7)')
-    if not anchors.is_cuda:
-        raise RuntimeError('anchor_head_get_targets: the MI355X implementation has no CPU path')
+    _host.gpu_only(anchors, 'anchor_head_get_targets')
     H, W, S, R, _ = anchors.shape
     cfgs = [_assigner(assigner)] if single else [_assigner(c) for c in assigner]
     if not single and len(cfgs) != S:
@@ -101,27 +99,23 @@ def anchor_head_get_targets(anchors, gt_bboxes, gt_labels, assigner, num_classes
         d.pos_iou_thr[q], d.neg_iou_thr[q], d.min_pos_iou[q] = c[0], c[1], c[2]
     d.pos_weight, d.dir_offset = float(pos_weight), float(dir_offset)
     N = H * W * S * R
-    with torch.cuda.device(dev):
-        an = anchors.detach()
-        an = an if (an.dtype == torch.float32 and an.is_contiguous()) else an.float().contiguous()
-        if off:
-            boxes = torch.cat([r.detach()[:, :7].to(dev) for r in rows], dim=0).float().contiguous()
-            labs = torch.cat([l.reshape(-1).to(dev) for l in gt_labels], dim=0).to(torch.int64).contiguous()
-        else:
-            boxes, labs = None, None
-        labels = torch.empty((B, N), dtype=torch.int64, device=dev)
-        label_weights = torch.empty((B, N), dtype=torch.float32, device=dev)
-        bbox_targets = torch.empty((B, N, 7), dtype=torch.float32, device=dev)
-        bbox_weights = torch.empty((B, N, 7), dtype=torch.float32, device=dev)
-        dir_targets = torch.empty((B, N), dtype=torch.int64, device=dev)
-        dir_weights = torch.empty((B, N), dtype=torch.float32, device=dev)
-        counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        ws = torch.empty(lib.anchor_targets_workspace_bytes(len(cfgs), off), dtype=torch.uint8, device=dev)
-        _lib.check(lib.anchor_targets_build(ctypes.byref(d), an.data_ptr(), None if boxes is None else boxes.data_ptr(),
-                                            None if labs is None else labs.data_ptr(), ws.data_ptr(), labels.data_ptr(),
-                                            label_weights.data_ptr(), bbox_targets.data_ptr(), bbox_weights.data_ptr(), dir_targets.data_ptr(),
-                                            dir_weights.data_ptr(), counts.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                   'anchor_targets_build')
+    an = _host.f32c(anchors.detach())
+    if off:
+        boxes = torch.cat([r.detach()[:, :7].to(dev) for r in rows], dim=0).float().contiguous()
+        labs = torch.cat([l.reshape(-1).to(dev) for l in gt_labels], dim=0).to(torch.int64).contiguous()
+    else:
+        boxes, labs = None, None
+    labels = torch.empty((B, N), dtype=torch.int64, device=dev)
+    label_weights = torch.empty((B, N), dtype=torch.float32, device=dev)
+    bbox_targets = torch.empty((B, N, 7), dtype=torch.float32, device=dev)
+    bbox_weights = torch.empty((B, N, 7), dtype=torch.float32, device=dev)
+    dir_targets = torch.empty((B, N), dtype=torch.int64, device=dev)
+    dir_weights = torch.empty((B, N), dtype=torch.float32, device=dev)
+    counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.anchor_targets_workspace_bytes(len(cfgs), off), dtype=torch.uint8, device=dev)
+    _host.call_extras('anchor_targets_build', dev, (
+        ctypes.byref(d), an.data_ptr(), ptr(boxes), ptr(labs), ws.data_ptr(), labels.data_ptr(), label_weights.data_ptr(),
+        bbox_targets.data_ptr(), bbox_weights.data_ptr(), dir_targets.data_ptr(), dir_weights.data_ptr(), counts.data_ptr()))
     if padded:
         return labels, label_weights, bbox_targets, bbox_weights, dir_targets, dir_weights, counts
     c = counts.tolist()          # the one sync

@@ -13,7 +13,8 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _host, _lib
+from ._host import f32c
 
 _REV_ORDER = ('reg', 'height', 'dim', 'rot', 'vel')
 _YAW_ORDER = ('reg', 'height', 'dim', 'yaw', 'dir', 'vel')
@@ -26,25 +27,11 @@ def _task_dict(entry):
     return entry[0] if isinstance(entry, (list, tuple)) else entry
 
 
-def _f32c(t):
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _fill_geometry(desc, coder):
-    desc.norm_bbox = int(bool(coder.norm_bbox))
-    desc.out_size_factor = float(coder.out_size_factor)
-    desc.voxel_size = (ctypes.c_float * 2)(float(coder.voxel_size[0]), float(coder.voxel_size[1]))
-    desc.pc_range = (ctypes.c_float * 2)(float(coder.pc_range[0]), float(coder.pc_range[1]))
-
-
 def select_best(scores, preds, topk):
     """`bbox_coder.select_best(scores, preds, topk)` (centerpoint_bbox_coders.py:51-58): scores (B,C,H,W) — already passed
     through the sigmoid —, preds (B,N,H,W) -> scores (B,K), classes (B,K) int64, locs (B,K,2) int64 (x, y), preds (B,K,N):
     the K best cells over all classes by descending score (equal scores: ascending class, y, x), one launch."""
-    if not scores.is_cuda:
-        raise RuntimeError('select_best: the MI355X implementation has no CPU path')
+    _host.gpu_only(scores, 'select_best')
     lib = _lib.load_extras()
     B, C, H, W = scores.shape
     N = preds.shape[1]
@@ -55,7 +42,7 @@ def select_best(scores, preds, topk):
     K = int(topk)
     if K > H * W:
         raise RuntimeError('selected index k out of range')     # what torch.topk raises in the reference
-    sc, pr = _f32c(scores), _f32c(preds)
+    sc, pr = f32c(scores), f32c(preds)
     dev = sc.device
     task = _lib.CenterInferTask()
     task.heatmap = sc.data_ptr()
@@ -71,10 +58,9 @@ def select_best(scores, preds, topk):
     out_c = torch.empty((B, K), dtype=torch.int64, device=dev)
     out_xy = torch.empty((B, K, 2), dtype=torch.int64, device=dev)
     out_p = torch.empty((B, K, N), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.center_infer_select_workspace_bytes(ctypes.byref(desc)), dtype=torch.uint8, device=dev)
-        _lib.check(lib.center_infer_select(ctypes.byref(desc), ws.data_ptr(), out_s.data_ptr(), out_c.data_ptr(), out_xy.data_ptr(),
-                                           out_p.data_ptr(), torch.cuda.current_stream().cuda_stream), 'center_infer_select')
+    ws = torch.empty(lib.center_infer_select_workspace_bytes(ctypes.byref(desc)), dtype=torch.uint8, device=dev)
+    _host.call_extras('center_infer_select', dev, (ctypes.byref(desc), ws.data_ptr(), out_s.data_ptr(), out_c.data_ptr(), out_xy.data_ptr(),
+                                                   out_p.data_ptr()))
     if scores.dtype != torch.float32:
         out_s = out_s.to(scores.dtype)
     if preds.dtype != torch.float32:
@@ -116,8 +102,7 @@ def center_head_get_bboxes(preds_dicts, bbox_coder, test_cfg, num_classes, img_m
         return []
     first = tasks[0]
     heat0 = first['heatmap']
-    if not heat0.is_cuda:
-        raise RuntimeError('center_head_get_bboxes: the MI355X implementation has no CPU path')
+    _host.gpu_only(heat0, 'center_head_get_bboxes')
     if len(num_classes) != len(tasks):
         raise RuntimeError(f'{len(tasks)} tasks but {len(num_classes)} class counts')
     lib = _lib.load_extras()
@@ -138,7 +123,7 @@ def center_head_get_bboxes(preds_dicts, bbox_coder, test_cfg, num_classes, img_m
     # (the caching allocator hands them back step after step) pays for it once.
     keep_alive, ptrs, ncls = [], [], []
     for t, pd in enumerate(tasks):
-        heat = _f32c(pd['heatmap'])
+        heat = f32c(pd['heatmap'])
         if heat.dim() != 4 or heat.shape[0] != B or tuple(heat.shape[2:]) != (H, W):
             raise RuntimeError(f'task {t}: heatmap {tuple(heat.shape)} vs (B={B}, C, {H}, {W})')
         keep_alive.append(heat)
@@ -151,7 +136,7 @@ def center_head_get_bboxes(preds_dicts, bbox_coder, test_cfg, num_classes, img_m
                     raise RuntimeError(f'task {t}: head map {k!r} is missing')
                 ptrs.append(0)               # no 'reg' head: the constant 0.5 (:206-208)
                 continue
-            m = _f32c(m)
+            m = f32c(m)
             if tuple(m.shape) != (B, _WIDTH[k], H, W):
                 raise RuntimeError(f'task {t}: {k} is {tuple(m.shape)}, expected {(B, _WIDTH[k], H, W)}')
             keep_alive.append(m)
@@ -191,7 +176,7 @@ def center_head_get_bboxes(preds_dicts, bbox_coder, test_cfg, num_classes, img_m
         desc.max_per_img, desc.num_channels = K, nchan
         desc.decode = 2 if kind == 'yaw' else 1
         desc.heat_is_logit = 1
-        _fill_geometry(desc, bbox_coder)
+        _lib.fill_geometry(desc, bbox_coder)
         desc.use_score_threshold = 1
         desc.score_threshold = float(test_cfg.get('score_threshold', 0.1))
         desc.use_limit_range = int(rng is not None)
@@ -209,15 +194,13 @@ def center_head_get_bboxes(preds_dicts, bbox_coder, test_cfg, num_classes, img_m
     desc, _, rows, ws_bytes = hit
     co = nchan - (2 if kind == 'yaw' else 1)
     T = len(tasks)
-    with torch.cuda.device(dev):
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        boxes = torch.empty((B, T * rows, co), dtype=torch.float32, device=dev)
-        scores = torch.empty((B, T * rows), dtype=torch.float32, device=dev)
-        labels = torch.empty((B, T * rows), dtype=torch.int32, device=dev)
-        count = torch.empty(B, dtype=torch.int64, device=dev)
-        _lib.check(lib.center_infer_bboxes(ctypes.byref(desc), ws.data_ptr(), boxes.data_ptr(), scores.data_ptr(),
-                                           labels.data_ptr(), count.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                   'center_infer_bboxes')
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    boxes = torch.empty((B, T * rows, co), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, T * rows), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, T * rows), dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int64, device=dev)
+    _host.call_extras('center_infer_bboxes', dev, (ctypes.byref(desc), ws.data_ptr(), boxes.data_ptr(), scores.data_ptr(),
+                                                   labels.data_ptr(), count.data_ptr()))
     if padded:
         return dict(bboxes=boxes, scores=scores, labels=labels, counts=count)
     ns = count.tolist()          # the one sync: B data-dependent detection counts

@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _host, _lib
 
 
 def center_head_get_targets(gt_bboxes_3d, gt_labels_3d, class_names, train_cfg, padded=False):
@@ -35,8 +35,7 @@ def center_head_get_targets(gt_bboxes_3d, gt_labels_3d, class_names, train_cfg, 
     if any(objs) != all(objs):
         raise RuntimeError('center_head_get_targets: box objects and plain tensors mixed in one batch')
     rows = [b.tensor if o else b for b, o in zip(gt_bboxes_3d, objs)]
-    if not rows[0].is_cuda:
-        raise RuntimeError('center_head_get_targets: the MI355X implementation has no CPU path')
+    _host.gpu_only(rows[0], 'center_head_get_targets')
     lib = _lib.load_extras()
     dev = rows[0].device
     cols = rows[0].shape[1]
@@ -68,18 +67,16 @@ def center_head_get_targets(gt_bboxes_3d, gt_labels_3d, class_names, train_cfg, 
     d.voxel_size = (ctypes.c_float * 2)(float(vs[0]), float(vs[1]))
     d.out_size_factor = float(osf)
     d.gaussian_overlap = float(train_cfg['gaussian_overlap'])
-    with torch.cuda.device(dev):
-        boxes = torch.cat([r.detach() for r in rows], dim=0).float().contiguous() if total else torch.zeros((0, cols), device=dev)
-        labels = torch.cat([l.reshape(-1) for l in gt_labels_3d], dim=0).to(torch.int64).contiguous() if total else \
-            torch.zeros(0, dtype=torch.int64, device=dev)
-        heat = torch.zeros(B * sum(counts) * H * W, dtype=torch.float32, device=dev)       # ONE fill for every task's maps
-        anno = torch.empty((total, cols), dtype=torch.float32, device=dev)
-        pos = torch.empty((total, 3), dtype=torch.int64, device=dev)
-        start = torch.empty(T + 1, dtype=torch.int64, device=dev)
-        ws = torch.empty(lib.center_targets_workspace_bytes(total), dtype=torch.uint8, device=dev)
-        _lib.check(lib.center_targets_build(ctypes.byref(d), boxes.data_ptr(), labels.data_ptr(), ws.data_ptr(), heat.data_ptr(),
-                                            anno.data_ptr(), pos.data_ptr(), start.data_ptr(),
-                                            torch.cuda.current_stream().cuda_stream), 'center_targets_build')
+    boxes = torch.cat([r.detach() for r in rows], dim=0).float().contiguous() if total else torch.zeros((0, cols), device=dev)
+    labels = torch.cat([l.reshape(-1) for l in gt_labels_3d], dim=0).to(torch.int64).contiguous() if total else \
+        torch.zeros(0, dtype=torch.int64, device=dev)
+    heat = torch.zeros(B * sum(counts) * H * W, dtype=torch.float32, device=dev)       # ONE fill for every task's maps
+    anno = torch.empty((total, cols), dtype=torch.float32, device=dev)
+    pos = torch.empty((total, 3), dtype=torch.int64, device=dev)
+    start = torch.empty(T + 1, dtype=torch.int64, device=dev)
+    ws = torch.empty(lib.center_targets_workspace_bytes(total), dtype=torch.uint8, device=dev)
+    _host.call_extras('center_targets_build', dev, (ctypes.byref(d), boxes.data_ptr(), labels.data_ptr(), ws.data_ptr(), heat.data_ptr(),
+                                                    anno.data_ptr(), pos.data_ptr(), start.data_ptr()))
     if padded:
         heatmaps, ho = [], 0
         for c in counts:

@@ -16,36 +16,19 @@
 In TRAINING the decode that feeds GDLoss runs from neither: it is fused into the loss kernel's prologue
 (head_loss.py -> gd3d_loss_fused_decoded).  These serve inference-time decoding and target encoding.
 """
-import ctypes
-
 import torch
 
-from . import _lib
-from ._host import on_device
-
-
-def _coder_struct(c):
-    p = _lib.Prologue()
-    p.kind = 2
-    p.norm_bbox = int(bool(c.norm_bbox))
-    p.aux = None
-    p.out_size_factor = float(c.out_size_factor)
-    p.voxel_size = (ctypes.c_float * 2)(float(c.voxel_size[0]), float(c.voxel_size[1]))
-    p.pc_range = (ctypes.c_float * 2)(float(c.pc_range[0]), float(c.pc_range[1]))
-    return p
+from . import _host, _lib
+from ._host import call, ptr
 
 
 def _rows32(t, cols):
-    t = t.reshape(-1, cols)
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t if t.is_contiguous() else t.contiguous()
+    return _host.f32c(t.reshape(-1, cols))
 
 
 class _CenterDecode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, preds, locs, cs, correct_yaw):
-        lib = _lib.load()
         lead, c = preds.shape[:-1], preds.shape[-1]
         p2, l2 = _rows32(preds, c), _rows32(locs, 2)
         n = p2.shape[0]
@@ -55,10 +38,7 @@ class _CenterDecode(torch.autograd.Function):
         out = torch.empty((n, co), dtype=torch.float32, device=preds.device)
         need = ctx.needs_input_grad[0]
         parity = torch.empty(n, dtype=torch.int32, device=preds.device) if (need and correct_yaw) else None
-        with on_device(preds.device) as stream:
-            rc = lib.coder_center_decode(cs, l2.data_ptr(), p2.data_ptr(), n, c, int(bool(correct_yaw)), out.data_ptr(),
-                                         None if parity is None else parity.data_ptr(), stream)
-        _lib.check(rc, 'coder_center_decode')
+        call('coder_center_decode', preds.device, (cs, l2.data_ptr(), p2.data_ptr(), n, c, int(bool(correct_yaw)), out.data_ptr(), ptr(parity)))
         ctx.cs, ctx.meta = cs, (n, c, lead, preds.dtype)
         if need:
             ctx.save_for_backward(out, parity)
@@ -67,15 +47,11 @@ class _CenterDecode(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         out, parity = ctx.saved_tensors
         n, c, lead, dtype = ctx.meta
         go = _rows32(grad_out, out.shape[1])
         gp = torch.empty((n, c), dtype=torch.float32, device=go.device)
-        with on_device(go.device) as stream:
-            rc = lib.coder_center_decode_backward(ctx.cs, go.data_ptr(), out.data_ptr(),
-                                                  None if parity is None else parity.data_ptr(), n, c, gp.data_ptr(), stream)
-        _lib.check(rc, 'coder_center_decode_backward')
+        call('coder_center_decode_backward', go.device, (ctx.cs, go.data_ptr(), out.data_ptr(), ptr(parity), n, c, gp.data_ptr()))
         gp = gp.reshape(lead + (c,))
         return (gp if dtype == torch.float32 else gp.to(dtype)), None, None, None
 
@@ -108,15 +84,11 @@ class CenterPointBBoxCoderRev:
 
     def decode(self, locs, preds):
         """locs (..., 2) cells, preds (..., N) raw [dx, dy, z, dims x3, sin, cos, others] -> (..., N-1) metric boxes."""
-        if not preds.is_cuda:
-            raise RuntimeError('CenterPointBBoxCoderRev: the MI355X implementation has no CPU path')
-        lib = _lib.load()
+        _host.gpu_only(preds, 'CenterPointBBoxCoderRev')
         lead, c = preds.shape[:-1], preds.shape[-1]
         p2, l2 = _rows32(preds.detach(), c), _rows32(locs.to(preds.device), 2)
         out = torch.empty((p2.shape[0], c - 1), dtype=torch.float32, device=p2.device)
-        with on_device(p2.device) as stream:
-            rc = lib.coder_center_decode(_coder_struct(self), l2.data_ptr(), p2.data_ptr(), p2.shape[0], c, 2, out.data_ptr(), None, stream)
-        _lib.check(rc, 'coder_center_decode')
+        call('coder_center_decode', p2.device, (_lib.prologue(2, None, self), l2.data_ptr(), p2.data_ptr(), p2.shape[0], c, 2, out.data_ptr(), None))
         out = out.reshape(lead + (c - 1,))
         return out if preds.dtype == torch.float32 else out.to(preds.dtype)
 
@@ -127,15 +99,11 @@ class CenterPointBBoxYawCoder(CenterPointBBoxCoderRev):
 
     def encode(self, target_boxes):
         """(..., 7+k) boxes [x,y,z,w,l,h,yaw, others] -> (..., 9+k): the first 7 as they are, sin yaw, cos yaw, others."""
-        if not target_boxes.is_cuda:
-            raise RuntimeError('CenterPointBBoxYawCoder: the MI355X implementation has no CPU path')
-        lib = _lib.load()
+        _host.gpu_only(target_boxes, 'CenterPointBBoxYawCoder')
         lead, c = target_boxes.shape[:-1], target_boxes.shape[-1]
         b2 = _rows32(target_boxes.detach(), c)
         out = torch.empty((b2.shape[0], c + 2), dtype=torch.float32, device=b2.device)
-        with on_device(b2.device) as stream:
-            rc = lib.coder_center_encode(b2.data_ptr(), b2.shape[0], c, out.data_ptr(), stream)
-        _lib.check(rc, 'coder_center_encode')
+        call('coder_center_encode', b2.device, (b2.data_ptr(), b2.shape[0], c, out.data_ptr()))
         out = out.reshape(lead + (c + 2,))
         return out if target_boxes.dtype == torch.float32 else out.to(target_boxes.dtype)
 
@@ -143,15 +111,13 @@ class CenterPointBBoxYawCoder(CenterPointBBoxCoderRev):
         """locs (..., 2) cell coordinates, preds (..., N) raw head outputs -> (..., N-2) metric boxes
         [x, y, z, dims, yaw, others]; with correct_yaw the yaw is snapped to the quarter turn the (sin, cos) channels
         point at and w / l are swapped on odd turns (ref :40-50)."""
-        if not preds.is_cuda:
-            raise RuntimeError('CenterPointBBoxYawCoder: the MI355X implementation has no CPU path')
-        return _CenterDecode.apply(preds, locs.to(preds.device), _coder_struct(self), bool(correct_yaw))
+        _host.gpu_only(preds, 'CenterPointBBoxYawCoder')
+        return _CenterDecode.apply(preds, locs.to(preds.device), _lib.prologue(2, None, self), bool(correct_yaw))
 
 
 class _PointDecode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, preds, priors, correct_yaw):
-        lib = _lib.load()
         lead, c = preds.shape[:-1], preds.shape[-1]
         p2, q2 = _rows32(preds, c), _rows32(priors, 3)
         n = p2.shape[0]
@@ -161,10 +127,7 @@ class _PointDecode(torch.autograd.Function):
         out = torch.empty((n, co), dtype=torch.float32, device=preds.device)
         need = ctx.needs_input_grad[0]
         parity = torch.empty(n, dtype=torch.int32, device=preds.device) if (need and correct_yaw) else None
-        with on_device(preds.device) as stream:
-            rc = lib.coder_point_decode(q2.data_ptr(), p2.data_ptr(), n, c, int(bool(correct_yaw)), out.data_ptr(),
-                                        None if parity is None else parity.data_ptr(), stream)
-        _lib.check(rc, 'coder_point_decode')
+        call('coder_point_decode', preds.device, (q2.data_ptr(), p2.data_ptr(), n, c, int(bool(correct_yaw)), out.data_ptr(), ptr(parity)))
         ctx.meta = (n, c, lead, preds.dtype)
         if need:
             ctx.save_for_backward(out, parity, q2)
@@ -173,15 +136,11 @@ class _PointDecode(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         out, parity, q2 = ctx.saved_tensors
         n, c, lead, dtype = ctx.meta
         go = _rows32(grad_out, out.shape[1])
         gp = torch.empty((n, c), dtype=torch.float32, device=go.device)
-        with on_device(go.device) as stream:
-            rc = lib.coder_point_decode_backward(q2.data_ptr(), go.data_ptr(), out.data_ptr(), None if parity is None else parity.data_ptr(),
-                                                 n, c, gp.data_ptr(), stream)
-        _lib.check(rc, 'coder_point_decode_backward')
+        call('coder_point_decode_backward', go.device, (q2.data_ptr(), go.data_ptr(), out.data_ptr(), ptr(parity), n, c, gp.data_ptr()))
         gp = gp.reshape(lead + (c,))
         return (gp if dtype == torch.float32 else gp.to(dtype)), None, None
 
@@ -199,8 +158,7 @@ class PointBBoxYawCoder:
         """priors (..., 3) [x, y, scale] of the points, preds (..., N) raw outputs [dx, dy, z, log dims, yaw, sin, cos, others]
         -> (..., N-2) boxes [dx scale + x, dy scale + y, z, exp(dims) (w, l times scale), yaw, others]; correct_yaw as in the
         CenterPoint yaw coder (:38-48).  Differentiable wrt preds (the priors are data: no gradient is produced for them)."""
-        if not preds.is_cuda:
-            raise RuntimeError('PointBBoxYawCoder: the MI355X implementation has no CPU path')
+        _host.gpu_only(preds, 'PointBBoxYawCoder')
         if priors.requires_grad:
             raise RuntimeError('PointBBoxYawCoder.decode: priors that require grad are not supported (gradient flows to preds only)')
         return _PointDecode.apply(preds, priors.to(preds.device), bool(correct_yaw))

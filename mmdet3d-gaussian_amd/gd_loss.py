@@ -20,7 +20,7 @@ from copy import deepcopy
 import torch
 from torch import nn
 from . import _host, _lib
-from ._pynode import guard_double_backward  # noqa: F401  (head_loss / heat_loss / anchor_cls import it from here)
+from ._host import guard_double_backward, unit_grad      # `unit_grad` stays this module's public name for the constant
 from .registry import LOSSES, register_with_mmdet
 
 LOSS_TYPES = {'gwd3d': 0, 'kld3d': 1, 'bd3d': 2, 'jd3d': 3, 'kld3d_symmax': 4, 'kld3d_symmin': 5, 'kfiou3d': 6}
@@ -85,10 +85,7 @@ def make_params(loss_type, fun, tau, alpha, center_offset, kwargs):
 
 _LIB = None
 _ptr = _host.ptr
-# raw-handle accessors (no Python-level device bookkeeping on the per-call path)
 _raw_stream = _host.raw_stream
-_get_device = _host.get_device
-_set_device = _host.set_device
 
 
 def _library():
@@ -110,9 +107,7 @@ def _rows(t):
     under @force_fp32, gd_anchor3d_head.py:167)."""
     if t.dim() != 2 or t.shape[1] != 7:
         t = t.reshape(-1, 7)
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t if t.is_contiguous() else t.contiguous()
+    return _host.f32c(t)
 
 
 _ONE_MAX = None
@@ -153,31 +148,6 @@ def _ticket(dev_index, stream):
 
 # gd3d_loss_workspace_bytes(n) / 4, memoised (one ctypes call less per forward)
 _ws_floats = _host.memo(lambda n: _library().gd3d_loss_workspace_bytes(n) // 4)
-
-
-_UNIT_GRAD = {}
-
-
-def unit_grad(device):
-    """The upstream gradient 1.0 as a CONSTANT of this library: one read-only 0-dim fp32 tensor per device.
-
-    `loss.backward()` makes torch fill a fresh ones tensor (one launch) and our backward then has to READ it on the device
-    to learn that nothing needs scaling (one more launch, gd3d_grad_finish's early exit).  A training step that passes this
-    tensor instead -- `torch.autograd.backward([l0, l1, l2], grad_tensors=[unit_grad(dev)] * 3)` -- is recognised by
-    ADDRESS (no read, no sync): the gradients the fused forward launch wrote are already final and backward launches
-    nothing.  Never write to the returned tensor."""
-    dev = torch.device(device)
-    if dev.type == 'cpu':
-        idx = 'cpu'
-    elif dev.type == 'cuda':
-        idx = dev.index if dev.index is not None else _get_device()
-    else:
-        raise RuntimeError(f'unit_grad: no implementation for device type {dev.type!r}')
-    t = _UNIT_GRAD.get(idx)
-    if t is None:
-        t = _UNIT_GRAD[idx] = torch.ones((), dtype=torch.float32, device=dev if idx == 'cpu' else torch.device('cuda', idx))
-        _lib.register_unit_grad(-1 if idx == 'cpu' else idx, t.data_ptr())   # the glue (either one) knows it by address
-    return t
 
 
 # `loss.backward()` without an explicit gradient makes torch FILL a ones tensor (one launch) that each GDLoss node then has to
@@ -224,7 +194,7 @@ def _as_loss_value(t):
     """The freshly produced loss scalar as a LossValue — by class assignment (the object is ours alone; torch itself does this in
     nn.parameter.UninitializedParameter.materialize): `as_subclass` would put an AliasBackward node behind every loss."""
     if _UNIT_ROOT and type(t) is torch.Tensor:
-        if (t.device.index if t.is_cuda else 'cpu') not in _UNIT_GRAD:
+        if not _host.has_unit_grad(t):
             # the constant is made HERE, eagerly, at the first reduced call on a device — never inside `.backward()`, which may run
             # under a hipGraph capture (its allocation would then belong to that graph's private pool); a first call that is
             # itself being captured returns a plain tensor (torch's own ones-fill is captured instead)
@@ -233,11 +203,6 @@ def _as_loss_value(t):
             unit_grad(t.device)
         t.__class__ = LossValue
     return t
-
-
-def _is_unit_grad(g):
-    t = _UNIT_GRAD.get(g.device.index if g.is_cuda else 'cpu')
-    return t is not None and g.data_ptr() == t.data_ptr() and g.dim() == 0 and g.dtype == torch.float32
 
 
 def _weight_ptrs(row_weight):
@@ -267,19 +232,12 @@ def per_pair_call(params, pred, target, row_weight, scale, want_loss, want_gp, w
             _lib.check(rc, 'gd3d_loss_fused_cpu')
         return loss, gp, gt
     dev = pred.device
-    prev = _get_device()
-    switch = prev != dev.index
-    if switch:
-        _set_device(dev.index)
-    try:
+    with _host.on_device(dev) as stream:
         loss = torch.empty(n, dtype=torch.float32, device=dev) if want_loss else None
         gp = torch.empty_like(pred) if want_gp else None
         gt = torch.empty_like(target) if want_gt else None
         rc = lib.gd3d_loss_fused_decoded(params, prologue, pred.data_ptr(), target.data_ptr(), w1, w7, n, scale, _ptr(loss), None,
-                                         _ptr(gp), _ptr(gt), None, _raw_stream(dev.index))
-    finally:
-        if switch:
-            _set_device(prev)
+                                         _ptr(gp), _ptr(gt), None, stream)
     if rc != 0:
         _lib.check(rc, 'gd3d_loss_fused')
     return loss, gp, gt

@@ -11,34 +11,21 @@ import ctypes
 
 import torch
 
-from . import _lib
-from ._host import on_device
-from .gd_loss import _is_unit_grad, guard_double_backward
-
-
-def _prologue(kind, aux, norm_bbox=False, out_size_factor=1.0, voxel_size=(1.0, 1.0), pc_range=(0.0, 0.0)):
-    p = _lib.Prologue()
-    p.kind = kind
-    p.norm_bbox = int(bool(norm_bbox))
-    p.aux = aux.data_ptr()
-    p.out_size_factor = float(out_size_factor)
-    p.voxel_size = (ctypes.c_float * 2)(float(voxel_size[0]), float(voxel_size[1]))
-    p.pc_range = (ctypes.c_float * 2)(float(pc_range[0]), float(pc_range[1]))
-    p._keepalive = aux  # the struct only holds a raw pointer
-    return p
+from . import _host, _lib
+from ._host import f32c, on_device
 
 
 def anchor_decoded_gd_loss(loss_module, anchors, pos_bbox_pred, pos_bbox_targets, weight=None, avg_factor=None):
     """loss_module(coder.decode(anchors, pos_bbox_pred), coder.decode(anchors, pos_bbox_targets), weight,
     avg_factor=avg_factor) with mmdet3d's DeltaXYZWLHRBBoxCoder, in one launch (gd_anchor3d_head.py:133-141)."""
-    anchors = anchors.reshape(-1, 7).to(torch.float32).contiguous()
+    anchors = f32c(anchors.reshape(-1, 7))
     n = pos_bbox_pred.reshape(-1, 7).shape[0]
     if anchors.shape[0] != n or pos_bbox_targets.reshape(-1, 7).shape[0] != n:
         raise RuntimeError(f'anchors {tuple(anchors.shape)}, pred {tuple(pos_bbox_pred.shape)} and targets '
                            f'{tuple(pos_bbox_targets.shape)} must have the same number of rows')
     if anchors.device != pos_bbox_pred.device:
         raise RuntimeError('anchors and predictions live on different devices')
-    pro = _prologue(1, anchors)
+    pro = _lib.prologue(1, anchors)
     return loss_module(pos_bbox_pred, pos_bbox_targets, weight, avg_factor=avg_factor, _prologue=pro)
 
 
@@ -83,14 +70,6 @@ def _anchor_head_fused(bbox_pred, bbox_targets, bbox_weights, anchors, pos_or_la
                                         float(w_gd), float(w_sl1))
 
 
-def _avg_tensor(t, dev, who):
-    """num_total_samples as a device-resident normaliser: one fp32 value on `dev`, detached"""
-    if t.numel() != 1 or t.device != dev:
-        raise RuntimeError(f'{who}: a tensor num_total_samples must hold one value on {dev}, got {tuple(t.shape)} on {t.device}')
-    t = t.detach().reshape(())
-    return t if t.dtype == torch.float32 else t.float()
-
-
 def _seven(w, name):
     """train_cfg['code_weight'] / ['decode_weight']: a list of 7 or a scalar (the shipped configs say `decode_weight=1`,
     which `bbox_weights.new_tensor(1)` broadcasts, gd_anchor3d_head.py:128-131).  Falsy -> None, as `if w:` does."""
@@ -121,15 +100,13 @@ def _head_operands(bbox_pred, bbox_targets, bbox_weights, labels, anchor_list, n
     for t in (bbox_targets, labels, anchor_list) + ((bbox_weights,) if need_weights else ()):
         if t.device != bbox_pred.device:
             raise RuntimeError('head-loss operands live on different devices')
-    bp = (bbox_pred if bbox_pred.dtype == torch.float32 else bbox_pred.float()).contiguous()
-    weights = bbox_weights.reshape(-1, 7).to(torch.float32).contiguous() if need_weights else None
-    return (bp, bbox_targets.reshape(-1, 7).to(torch.float32).contiguous(), weights,
-            anchor_list.reshape(-1, 7).to(torch.float32).contiguous(), labels)
+    weights = f32c(bbox_weights.reshape(-1, 7)) if need_weights else None
+    return f32c(bbox_pred), f32c(bbox_targets.reshape(-1, 7)), weights, f32c(anchor_list.reshape(-1, 7)), labels
 
 
 def _select(labels, num_classes, dense):
     if dense:
-        return labels.to(torch.int64).contiguous()
+        return _host.i64c(labels)
     return ((labels >= 0) & (labels < num_classes)).nonzero(as_tuple=False).reshape(-1).contiguous()
 
 
@@ -202,7 +179,7 @@ def anchor_head_bbox_loss(loss_decoded_bbox, loss_bbox, bbox_pred, bbox_targets,
     if dyn:
         if not dense:
             raise RuntimeError('anchor_head_bbox_loss: a device-resident num_total_samples needs the dense form')
-        avg_dev = _avg_tensor(num_total_samples, bbox_pred.device, 'anchor_head_bbox_loss')
+        avg_dev = _host.avg_tensor(num_total_samples, bbox_pred.device, 'anchor_head_bbox_loss')
     sl1 = _lib.SmoothL1()
     sl1.beta = beta
     sl1.scale = 0.0 if dyn else lw / float(num_total_samples)
@@ -221,12 +198,11 @@ def center_head_gd_loss(loss_module, coder, pos_ind, pred, anno_boxes, num_pos):
     pos_ind: (B, K, 3) long [b, x, y]; pred: (B, K, C>=7) gathered raw head outputs [reg(2), height, dim(3), yaw, ...];
     anno_boxes: (B, K, >=7).  The decode runs inside the kernel; the gradient reaches pred[..., :7]."""
     target_gd = anno_boxes[..., :7].reshape(-1, 7)        # encode() leaves the first 7 entries as they are (:11-16)
-    locs = pos_ind[..., 1:].reshape(-1, 2).to(torch.float32).contiguous()
+    locs = f32c(pos_ind[..., 1:].reshape(-1, 2))
     if locs.shape[0] != pred[..., :7].reshape(-1, 7).shape[0] or locs.shape[0] != target_gd.shape[0]:
         raise RuntimeError(f'pos_ind {tuple(pos_ind.shape)}, pred {tuple(pred.shape)} and anno_boxes '
                            f'{tuple(anno_boxes.shape)} must describe the same number of objects')
-    pro = _prologue(2, locs, norm_bbox=coder.norm_bbox, out_size_factor=coder.out_size_factor,
-                    voxel_size=coder.voxel_size, pc_range=coder.pc_range)
+    pro = _lib.prologue(2, locs, coder)
     pred7 = pred[..., :7].reshape(-1, 7)
     if pred7.numel() == 0:
         # the reference returns new_zeros((1,)) (:436-438); same value and shape here, but attached to `pred` so that the
@@ -329,19 +305,15 @@ class _CenterHeadFused(torch.autograd.Function):
         return losses
 
     @staticmethod
-    @guard_double_backward
+    @_host.guard_double_backward
     def backward(ctx, grad_losses):
-        lib = _lib.load()
         if ctx.used:  # retain_graph replay: the saved maps were scaled in place: recompute them
             _, grads, tasks = _center_head_launch(*ctx.replay)
         else:  # hand the maps over (no reference left here: a leaf's AccumulateGrad then keeps its map instead of cloning it)
             grads, tasks, ctx.used = ctx.grads, ctx.tasks, True
             ctx.grads = ctx.tasks = None
         go = grad_losses.contiguous().float()
-        dev = go.device
-        with on_device(dev) as stream:
-            rc = lib.gd3d_center_head_scale(tasks, len(tasks), go.data_ptr(), stream)
-        _lib.check(rc, 'gd3d_center_head_scale')
+        _host.call('gd3d_center_head_scale', go.device, (tasks, len(tasks), go.data_ptr()))
         return (None,) + tuple(grads)
 
 
@@ -399,7 +371,7 @@ def center_head_losses(loss_gd, loss_bbox, coder, preds_dicts, pos_inds, anno_bo
                 if tuple(m.shape) != (B, _CENTER_CH[h], H, W) or m.device != dev:
                     raise RuntimeError(f"task {t}: head '{name}' has shape {tuple(m.shape)}, expected {(B, _CENTER_CH[h], H, W)}")
                 row.append(len(maps))
-                maps.append((m if m.dtype == torch.float32 else m.float()).contiguous())
+                maps.append(f32c(m))
             elif name in ('height', 'dim', 'yaw', 'dir'):
                 raise RuntimeError(f"task {t}: head '{name}' is missing")
             else:
@@ -420,8 +392,7 @@ def center_head_losses(loss_gd, loss_bbox, coder, preds_dicts, pos_inds, anno_bo
         else:
             avg = max(float(num_pos[t]), 1.0)
             scales.append((float(loss_gd.loss_weight) / avg, lw / avg))
-    pro = _prologue(2, maps[0], norm_bbox=coder.norm_bbox, out_size_factor=coder.out_size_factor,
-                    voxel_size=coder.voxel_size, pc_range=coder.pc_range)
+    pro = _lib.prologue(2, maps[0], coder)
     losses = _CenterHeadFused.apply((loss_gd._params({}), pro, layout, pis, ans, scales, cw, n_l1, rows, num_pos if dyn else None), *maps)
     flat = losses.reshape(-1).unbind(0)          # one autograd node for all 2T scalars
     return [(flat[2 * t], flat[2 * t + 1]) for t in range(T)]

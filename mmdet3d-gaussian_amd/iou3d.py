@@ -145,22 +145,6 @@ def nms_normal_gpu(boxes, scores, thresh):
     return _nms(boxes, scores, thresh, None, None, normal=True)
 
 
-_THRESH_CACHE = {}
-
-
-def _thresh_tensor(thresh, groups, dev):
-    vals = tuple(float(t) for t in thresh) if isinstance(thresh, (list, tuple)) else (float(thresh),) * groups
-    if len(vals) != groups:
-        raise RuntimeError(f'{len(vals)} thresholds for {groups} groups')
-    key = (vals, dev)
-    t = _THRESH_CACHE.get(key)
-    if t is None:
-        if len(_THRESH_CACHE) > 64:
-            _THRESH_CACHE.clear()
-        t = _THRESH_CACHE[key] = torch.tensor(vals, dtype=torch.float32, device=dev)
-    return t
-
-
 def nms_gpu_batched(boxes, scores, thresh, valid=None, pre_max_size=None, post_max_size=None, normal=False,
                     circle=False):
     """G independent NMS problems over ONE box array in one set of launches and one host sync.
@@ -207,7 +191,7 @@ def nms_gpu_batched(boxes, scores, thresh, valid=None, pre_max_size=None, post_m
             return _no_groups(G, dev)
         sc = (scores if scores.dtype == torch.float32 else scores.float()).contiguous()
         vb = None if valid is None else valid.to(torch.bool).contiguous()   # 1 byte per flag
-        th = _thresh_tensor(thresh, G, dev)
+        th = _host.thresh_tensor(thresh, G, dev)
         keep = torch.empty((G, cap), dtype=torch.int64, device=dev)
         ws = torch.empty(_batched_ws_bytes(G, N, cap), dtype=torch.uint8, device=dev)
         # the G data-dependent result lengths arrive in pinned host memory, written by the scan kernels themselves, and are
@@ -233,7 +217,7 @@ def nms_gpu_batched(boxes, scores, thresh, valid=None, pre_max_size=None, post_m
         if cap == 0:
             return _no_groups(G, dev)
         order = order.contiguous()
-        th = _thresh_tensor(thresh, G, dev)
+        th = _host.thresh_tensor(thresh, G, dev)
         keep = torch.empty((G, cap), dtype=torch.int64, device=dev)
         num = torch.empty(G, dtype=torch.int64, device=dev)
         ws = torch.empty(lib.rnms_batched_workspace_bytes(G, cap), dtype=torch.uint8, device=dev)
@@ -283,7 +267,7 @@ def nms_gpu_multi(boxes_list, scores_list, thresh, pre_max_size=None, post_max_s
         boxes = _check_boxes(torch.cat([b.reshape(-1, 5) for b in boxes_list], dim=0), 5, 'nms_gpu_multi')
         flat = torch.cat([s2.reshape(-1) for s2 in scores_list], dim=0).to(torch.float32).contiguous()
         seg = torch.tensor(offs, dtype=torch.int32, device=dev)
-        th = _thresh_tensor(ths, G, dev)
+        th = _host.thresh_tensor(ths, G, dev)
         keep = torch.empty((G, cap), dtype=torch.int64, device=dev)
         num = torch.empty(G, dtype=torch.int64, device=dev)
         ws = torch.empty(lib.rnms_batched_scored_workspace_bytes(G, nmax, cap), dtype=torch.uint8, device=dev)
@@ -301,7 +285,7 @@ def multi_class_nms(box_probs, boxes_for_nms, score_thr, nms_thr, use_rotate_nms
     N, C = box_probs.shape
     st = score_thr if isinstance(score_thr, (list, tuple)) else [score_thr] * C
     sc = box_probs.t().contiguous().to(torch.float32)
-    valid = sc >= _thresh_tensor(st, C, sc.device).unsqueeze(1)
+    valid = sc >= _host.thresh_tensor(st, C, sc.device).unsqueeze(1)
     per_class = nms_gpu_batched(boxes_for_nms, sc, nms_thr, valid, normal=not use_rotate_nms)
     sel = [k for k in per_class if k.shape[0] > 0]
     return torch.cat(sel, dim=0) if sel else []
@@ -321,7 +305,7 @@ def multi_class_nms_batch(box_probs, boxes_for_nms, roi_batch_id, batch_size, sc
     dev = box_probs.device
     bid = roi_batch_id.to(device=dev, dtype=torch.int64).reshape(-1)
     sc = box_probs.t().contiguous().to(torch.float32)                                   # (C, R)
-    above = sc >= _thresh_tensor(st, C, dev).unsqueeze(1)                              # (C, R)
+    above = sc >= _host.thresh_tensor(st, C, dev).unsqueeze(1)                              # (C, R)
     member = bid.unsqueeze(0) == torch.arange(batch_size, device=dev).unsqueeze(1)      # (B, R)
     valid = (member.unsqueeze(1) & above.unsqueeze(0)).reshape(batch_size * C, R)       # group b * C + k
     scores = sc.unsqueeze(0).expand(batch_size, C, R).reshape(batch_size * C, R)

@@ -10,8 +10,9 @@ between mmdet3d 0.x and 1.0 — `clockwise` selects (default: 1.0's counter-cloc
 """
 import torch
 
-from . import _lib
-from .iou3d import _thresh_tensor, nms_gpu_batched
+from . import _host
+from ._host import f32c
+from .iou3d import nms_gpu_batched
 
 
 def pvrcnn_head_get_bboxes(rois, cls_score, bbox_pred, class_labels, class_pred, cfg, batch_size=None, clockwise=False, return_decoded=False):
@@ -23,26 +24,19 @@ def pvrcnn_head_get_bboxes(rois, cls_score, bbox_pred, class_labels, class_pred,
     batch_size   : number of samples; default len(class_pred) (the reference reads `roi_batch_id.max()` back).
     Returns per sample (boxes (n, 7), scores (n,), labels (n,)): the kept rois class after class, as the reference returns them (its
     `box_type_3d(...)` wrapper aside).  return_decoded=True adds the (R, 7) decoded boxes and (R, 5) NMS rectangles as a fourth item."""
-    if not rois.is_cuda:
-        raise RuntimeError('pvrcnn_head_get_bboxes: the MI355X implementation has no CPU path')
+    _host.gpu_only(rois, 'pvrcnn_head_get_bboxes')
     if rois.dim() != 2 or rois.shape[1] != 8 or bbox_pred.shape != (rois.shape[0], 7):
         raise RuntimeError(f'pvrcnn_head_get_bboxes: rois {tuple(rois.shape)} / bbox_pred {tuple(bbox_pred.shape)} are not (R, 8) / (R, 7)')
     B = len(class_pred) if batch_size is None else int(batch_size)
     if len(class_pred) != B or len(class_labels) != B:
         raise RuntimeError(f'pvrcnn_head_get_bboxes: {B} samples but {len(class_pred)} class_pred / {len(class_labels)} class_labels entries')
-    get = (lambda k: cfg[k]) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k))
-    lib = _lib.load()
+    get = lambda k: _host.cfg_get(cfg, k)        # no default: a missing key raises
     dev = rois.device
     R = rois.shape[0]
-    r32 = rois.detach()
-    r32 = r32 if (r32.dtype == torch.float32 and r32.is_contiguous()) else r32.float().contiguous()
-    p32 = bbox_pred.detach()
-    p32 = p32 if (p32.dtype == torch.float32 and p32.is_contiguous()) else p32.float().contiguous()
+    r32, p32 = f32c(rois.detach()), f32c(bbox_pred.detach())
     boxes = torch.empty((R, 7), dtype=torch.float32, device=dev)
     bev = torch.empty((R, 5), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.coder_roi_decode(r32.data_ptr(), 8, 1, p32.data_ptr(), R, int(bool(clockwise)), boxes.data_ptr(), bev.data_ptr(),
-                                        torch.cuda.current_stream().cuda_stream), 'coder_roi_decode')
+    _host.call('coder_roi_decode', dev, (r32.data_ptr(), 8, 1, p32.data_ptr(), R, int(bool(clockwise)), boxes.data_ptr(), bev.data_ptr()))
     bid = rois[:, 0].to(torch.int64)
     # the sample's rois in their order inside `rois`: a stable sort by sample id gives, per sample, the global rows in that order
     order = torch.sort(bid, stable=True)[1]
@@ -66,7 +60,7 @@ def pvrcnn_head_get_bboxes(rois, cls_score, bbox_pred, class_labels, class_pred,
     starts = [0]
     for n in sizes:
         starts.append(starts[-1] + n)
-    above = probs.t() >= _thresh_tensor(st, C, dev).unsqueeze(1)                       # (C, R)
+    above = probs.t() >= _host.thresh_tensor(st, C, dev).unsqueeze(1)                       # (C, R)
     pos = torch.arange(R, device=dev)
     lo = torch.tensor(starts[:-1], device=dev).unsqueeze(1)
     hi = torch.tensor(starts[1:], device=dev).unsqueeze(1)

@@ -330,6 +330,28 @@ def test_get_bboxes_replays_as_a_hipgraph():
             assert torch.equal(out['labels'][b, :n[b]], want[b][2])
 
 
+def test_select_best_is_captured_on_the_callers_stream():
+    """select_best launches on the CURRENT stream of the tensors' device — inside `torch.cuda.graph` that is the capture's side
+    stream.  A launch that went to another stream would be missing from the graph and the replay would return the rows of the
+    warm-up call.  128 cells per sample (2 classes x 8 x 8) and K = 5: the keep-everything path of the selection kernel."""
+    g = torch.Generator().manual_seed(41)
+    K = 5
+    scores = torch.rand((2, 2, 8, 8), generator=g).to(dev())
+    preds = torch.randn((2, 3, 8, 8), generator=g).to(dev())
+    amd.extras.select_best(scores, preds, K)      # sets the kernel's LDS attribute outside the capture
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = amd.extras.select_best(scores, preds, K)
+    scores.copy_(torch.rand((2, 2, 8, 8), generator=g))
+    preds.copy_(torch.randn((2, 3, 8, 8), generator=g))
+    graph.replay()
+    torch.cuda.synchronize()
+    want = amd.extras.select_best(scores, preds, K)
+    for got, ref in zip(out, want):
+        assert got.dtype == ref.dtype and torch.equal(got, ref)
+
+
 def test_get_bboxes_kitti_centerpoint_geometry():
     """configs/_base_/models/pillarmvf_centerpoint_016pillar_second_secfpn_kitti.py: maps of 248 rows x 216 columns, tasks with
     1 / 1 / 2 heat-map classes, CenterPointBBoxCoderRev (rot = atan2(sin, cos)), its test_cfg"""

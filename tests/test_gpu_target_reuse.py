@@ -3,6 +3,8 @@ launch of its stream runs opposite to it (so that it starts on the target rows s
 launch ascends.  The order must change nothing: repeated calls on one target, which alternate direction, return
 bit-identical losses and gradients, on every path of the kernel (partial last tile, unaligned rows, (N,7) weights with and
 without positives, target gradient, bbox-coder prologues, single-launch finish and two-stage reduce)."""
+import types
+
 import numpy as np
 import pytest
 import torch
@@ -102,7 +104,7 @@ def test_target_requires_grad(amd, n):
 
 @pytest.mark.parametrize('n', (255, 16_385, 1_000_003))
 def test_prologues(amd, n):
-    from mmdet3d_gaussian_amd.head_loss import _prologue
+    from mmdet3d_gaussian_amd._lib import prologue as _prologue
     g = torch.Generator().manual_seed(13)
     enc_p = (torch.randn(n, 7, generator=g) * 0.2).cuda()
     enc_t = (torch.randn(n, 7, generator=g) * 0.2).cuda()
@@ -113,7 +115,7 @@ def test_prologues(amd, n):
     mod = amd.GDLoss('kld3d', fun='log1p', tau=1.0, reduction='mean', loss_weight=2.0)
     pro_a = _prologue(1, anchors)
     _same(_repeat(lambda: _call(mod, enc_p, enc_t, weight=w, avg_factor=float(n), _prologue=pro_a)))
-    pro_c = _prologue(2, locs, norm_bbox=True, out_size_factor=4.0, voxel_size=(0.1, 0.1), pc_range=(-51.2, -51.2))
+    pro_c = _prologue(2, locs, types.SimpleNamespace(norm_bbox=True, out_size_factor=4.0, voxel_size=(0.1, 0.1), pc_range=(-51.2, -51.2)))
     dims = enc_t.clone()
     dims[:, 3:6] = dims[:, 3:6].exp()
     _same(_repeat(lambda: _call(mod, enc_p, dims, avg_factor=float(n), _prologue=pro_c)))

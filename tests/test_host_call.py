@@ -1,5 +1,6 @@
 """mmdet3d-gaussian_amd/_host.py — the per-call plumbing every module above the C ABI shares (pointer helpers, the GPU / `_cpu` twin
-dispatch, the bounded memo, the count check) — and the group-cut helper of iou3d.py.  No GPU needed."""
+dispatch and its extras counterpart, operand normalisation, the config lookup, the GPU-only refusal, the unit-gradient registry, the
+bounded memo, the count check) — and the group-cut helper of iou3d.py.  No GPU needed."""
 import types
 
 import numpy as np
@@ -106,3 +107,98 @@ def test_the_workspace_memos_go_through_it():
     assert gd_loss._ws_floats(64) == lib.gd3d_loss_workspace_bytes(64) // 4 == gd_loss._ws_floats(64)
     assert iou3d._ws_bytes(700) == lib.rnms_workspace_bytes(700)
     assert iou3d._batched_ws_bytes(3, 700, 500) == lib.rnms_batched_scored_workspace_bytes(3, 700, 500)
+
+
+def test_f32c_and_i64c_return_the_operand_itself_when_it_already_is():
+    f, i = torch.arange(12, dtype=torch.float32).reshape(3, 4), torch.arange(5)
+    assert _host.f32c(f) is f and _host.i64c(i) is i
+    for fn, dtype, ops in ((_host.f32c, torch.float32, (f.t(), f[:, ::2], f.half(), torch.arange(6, dtype=torch.int32))),
+                           (_host.i64c, torch.int64, (torch.arange(12).reshape(3, 4).t(), torch.arange(6, dtype=torch.int32), f))):
+        for t in ops:
+            got = fn(t)
+            assert got is not t and got.dtype == dtype and got.is_contiguous() and got.shape == t.shape
+            assert torch.equal(got, t.to(dtype))
+
+
+def test_cfg_get_reads_a_dict_or_an_object_and_raises_only_without_a_default():
+    d, o = dict(gamma=2.0, alpha=None), types.SimpleNamespace(gamma=3.0, alpha=None)
+    assert _host.cfg_get(d, 'gamma', 1.0) == 2.0 and _host.cfg_get(o, 'gamma', 1.0) == 3.0
+    assert _host.cfg_get(d, 'alpha', 0.25) is None and _host.cfg_get(o, 'alpha', 0.25) is None   # present: not the default
+    assert _host.cfg_get(d, 'beta', 1.0) == 1.0 and _host.cfg_get(o, 'beta', 1.0) == 1.0
+    assert _host.cfg_get(d, 'beta', None) is None and _host.cfg_get(o, 'beta', None) is None
+    assert _host.cfg_get(d, 'gamma') == 2.0 and _host.cfg_get(o, 'gamma') == 3.0
+    with pytest.raises(KeyError):
+        _host.cfg_get(d, 'beta')
+    with pytest.raises(AttributeError):
+        _host.cfg_get(o, 'beta')
+
+
+def test_gpu_only_refuses_a_cpu_tensor_with_the_one_sentence():
+    with pytest.raises(RuntimeError) as e:
+        _host.gpu_only(torch.zeros(2), 'select_best')
+    assert str(e.value) == 'select_best: the MI355X implementation has no CPU path'
+    with pytest.raises(RuntimeError, match='^center_head_heatmap_loss: the MI355X implementation has no CPU path$'):
+        amd.extras.center_head_heatmap_loss(dict(type='GaussianFocalLoss'), [torch.zeros(1, 1, 2, 2)], [torch.zeros(1, 1, 2, 2)])
+
+
+def test_call_extras_appends_the_stream_under_the_guard_and_raises_with_the_entry_points_name(monkeypatch):
+    seen, current = [], [0]
+
+    def op(*args):
+        seen.append((current[0],) + args)
+        return 0
+    lib = types.SimpleNamespace(op=op, bad=lambda *args: 10002)
+    monkeypatch.setattr(_host._lib, 'load_extras', lambda: lib)
+    monkeypatch.setattr(_host, 'get_device', lambda: current[0])
+    monkeypatch.setattr(_host, 'set_device', lambda i: current.__setitem__(0, i))
+    monkeypatch.setattr(_host, 'raw_stream', lambda i: 0x5000 + i)
+    _host.call_extras('op', torch.device('cuda', 1), (1, 2.5, None))
+    _host.call_extras('op', torch.device('cuda', 0), ())
+    assert seen == [(1, 1, 2.5, None, 0x5001), (0, 0x5000)]     # ran with the tensors' device current, on ITS current stream
+    assert current[0] == 0
+    with pytest.raises(RuntimeError, match=r'^bad failed with code 10002 \(too large\)$'):
+        _host.call_extras('bad', torch.device('cuda', 1), (1,))
+    assert current[0] == 0
+    with pytest.raises(AttributeError):               # an entry point the library does not have: an error, not another path
+        _host.call_extras('missing', torch.device('cuda', 1), ())
+    assert current[0] == 0
+
+
+def test_the_unit_gradient_is_known_by_address_alone():
+    from mmdet3d_gaussian_amd import gd_loss
+    u = _host.unit_grad('cpu')
+    assert gd_loss.unit_grad is _host.unit_grad and gd_loss.unit_grad('cpu') is u and _host.unit_grad(CPU) is u
+    assert u.dim() == 0 and u.dtype == torch.float32 and float(u) == 1.0
+    assert _host.is_unit_grad(u) and _host.has_unit_grad(torch.zeros(1))
+    assert not _host.is_unit_grad(u.clone())
+    assert not _host.is_unit_grad(u.reshape(1))                         # the same address, one dimension
+    assert not _host.is_unit_grad(torch.ones((), dtype=torch.float64))
+    with pytest.raises(RuntimeError, match='unit_grad: no implementation'):
+        _host.unit_grad('meta')
+
+
+@pytest.mark.parametrize('glue', ['python', None])
+def test_the_unit_gradient_is_recognised_whichever_glue_is_loaded_after_it(glue):
+    """The constant exists BEFORE the glue is (re)loaded — the order the two tables of earlier versions depended on: the same
+    tensor is still the unit gradient, and `.backward()` of a CPU GDLoss value (which starts from it: gd_loss.LossValue) gives
+    the gradients of an explicit ones gradient bit for bit."""
+    from mmdet3d_gaussian_amd import _lib
+    u = _host.unit_grad('cpu')
+    g = torch.Generator().manual_seed(3)
+    tgt = torch.rand(33, 7, generator=g) * torch.tensor([40, 40, 2, 3, 3, 2, 3.0]) + torch.tensor([0, 0, 0, 0.5, 0.5, 0.5, -1.5])
+    pred = tgt + 0.1 * torch.randn(33, 7, generator=g)
+    mod = amd.build_loss(dict(type='GDLoss', loss_type='kld3d', fun='log1p', tau=1.0, loss_weight=5.0))
+    try:
+        _lib.set_host_glue(glue)
+        _lib.load_node()
+        assert _host.unit_grad('cpu') is u and _host.is_unit_grad(u)
+        grads = []
+        for explicit in (False, True):
+            p, t = pred.clone().requires_grad_(True), tgt.clone().requires_grad_(True)
+            out = mod(p, t)
+            out.backward(gradient=torch.ones(())) if explicit else out.backward()
+            grads.append((p.grad, t.grad))
+        assert grads[0][0].abs().max() > 0 and grads[0][1].abs().max() > 0
+        assert torch.equal(grads[0][0], grads[1][0]) and torch.equal(grads[0][1], grads[1][1])
+    finally:
+        _lib.set_host_glue(None)

@@ -60,8 +60,8 @@ def main():
         return [l.detach() for l in ls]
 
     variants = [('sum_bwd', lambda: step_sum()), ('unit_bwd', lambda: step_unit())]
-    from mmdet3d_gaussian_amd import _lib, _pynode
-    real_is_unit = _pynode._is_unit_grad
+    from mmdet3d_gaussian_amd import _host, _lib
+    real_is_unit = _host.is_unit_grad
 
     def with_python_glue(fn, hack):
         def run():
@@ -71,11 +71,11 @@ def main():
             def one(g):
                 calls[0] += 1
                 return real_is_unit(g) or calls[0] % 3 != 1
-            _pynode._is_unit_grad = {'none': real_is_unit, 'no_finish': lambda g: True, 'one_finish': one}[hack]
+            _host.is_unit_grad = {'none': real_is_unit, 'no_finish': lambda g: True, 'one_finish': one}[hack]
             try:
                 return fn()
             finally:
-                _pynode._is_unit_grad = real_is_unit
+                _host.is_unit_grad = real_is_unit
                 _lib.set_host_glue(None)
         return run
     variants += [('sum_bwd_py', with_python_glue(step_sum, 'none')), ('sum_bwd_py_no_finish', with_python_glue(step_sum, 'no_finish')),
