@@ -759,6 +759,65 @@ int gd3d_pib_mask_targets_cpu(const float* points, const int32_t* pts_batch_cnt,
 int gd3d_roi_grid_points_cpu(const float* rois, int32_t roi_stride, int32_t first_col, int64_t R, int32_t G,
                              int32_t clockwise, float* out, int32_t nthreads);
 
+/* ------------------------------------------------------------------------------------
+ * The RoI head's training slice (an addition inside ABI 6): PVRCNNBboxHead.get_targets / _get_target_single
+ * (models/roi_heads/bbox_heads/pvrcnn_bbox_head.py:213-316, concat=True) as one launch, and loss with get_corner_loss_lidar
+ * (:140-211, :318-351) — the three losses and their gradients — as one launch.  One workgroup each, no workspace, no atomics on
+ * floats, no read-back: the same inputs give the same bits on every run.
+ *
+ * gd3d_roi_head_targets : pos_bboxes / pos_gt_bboxes (P,7) fp32 = the positives' RoIs and gt boxes of B samples one after
+ *   another with pos_batch_cnt (B) int32; ious (R) fp32 = the sampled RoIs' IoUs with roi_batch_cnt (B) int32.  Every count
+ *   is clamped to [0, rows left]; nothing is validated on the host.  B <= 1024, P, R <= 2^24 (GD3D_E_TOOLARGE).
+ *     label (R) fp32         = iou > pos ? 1 : (iou < neg ? 0 : iou * 2 - 0.5)
+ *     reg_mask (R) int64     = 1 for the first pos_batch_cnt[b] rows of sample b
+ *     label_weights (R) fp32 = (label >= 0) / max(their number, 1);  bbox_weights (R) fp32 = reg_mask / max(its sum, 1)
+ *     RoI rows past the counts' sum belong to no sample: label 0, mask 0, both weights 0.
+ *     bbox_targets (P,7) fp32: with mod(a) = fmodf(a, 2 pi), + 2 pi when negative (the constants are the fp32 roundings of the
+ *       doubles 2 pi, pi, pi / 2, 3 pi / 2):  ry = mod(roi[6]);  d = gt[0:3] - roi[0:3] turned about z by -ry
+ *       (x' = dx cos ry + dy sin ry, y' = -dx sin ry + dy cos ry; clockwise != 0 flips the angle's sign);  r = mod(gt[6] - ry);
+ *       pi / 2 < r < 3 pi / 2: r = mod(r + pi);  r > pi: r -= 2 pi;  r clamped to [-pi / 2, pi / 2];  then
+ *       DeltaXYZWLHRBBoxCoder.encode of (x', y', d_z, gt dims, r) against the anchor (0, 0, 0, roi dims, 0).  Rows past the
+ *       positive counts' sum are written 0.
+ *     PRECONDITION, not checked (it would take a host read): pos_batch_cnt[b] <= roi_batch_cnt[b] for every sample.  A sample
+ *       with more positives than RoIs gets more target rows than reg_mask has ones, and gd3d_roi_head_loss, which pairs the j-th
+ *       mask positive with target row j, then pairs every later positive with the wrong target.
+ * gd3d_roi_head_loss : cls_score (R), bbox_pred (R,7), rois = R rows of roi_stride floats with the box at column first_col (as
+ *   coder_roi_decode takes them), labels / label_weights / bbox_weights (R) fp32, reg_mask (R) int64, bbox_targets /
+ *   pos_gt_bboxes (P,7).  The j-th row with reg_mask > 0, in row order, pairs with row j of the two (P,7) arrays; positive rows
+ *   past the P-th are ignored.  losses (3) fp32:
+ *     [0] cls_weight  * sum_i label_weights[i] (max(x, 0) - x z + log1p(exp(-|x|)))         (sigmoid cross entropy, 'sum')
+ *     [1] bbox_weight * sum over the paired rows and 7 columns of bbox_weights[row] * smooth_l1(pred - target; beta), beta > 0
+ *     [2] with_corner_loss != 0: the mean over the paired rows of the mean over the 8 corners of Huber(min(|p - g|, |p - g'|), 1):
+ *         p the corners of the box decoded from (roi, pred) by coder_roi_decode's math, g those of the gt, g' of the gt turned
+ *         by pi; corners = centre + Rz(yaw) (dims * n), n_x, n_y = -+0.5, n_z = 0, 1.  Otherwise 0.
+ *   grad_cls (R), grad_bbox (R,7) = d([1] + [2]) / d bbox_pred, grad_bbox_l1 = d[1] / d bbox_pred, grad_bbox_corner = d[2] / d
+ *   bbox_pred; each nullable, each written in full (zeros for the rows without a pair).  A zero corner distance has a zero
+ *   gradient; on an exact tie of the two distances the unflipped gt takes the whole gradient.  No pair at all: [1] = [2] = 0.
+ *   clockwise != 0 flips the sense of the decode's and the corners' rotations, as in gd3d_roi_head_targets.
+ * `_cpu` twins (csrc/roi_head_cpu.cpp): the same contracts on HOST memory on the calling thread; label, reg_mask and both
+ * weight arrays BIT-IDENTICAL to the kernels', the other values equal up to the two math libraries' sin / cos / exp / log.
+ * ---------------------------------------------------------------------------------- */
+int gd3d_roi_head_targets(const float* pos_bboxes, const float* pos_gt_bboxes, const float* ious,
+                          const int32_t* pos_batch_cnt, const int32_t* roi_batch_cnt, int32_t B, int64_t P, int64_t R,
+                          float cls_pos_thr, float cls_neg_thr, int32_t clockwise, float* label, float* bbox_targets,
+                          int64_t* reg_mask, float* label_weights, float* bbox_weights, void* stream);
+int gd3d_roi_head_loss(const float* cls_score, const float* bbox_pred, const float* rois, int32_t roi_stride,
+                       int32_t first_col, const float* labels, const float* bbox_targets, const float* pos_gt_bboxes,
+                       const int64_t* reg_mask, const float* label_weights, const float* bbox_weights, int64_t R, int64_t P,
+                       float beta, float cls_weight, float bbox_weight, int32_t with_corner_loss, int32_t clockwise,
+                       float* losses, float* grad_cls, float* grad_bbox, float* grad_bbox_l1, float* grad_bbox_corner,
+                       void* stream);
+int gd3d_roi_head_targets_cpu(const float* pos_bboxes, const float* pos_gt_bboxes, const float* ious,
+                              const int32_t* pos_batch_cnt, const int32_t* roi_batch_cnt, int32_t B, int64_t P, int64_t R,
+                              float cls_pos_thr, float cls_neg_thr, int32_t clockwise, float* label, float* bbox_targets,
+                              int64_t* reg_mask, float* label_weights, float* bbox_weights);
+int gd3d_roi_head_loss_cpu(const float* cls_score, const float* bbox_pred, const float* rois, int32_t roi_stride,
+                           int32_t first_col, const float* labels, const float* bbox_targets, const float* pos_gt_bboxes,
+                           const int64_t* reg_mask, const float* label_weights, const float* bbox_weights, int64_t R,
+                           int64_t P, float beta, float cls_weight, float bbox_weight, int32_t with_corner_loss,
+                           int32_t clockwise, float* losses, float* grad_cls, float* grad_bbox, float* grad_bbox_l1,
+                           float* grad_bbox_corner);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

@@ -15,6 +15,8 @@
   * ``points_in_boxes_part`` / ``points_in_boxes_all`` (+ ``*_stacked``) / ``pointwise_mask_targets`` / ``roi_grid_points`` /
     ``roi_grid_queries``       — mmdet3d's roiaware_pool3d point-in-box ops, PointwiseMaskHead.get_targets
                                  (pointwise_mask_head.py:62-92) and the RoI grid points (batch_roigrid_extractor.py:56-71)
+  * ``pvrcnn_head_get_targets`` / ``pvrcnn_head_loss`` — PVRCNNBboxHead's training slice (pvrcnn_bbox_head.py:140-351): the targets
+                                 in one launch, the class, box and corner losses with their gradients in one more, no host sync
   * ``GraphedStep``            — a launch-bound loss slice, forward and backward, captured once as a hipGraph and replayed
 Everything outside §8 that earlier rounds built (frozen, DESIGN_EXTRAS.md) lives in ``mmdet3d_gaussian_amd.extras``.
 
@@ -38,6 +40,7 @@ from .scatter import Scatter, scatter_index, scatter_reduce
 from .vsa import QueryAndGroup, ball_query, furthest_point_sample, furthest_point_sample_stacked, grouping
 from .points_in_boxes import (pointwise_mask_targets, points_in_boxes_all, points_in_boxes_all_stacked, points_in_boxes_part,
                               points_in_boxes_part_stacked, roi_grid_points, roi_grid_queries)
+from .pvrcnn_train import pvrcnn_head_get_targets, pvrcnn_head_loss
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
                         anchor_head_decoded_loss_fused, center_head_gd_loss, center_head_losses)
 from . import extras
@@ -59,4 +62,4 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'center_head_losses', 'Scatter', 'scatter_index', 'scatter_reduce', 'QueryAndGroup', 'ball_query', 'grouping',
            'furthest_point_sample', 'furthest_point_sample_stacked', 'points_in_boxes_part', 'points_in_boxes_all',
            'points_in_boxes_part_stacked', 'points_in_boxes_all_stacked', 'pointwise_mask_targets', 'roi_grid_points', 'roi_grid_queries',
-           'extras']
+           'pvrcnn_head_get_targets', 'pvrcnn_head_loss', 'extras']

@@ -261,6 +261,12 @@ SYMBOLS = {
     'gd3d_pib_all_cpu': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _i32]),
     'gd3d_pib_mask_targets_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _i32, _vp, _vp, _i32]),
     'gd3d_roi_grid_points_cpu': (_int, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _i32]),
+    'gd3d_roi_head_targets': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_roi_head_loss': (_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _f32, _i32, _i32,
+                                  _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_roi_head_targets_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_roi_head_loss_cpu': (_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _f32, _i32, _i32,
+                                      _vp, _vp, _vp, _vp, _vp]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 

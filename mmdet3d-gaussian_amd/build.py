@@ -33,6 +33,7 @@ SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'coders.hip': ['-ffp-contract=off'],      # same rounding sequence as the torch elementwise ops it replaces
     'vsa.hip': ['-ffp-contract=off'],         # ball-query membership and FPS arg-max decisions replay bit for bit in vsa_cpu.cpp
     'pib.hip': ['-ffp-contract=off'],         # point-in-box decisions and RoI grid points replay bit for bit in pib_cpu.cpp
+    'roi_head.hip': ['-ffp-contract=off'],    # label / mask decisions and the target yaw's folds replay bit for bit in roi_head_cpu.cpp
 }
 # The frozen round-3 extras OUTSIDE §8 (DESIGN_EXTRAS.md; include/gd3d_extras.h): a library of their own since round 6,
 # libgd3d_extras.so, linked against libgd3d.so (the inference slices call its rnms_* entry points) and loaded only by
@@ -58,6 +59,7 @@ HOST_SOURCES = {
     'rbox_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],   # same single-operation sequence as rbox.hip: bit-identical decisions
     'vsa_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],    # same for vsa.hip: idx, cnt, mask and FPS picks bit-identical
     'pib_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],    # same for pib.hip: box_idx, flags, targets and grid points bit-identical
+    'roi_head_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],   # same for roi_head.hip: label, reg_mask and the weights bit-identical
 }
 HOST_COMMON = ['-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 
