@@ -818,6 +818,68 @@ int gd3d_roi_head_loss_cpu(const float* cls_score, const float* bbox_pred, const
                            int32_t clockwise, float* losses, float* grad_cls, float* grad_bbox, float* grad_bbox_l1,
                            float* grad_bbox_corner);
 
+/* ------------------------------------------------------------------------------------
+ * The RoI head's assign-and-sample stage (an addition inside ABI 6): PVRCNNROIHead._assign_and_sample
+ * (models/roi_heads/pvrcnn_roi_head.py:225-297) — a MaxIoUAssigner per class on BboxOverlaps3D(coordinate='lidar') and the
+ * IoUNegPiecewiseSampler — for a whole batch: one launch of one workgroup per sample and one single-workgroup launch that packs
+ * the samples back to back.  No read-back, no allocation; given the keys the outputs are the same bits on every run and in the
+ * `_cpu` twins (csrc/roi_sample_cpu.cpp, host memory, calling thread).  mmdet's assigner and sampler are third party, absent from
+ * the reference and not pinned by it: the rules below are what is computed.
+ *
+ * gd3d_roi_iou3d : iou (n1, n2) fp32 of rows [x, y, z, dx, dy, dz, yaw], z the BOTTOM face.  Per pair, in fp32, one operation at
+ *   a time (-ffp-contract=off, the NMS path's fixed sin / cos / atan2 sequences):
+ *     ov_bev = the iou3d-family overlap (rnms_*'s pair test) of the rectangles [x - dx/2, y - dy/2, x + dx/2, y + dy/2, yaw]
+ *     ov_h   = max(min(z1 + dz1, z2 + dz2) - max(z1, z2), 0);   ov = ov_bev * ov_h
+ *     iou    = ov / max(dx1 dy1 dz1 + dx2 dy2 dz2 - ov, 1e-8)
+ *   n1 * n2 < 2^31 (GD3D_E_TOOLARGE); an empty operand writes nothing.
+ *
+ * gd3d_roi_assign_sample : proposals (N,7) fp32 / proposal_labels (N) int64 / keys (N) fp32 of B samples one after another with
+ *   prop_batch_cnt (B) int32; gt_bboxes (G,7) / gt_labels (G) int64 with gt_batch_cnt (B); fill_keys (B * num) fp32.  Counts are
+ *   DEVICE memory, clamped to [0, rows left]; of a sample's segment the first 4096 proposals and 1024 gts take part.
+ *   HOST arrays: pos_iou_thr / neg_iou_thr / min_pos_iou (C) fp32 and assign_flags (C) (bit 0 match_low_quality, bit 1
+ *   gt_max_assign_all), one assigner per class; neg_piece_fractions (K) fp64 in [0, 1] and neg_iou_piece_thrs (K) fp32, positive
+ *   and strictly descending.  C <= 16, num <= 1024, 0 <= npos <= num, K <= 8, B <= 1024.
+ *   Assignment, per sample: a proposal with label c in [0, C) meets the gts with label c, under assigner c; any other label meets
+ *   nothing.  An IoU that is NaN or negative counts as 0.  max_overlap[n] = the largest IoU over its class's gts (lowest gt on a
+ *   tie); without one max_overlap = 0 and gt_ind = 0.  Otherwise, in this order: gt_ind = -1;  0 where 0 <= max < neg_iou_thr;
+ *   argmax + 1 where max >= pos_iou_thr;  with match_low_quality, for each gt g of the class in ascending index with gt_max[g] >=
+ *   min_pos_iou: every proposal of the class with iou[n, g] == gt_max[g] (gt_max_assign_all), or only the lowest-index one, gets
+ *   g + 1, a later gt overwriting.  gt_ind numbers the sample's full gt list.
+ *   Sampling, per sample; "draw k of S" = all of S when |S| <= k, else the k members with the smallest (key, proposal index); a
+ *   key outside [0, 1) or NaN is clamped into it.  Positives {gt_ind > 0}: a draw of npos, output in ascending proposal index.
+ *   Negatives {gt_ind == 0}, expected = num - positives drawn: piece i = {lo <= max_overlap < thr[i]}, lo = thr[i + 1], 0 for the
+ *   last piece; piece i < K - 1 expects (int)(expected * fraction[i]) + carry, the last one expected - chosen so far; a piece with
+ *   fewer members gives them all and ADDS its shortfall to the carry, another gives a draw and zeroes the carry; no piece gives
+ *   more than what is left of expected; members leave a piece in (key, index) order.  A short last piece is followed by slots
+ *   filled with replacement up to expected: the slot at position j of the sample's output takes member min(floor(fill_keys[b *
+ *   num + j] * m), m - 1) of the last piece in ascending index order, or, that piece being empty, of the negatives chosen so far
+ *   in output order; nothing chosen, nothing filled.
+ *   Outputs, samples packed back to back (positives, then negatives), rows past the counts' sums written as batch id -1 / zeros:
+ *   rois (B * num, 8) [batch id, box], ious (B * num) = max_overlap, inds (B * num) int64 = proposal index within its sample,
+ *   pos_bboxes / pos_gt_bboxes (B * npos, 7), pos_assigned_gt_inds (B * npos) int64 = gt_ind - 1, pos_batch_cnt / roi_batch_cnt
+ *   (B) int32; gt_inds / max_overlaps / labels (N) (labels = the assigned gt's label, -1 where gt_ind <= 0; rows of no sample or
+ *   past a sample's limit: -1 / 0 / -1).  stage: B * (2 + num) int32 of scratch (per sample: positives drawn, rows, the chosen
+ *   indices), written in full.
+ * ---------------------------------------------------------------------------------- */
+int gd3d_roi_iou3d(const float* bboxes1, int64_t n1, const float* bboxes2, int64_t n2, float* iou, void* stream);
+int gd3d_roi_assign_sample(const float* proposals, const int64_t* proposal_labels, const int32_t* prop_batch_cnt, int64_t N,
+                           const float* gt_bboxes, const int64_t* gt_labels, const int32_t* gt_batch_cnt, int64_t G, int32_t B,
+                           const float* keys, const float* fill_keys, int32_t C, const float* pos_iou_thr,
+                           const float* neg_iou_thr, const float* min_pos_iou, const int32_t* assign_flags, int32_t num,
+                           int32_t npos, int32_t K, const double* neg_piece_fractions, const float* neg_iou_piece_thrs,
+                           float* rois, float* ious, int64_t* inds, float* pos_bboxes, float* pos_gt_bboxes,
+                           int64_t* pos_assigned_gt_inds, int32_t* pos_batch_cnt, int32_t* roi_batch_cnt, int64_t* gt_inds,
+                           float* max_overlaps, int64_t* labels, int32_t* stage, void* stream);
+int gd3d_roi_iou3d_cpu(const float* bboxes1, int64_t n1, const float* bboxes2, int64_t n2, float* iou);
+int gd3d_roi_assign_sample_cpu(const float* proposals, const int64_t* proposal_labels, const int32_t* prop_batch_cnt, int64_t N,
+                               const float* gt_bboxes, const int64_t* gt_labels, const int32_t* gt_batch_cnt, int64_t G,
+                               int32_t B, const float* keys, const float* fill_keys, int32_t C, const float* pos_iou_thr,
+                               const float* neg_iou_thr, const float* min_pos_iou, const int32_t* assign_flags, int32_t num,
+                               int32_t npos, int32_t K, const double* neg_piece_fractions, const float* neg_iou_piece_thrs,
+                               float* rois, float* ious, int64_t* inds, float* pos_bboxes, float* pos_gt_bboxes,
+                               int64_t* pos_assigned_gt_inds, int32_t* pos_batch_cnt, int32_t* roi_batch_cnt,
+                               int64_t* gt_inds, float* max_overlaps, int64_t* labels, int32_t* stage);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

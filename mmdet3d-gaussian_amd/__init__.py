@@ -41,6 +41,7 @@ from .vsa import QueryAndGroup, ball_query, furthest_point_sample, furthest_poin
 from .points_in_boxes import (pointwise_mask_targets, points_in_boxes_all, points_in_boxes_all_stacked, points_in_boxes_part,
                               points_in_boxes_part_stacked, roi_grid_points, roi_grid_queries)
 from .pvrcnn_train import pvrcnn_head_get_targets, pvrcnn_head_loss
+from .pvrcnn_sample import bbox_overlaps_3d, pvrcnn_assign_and_sample
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
                         anchor_head_decoded_loss_fused, center_head_gd_loss, center_head_losses)
 from . import extras
@@ -62,4 +63,4 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'center_head_losses', 'Scatter', 'scatter_index', 'scatter_reduce', 'QueryAndGroup', 'ball_query', 'grouping',
            'furthest_point_sample', 'furthest_point_sample_stacked', 'points_in_boxes_part', 'points_in_boxes_all',
            'points_in_boxes_part_stacked', 'points_in_boxes_all_stacked', 'pointwise_mask_targets', 'roi_grid_points', 'roi_grid_queries',
-           'pvrcnn_head_get_targets', 'pvrcnn_head_loss', 'extras']
+           'pvrcnn_head_get_targets', 'pvrcnn_head_loss', 'bbox_overlaps_3d', 'pvrcnn_assign_and_sample', 'extras']

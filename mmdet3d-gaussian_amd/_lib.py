@@ -267,6 +267,12 @@ SYMBOLS = {
     'gd3d_roi_head_targets_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
     'gd3d_roi_head_loss_cpu': (_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _f32, _i32, _i32,
                                       _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_roi_iou3d': (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    'gd3d_roi_iou3d_cpu': (_int, [_vp, _i64, _vp, _i64, _vp]),
+    'gd3d_roi_assign_sample': (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_roi_assign_sample_cpu': (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32,
+                                          _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 
