@@ -8,6 +8,9 @@ EQUAL.  `exact_iou3d` is the fp64 yardstick of the IoU values themselves.
 
 Each case is built from jittered copies of its gts — a copy lifted by a fraction f of the height has IoU (1 - f) / (1 + f), so all
 three regimes of the assigner occur by construction — and the builder ASSERTS that the situation a case is named after arises.
+The first sixteen cases spread their gts over 30 m: a proposal meets about one gt.  The `dense_*`, `limits`, `num1024_*`,
+`b1024_tiny` and `boundary_pairs` cases reach what only the device has: rounds of the pair queue, chunks of 1024 proposals, the
+sort at 4096 entries, every limit, and pairs on the edges of the two cheap overlap tests (`may_overlap_np` counts what is queued).
 """
 import functools
 import math
@@ -260,6 +263,210 @@ def mixed(n):
     return [('tight', a), ('medium', a), ('loose', a), ('far', n - 3 * a)]
 
 
+# ---- cases that fill the pair queue: WL_CAP pairs per round and chunk of 1024 proposals (csrc/roi_sample.hip)
+CHUNK, WL_CAP = 1024, 4096
+
+
+def _where_lt(a, b):
+    return np.where(a < b, a, b)                                      # rbox::fmin2, also on a NaN
+
+
+def _where_gt(a, b):
+    return np.where(a > b, a, b)                                      # rbox::fmax2
+
+
+def _lite_np(b):
+    """`lite_of` of csrc/roi_sample_common.h on (rows, 7) fp32, one operation at a time"""
+    b = np.asarray(b, np.float32)
+    two = np.float32(2.0)
+    hw, hh = b[:, 3] / two, b[:, 4] / two
+    x1, y1, x2, y2 = b[:, 0] - hw, b[:, 1] - hh, b[:, 0] + hw, b[:, 1] + hh
+    return dict(cx=(x1 + x2) / two, cy=(y1 + y2) / two, ra=np.abs(x2 - x1) + np.abs(y2 - y1), z0=b[:, 2], z1=b[:, 2] + b[:, 5])
+
+
+def pair_terms_np(props, gts):
+    """the quantities `may_overlap` decides on, (proposals, gts) fp32 matrices: squared centre distance, the circle test's bound
+    reach^2 * 1.0001 and the height overlap"""
+    a, b = _lite_np(props), _lite_np(gts)
+    with np.errstate(invalid='ignore', over='ignore'):
+        ddx, ddy = a['cx'][:, None] - b['cx'][None], a['cy'][:, None] - b['cy'][None]
+        reach = np.float32(0.5) * (a['ra'][:, None] + b['ra'][None]) + np.float32(1e-2)
+        d2 = ddx * ddx + ddy * ddy
+        bound = reach * reach * np.float32(1.0001)
+        top, bottom = _where_lt(a['z1'][:, None], b['z1'][None]), _where_gt(a['z0'][:, None], b['z0'][None])
+        ov_h = _where_gt(top - bottom, np.float32(0.0))
+    assert d2.dtype == bound.dtype == ov_h.dtype == np.float32
+    return d2, bound, ov_h
+
+
+def may_overlap_np(props, gts):
+    """numpy fp32 restatement of `lite_of` / `may_overlap` (csrc/roi_sample_common.h): (proposals, gts) bool, True where the device
+    queues the pair for clipping.  Used to COUNT queued pairs, so that a builder can assert the situation; never to decide."""
+    d2, bound, ov_h = pair_terms_np(props, gts)
+    with np.errstate(invalid='ignore'):
+        return ~(d2 > bound) & (ov_h != 0)
+
+
+def queued_pairs(sample, C):
+    """pairs of equal class in [0, C) the device queues, per chunk of 1024 proposals of one sample"""
+    props, plab, gts, glab = (t.numpy() for t in sample)
+    if props.shape[0] == 0 or gts.shape[0] == 0:
+        return [0] * -(-props.shape[0] // CHUNK)
+    m = may_overlap_np(props, gts) & (plab[:, None] == glab[None]) & (plab[:, None] >= 0) & (plab[:, None] < C)
+    return [int(m[i:i + CHUNK].sum()) for i in range(0, props.shape[0], CHUNK)]
+
+
+def make_dense(seed, n, n_gt, dup=False):
+    """one class, a parked row of cars: n_gt gts with centres in a 6 m x 6 m square, every proposal a tight / medium / loose copy of
+    gt (i mod n_gt), so a proposal passes the cheap tests with most gts.  `dup`: the last gt row is a copy of row 0 and the best
+    proposal of gt 0 is copied onto two other proposals of gt 0: three proposals tie the maxima of BOTH rows, and rule 4 with
+    gt_max_assign_all gives them to the higher index."""
+    rng = np.random.default_rng(seed)
+    gts = np.zeros((n_gt, 7), np.float32)
+    gts[:, :2] = rng.uniform(-3.0, 3.0, (n_gt, 2))
+    gts[:, 2] = rng.uniform(-1.2, -0.8, n_gt)
+    gts[:, 3:6] = np.array([3.9, 1.6, 1.5]) * rng.uniform(0.9, 1.1, (n_gt, 3))
+    gts[:, 6] = rng.uniform(-3.1, 3.1, n_gt)
+    if dup:
+        gts[-1] = gts[0]
+    props = np.asarray([_jitter(rng, gts[i % n_gt], ('tight', 'medium', 'loose')[i % 3]) for i in range(n)], np.float32)
+    props = torch.from_numpy(props[rng.permutation(n)])
+    gts = torch.from_numpy(gts)
+    if dup:
+        v = amd.bbox_overlaps_3d(props, gts[:1])[:, 0]
+        best = int(v.argmax())
+        others = [i for i in (v > 0.2).nonzero().view(-1).tolist() if i != best]
+        props[others[0]] = props[best]
+        props[others[-1]] = props[best]
+    return props, torch.zeros(n, dtype=torch.int64), gts, torch.zeros(n_gt, dtype=torch.int64)
+
+
+def _dense_check(name, case, chunks, dup=False):
+    """`chunks`: what must hold of the queued pairs per chunk"""
+    def check(out, infos):
+        q = queued_pairs([case[k][0] for k in ('proposals', 'proposal_labels', 'gt_bboxes', 'gt_labels')], 3)
+        n_gt = case['gt_bboxes'][0].shape[0]
+        FACTS[name] = dict(queued=q, to_last_gt=int((out['gt_inds'] == n_gt).sum()), n_pos=infos[0]['n_pos'])
+        ok = chunks(q)
+        if dup:     # the duplicate row: the three tied proposals go to the HIGHER index, nobody else does, gt 1 keeps the rest
+            v = amd.bbox_overlaps_3d(case['proposals'][0], case['gt_bboxes'][0][:1])[:, 0]
+            tied = v == v.max()
+            ok = ok and int(tied.sum()) >= 3 and bool((out['gt_inds'][tied] == n_gt).all()) and int((out['gt_inds'] == n_gt).sum()) >= 3 \
+                and bool((out['gt_inds'][~tied] != n_gt).all()) and int((out['gt_inds'] == 1).sum()) > 0
+        return ok
+    return check
+
+
+FACTS = {}      # what the builders measured, by case: printed by the tests, quoted in DESIGN.md
+
+
+def make_boundary(seed):
+    """one class, 64 gts 40 m apart (a proposal meets its own gt only) and 9 proposals per gt, placed ON the edges of the two cheap
+    tests of `may_overlap`:
+      a  same BEV rectangle, the bottom face at fp32(z + dz) of the gt: the height overlap is exactly 0.0f -> not queued, IoU 0;
+      b  the bottom face 1..8 ulp below that: a height overlap below 1e-6 and an IoU that is tiny and POSITIVE -> must be queued;
+      c  the centre at a squared distance of reach^2 * 1.0001 * (1 -+ 5e-4) from the gt's: just inside (queued, clipped to 0) and
+         just outside (not queued) the bounding-circle test;
+      d  shifted by 0.8 of the length along the gt's long axis: a real overlap whose centre distance is beyond HALF the reach, so a
+         circle test with too small a radius loses it;
+    and four ordinary copies (tight, tight, medium, loose)."""
+    rng = np.random.default_rng(seed)
+    n_gt = 64
+    gts = np.zeros((n_gt, 7), np.float32)
+    gts[:, 0] = (np.arange(n_gt) % 8 - 3.5) * 40.0 + rng.uniform(-2, 2, n_gt)
+    gts[:, 1] = (np.arange(n_gt) // 8 - 3.5) * 40.0 + rng.uniform(-2, 2, n_gt)
+    gts[:, 2] = rng.uniform(-1.2, -0.8, n_gt)
+    gts[:, 3:6] = np.array([3.9, 1.6, 1.5]) * rng.uniform(0.9, 1.1, (n_gt, 3))
+    gts[:, 6] = rng.uniform(-3.1, 3.1, n_gt)
+    props, kind, own = [], [], []
+
+    def add(p, k, g):
+        props.append(np.asarray(p, np.float32))
+        kind.append(k)
+        own.append(g)
+    for g in range(n_gt):
+        gt = gts[g]
+        top = np.float32(gt[2] + gt[5])                                # the gt's top face as the kernel computes it
+        p = gt.copy()
+        p[2] = top
+        add(p, 'a', g)
+        p = gt.copy()
+        p[2] = top
+        for _ in range(int(rng.integers(1, 9))):
+            p[2] = np.nextafter(p[2], np.float32(-np.inf))
+        add(p, 'b', g)
+        ra = np.float32(gt[3] + gt[4])
+        bound = float((np.float32(0.5) * (ra + ra) + np.float32(1e-2)) ** 2 * np.float32(1.0001))
+        for k, f in (('c_in', 1.0 - 5e-4), ('c_out', 1.0 + 5e-4)):
+            t = rng.uniform(0, 2 * np.pi)
+            d = math.sqrt(bound * f)
+            p = gt.copy()
+            p[0] += d * math.cos(t)
+            p[1] += d * math.sin(t)
+            add(p, k, g)
+        p = gt.copy()                                                  # the rectangle turns clockwise by yaw (rbox::obox_make)
+        p[0] += 0.8 * gt[3] * math.cos(gt[6])
+        p[1] -= 0.8 * gt[3] * math.sin(gt[6])
+        add(p, 'd', g)
+        for regime in ('tight', 'tight', 'medium', 'loose'):
+            add(_jitter(rng, gt, regime), regime, g)
+    order = rng.permutation(len(props))
+    props, kind, own = np.stack(props)[order], np.asarray(kind)[order], np.asarray(own)[order]
+    sample = (torch.from_numpy(props), torch.zeros(len(props), dtype=torch.int64), torch.from_numpy(gts), torch.zeros(n_gt, dtype=torch.int64))
+
+    def check(out, infos):
+        d2, bound, ov_h = pair_terms_np(props, gts)
+        may = may_overlap_np(props, gts)
+        rows = np.arange(len(props))
+        d2, bound, ov_h, mine = d2[rows, own], bound[rows, own], ov_h[rows, own], may[rows, own]
+        iou = amd.bbox_overlaps_3d(sample[0], sample[2]).numpy()
+        assert not may[iou > 0].size or may[iou > 0].all()             # the cheap tests exclude pairs of IoU 0 only
+        assert (may.sum(1) <= 1).all()                                 # the gts are far apart: nobody meets a second one
+        own_iou = iou[rows, own]
+        inside = d2 <= bound
+        near = np.abs(d2.astype(np.float64) / bound.astype(np.float64) - 1.0) < 1e-3
+        a = (kind == 'a') & inside & (ov_h == 0) & ~mine & (own_iou == 0)
+        b = (kind == 'b') & inside & (ov_h > 0) & (ov_h < 1e-6) & mine & (own_iou > 0) & (own_iou < 1e-6)
+        c_in = (kind == 'c_in') & near & inside & mine & (own_iou == 0)
+        c_out = (kind == 'c_out') & near & ~inside & ~mine & (own_iou == 0)
+        half = (np.float32(0.25) * (_lite_np(props)['ra'] + _lite_np(gts)['ra'][own])) ** 2
+        d = (kind == 'd') & (d2 > half) & mine & (own_iou > 0.05)
+        FACTS['boundary_pairs'] = dict(a=int(a.sum()), b=int(b.sum()), c_in=int(c_in.sum()), c_out=int(c_out.sum()), d=int(d.sum()),
+                                       queued=int(may.sum()))
+        # b and d reach the outputs: a proposal whose only overlap is lost would come out with max_overlap 0
+        mo = out['max_overlaps'].numpy()
+        return min(a.sum(), b.sum(), c_in.sum(), c_out.sum(), d.sum()) >= 32 and (mo[b] > 0).all() and (mo[d] > 0.05).all() \
+            and (mo[a | c_in | c_out] == 0).all()
+    return sample, check
+
+
+def make_tiny_batch(seed, B):
+    """B samples of 0..5 proposals on 0..2 gts"""
+    rng = np.random.default_rng(seed)
+    return [make_sample(1000 + b, mixed(int(rng.integers(0, 6))), int(rng.integers(0, 3))) for b in range(B)]
+
+
+LIMIT_THRS = (0.55, 0.5, 0.4, 0.3, 0.2, 0.1, 0.05, 0.01)
+LIMIT_FRACS = (0.02, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1, 0.38)      # the first piece comes up short and carries; every piece then takes
+
+
+@functools.lru_cache(maxsize=None)
+def clamped_call():
+    """a stacked call whose counts pass the limits: sample 0 has 4100 proposals and 1030 gts, sample 1 65 on 5.  Returns the stacked
+    operands with the counts [4100, 65] / [1030, 5], and the restatement of the case the kernel must make of it: rows [:4096] and
+    [:1024] of sample 0, its keys cut alike.  Shared, never modified."""
+    big, small = make_sample(51, mixed(4100), 1030), make_sample(52, mixed(65), 5)
+    full = _case([big, small], SHIPPED, _sampler(128), 43)
+    cut = dict(full, proposals=[big[0][:4096], small[0]], proposal_labels=[big[1][:4096], small[1]], gt_bboxes=[big[2][:1024], small[2]],
+               gt_labels=[big[3][:1024], small[3]], keys=torch.cat([full['keys'][:4096], full['keys'][4100:]]))
+    want, infos = restate(cut)
+    # the surplus rows would matter if they took part: a proposal past 4096 is a tight copy of a gt, a kept proposal belongs to a gt past 1024
+    surplus = amd.bbox_overlaps_3d(big[0][4096:], big[2][:1024]).max(1).values
+    lost = amd.bbox_overlaps_3d(big[0][:4096], big[2][1024:]).max(1).values
+    assert infos[0]['n_pos'] > 64 and infos[1]['n_pos'] > 0 and infos[1]['n_neg'] > 0 and (surplus > 0.55).any() and (lost > 0.55).any()
+    return full, want
+
+
 def _case(samples, assigner, sampler, seed, keys=None):
     g = torch.Generator().manual_seed(seed)
     n = sum(s[0].shape[0] for s in samples)
@@ -328,13 +535,58 @@ def _build(name):
         s = make_sample(22, [('tight', 40), ('medium', 60), ('loose', 60), ('far', 40)], 7)
         return _case([s], SHIPPED, _sampler(8), 15, keys=torch.full((200,), 0.5)), \
             lambda out, infos: infos[0]['n_pos'] > 4 and infos[0]['pieces'][0] > infos[0]['takes'][0] > 0
+    if name in ('dense_two_rounds', 'dense_three_rounds', 'dense_2049', 'dense_4096'):
+        n, n_gt, dup, seed = dict(dense_two_rounds=(1024, 8, True, 31), dense_three_rounds=(1024, 12, False, 32), dense_2049=(2049, 6, True, 31),
+                                  dense_4096=(4096, 3, False, 31))[name]
+        case = _case([make_dense(seed, n, n_gt, dup=dup)], SHIPPED, _sampler(128), 40)
+        if name == 'dense_two_rounds':
+            return case, _dense_check(name, case, lambda q: len(q) == 1 and WL_CAP < q[0] <= 2 * WL_CAP, dup=True)
+        if name == 'dense_three_rounds':
+            return case, _dense_check(name, case, lambda q: len(q) == 1 and q[0] > 2 * WL_CAP)
+        if name == 'dense_2049':      # two full chunks of two rounds each, and ONE proposal in the third
+            return case, _dense_check(name, case, lambda q: len(q) == 3 and q[0] > WL_CAP and q[1] > WL_CAP and 0 < q[2] <= 6, dup=True)
+        full = _dense_check(name, case, lambda q: len(q) == 4 and min(q) > CHUNK)      # four full chunks, the sort at 4096 entries
+        return case, lambda out, infos: full(out, infos) and infos[0]['n_pos'] > 64 and out['pos_batch_cnt'][0] == 64
+    if name == 'limits':      # MAX_PROPS, MAX_GTS, MAX_CLASSES, MAX_NUM and MAX_PIECES at once
+        case = _case([make_sample(50, mixed(4096), 1024, C=16)], [_assigner(0.55, 0.55, 0.55)] * 16,
+                     _sampler(1024, fractions=LIMIT_FRACS, thrs=LIMIT_THRS), 42)
+
+        def check(out, infos):
+            i = infos[0]
+            FACTS[name] = dict(n_pos=i['n_pos'], pieces=i['pieces'], takes=i['takes'], carried=i['carried'], fill=i['fill'],
+                               to_gt_1024=int((out['gt_inds'] == 1024).sum()), queued=queued_pairs([case[k][0] for k in (
+                                   'proposals', 'proposal_labels', 'gt_bboxes', 'gt_labels')], 16))
+            return i['n_pos'] >= 512 and out['pos_batch_cnt'][0] == 512 and min(i['pieces']) > 0 and min(i['takes']) > 0 \
+                and max(i['carried']) > 0 and (out['gt_inds'] == 1024).any() and len(set(case['gt_labels'][0].tolist())) == 16
+        return case, check
+    if name == 'num1024_fill_last':
+        def check(out, infos):
+            FACTS[name] = dict(fill=infos[0]['fill'], fill_from=infos[0]['fill_from'])
+            return infos[0]['fill'] > 900 and infos[0]['fill_from'] == 'last' and out['roi_batch_cnt'][0] == 1024
+        return _case([make_sample(23, [('tight', 40), ('far', 30)], 5)], SHIPPED, _sampler(1024), 16), check
+    if name == 'num1024_fill_chosen':
+        def check(out, infos):
+            FACTS[name] = dict(fill=infos[0]['fill'], fill_from=infos[0]['fill_from'])
+            return infos[0]['fill'] > 900 and infos[0]['fill_from'] == 'chosen' and infos[0]['pieces'][1] == 0 and out['roi_batch_cnt'][0] == 1024
+        return _case([make_sample(19, [('tight', 6), ('medium', 12)], 4)], [_assigner(0.6, 0.6, 0.6)] * 3, _sampler(1024, thrs=(0.6, 0.1)), 17), check
+    if name == 'b1024_tiny':      # MAX_SAMPLES
+        def check(out, infos):
+            FACTS[name] = dict(no_roi=int((out['roi_batch_cnt'] == 0).sum()), with_fill=sum(i['fill'] > 0 for i in infos),
+                               rows=int(out['roi_batch_cnt'].sum()))
+            return FACTS[name]['no_roi'] >= 100 and FACTS[name]['with_fill'] >= 100 and out['roi_batch_cnt'].numel() == 1024
+        return _case(make_tiny_batch(5, 1024), SHIPPED, _sampler(8), 18), check
+    if name == 'boundary_pairs':
+        sample, check = make_boundary(24)
+        return _case([sample], SHIPPED, _sampler(128), 19), check
     raise KeyError(name)
 
 
 CASES = ('b1_512_33', 'b3_middle_empty', 'b1_1025_65', 'b4_tiny', 'b3_num8', 'single_assigner', 'stray_labels', 'more_positives_than_npos',
          'no_negatives', 'hard_piece_empty', 'last_piece_short', 'last_piece_empty', 'rpn_style_ignored', 'low_quality_all',
-         'low_quality_first', 'equal_keys')
-SANITIZED = ('b3_middle_empty', 'last_piece_short', 'low_quality_all')     # the driver of tests/hostmath/roi_sample_sanitize.cpp runs these
+         'low_quality_first', 'equal_keys', 'dense_two_rounds', 'dense_three_rounds', 'dense_2049', 'dense_4096', 'limits', 'num1024_fill_last',
+         'num1024_fill_chosen', 'b1024_tiny', 'boundary_pairs')
+NEW_CASES = CASES[16:]
+SANITIZED = ('b3_middle_empty', 'last_piece_short', 'low_quality_all', 'dense_two_rounds', 'limits')     # the driver of tests/hostmath/roi_sample_sanitize.cpp runs these
 
 
 @functools.lru_cache(maxsize=None)

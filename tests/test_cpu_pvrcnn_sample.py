@@ -1,7 +1,7 @@
 """PV-RCNN's RoI assign-and-sample stage through the `_cpu` twins (csrc/roi_sample_cpu.cpp): `bbox_overlaps_3d` against an fp64
 evaluation of the same boxes, `pvrcnn_assign_and_sample` EQUAL to the plain-torch restatement of tests/pvrcnn_sample_ref.py on every
-case in the list, the stacked and the padded stacked form, hostile values, the default keys, the wrapper's refusals, and the twin's
-source under ASan + UBSan as a stand-alone program.  tests/test_gpu_pvrcnn_sample.py runs the same checks on the MI355X."""
+case in the list, the stacked and the padded stacked form, device counts past the limits, the cheap overlap tests against the full
+sequence, hostile values, the default keys, the wrapper's refusals, and the twin's source under ASan + UBSan as a stand-alone program.  tests/test_gpu_pvrcnn_sample.py runs the same checks on the MI355X."""
 import os
 import subprocess
 
@@ -112,10 +112,21 @@ def hostile_case(base):
     return case
 
 
+HOSTILE = ('b1_512_33', 'last_piece_short', 'dense_three_rounds')
+
+
+def same_bits(a, b):
+    """equal as bit patterns: NaN rows of a hostile proposal are copied into the outputs"""
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a,
+                                                                     b.view(torch.int32) if b.dtype == torch.float32 else b)
+
+
 def check_hostile(dev):
     """NaN / negative / infinite boxes and NaN / out-of-range keys: counts within [0, num], indices within their sample, every row of
-    its stratum; on the small case the fill with replacement runs on the hostile fill keys"""
-    for base in ('b1_512_33', 'last_piece_short'):
+    its stratum; on the small case the fill with replacement runs on the hostile fill keys, on the dense one the NaN rows (which
+    pass both cheap tests with every gt) go through three rounds of the pair queue.  Returns the outputs by case."""
+    outs = {}
+    for base in HOSTILE:
         case = hostile_case(base)
         out = run_package(case, dev=dev)
         num, n, ng = 128, case['proposals'][0].shape[0], case['gt_bboxes'][0].shape[0]
@@ -125,10 +136,55 @@ def check_hostile(dev):
         assert ((out['gt_inds'] >= -1) & (out['gt_inds'] <= ng)).all() and not torch.isnan(out['max_overlaps']).any()
         assert ((out['pos_assigned_gt_inds'] >= 0) & (out['pos_assigned_gt_inds'] < ng)).all()
         assert (out['gt_inds'][out['inds'][:pos]] > 0).all() and (out['gt_inds'][out['inds'][pos:rows]] == 0).all()
+        outs[base] = out
+    return outs
 
 
 def test_hostile_values_stay_in_bounds():
-    check_hostile('cpu')
+    outs = check_hostile('cpu')
+    case = hostile_case('dense_three_rounds')        # the situation: the hostile rows leave the queue fuller than the clean case does
+    q = ref.queued_pairs([case[k][0] for k in ('proposals', 'proposal_labels', 'gt_bboxes', 'gt_labels')], 3)
+    assert q[0] > 2 * ref.WL_CAP and outs['dense_three_rounds']['pos_batch_cnt'][0] == 64
+
+
+def check_clamped(dev):
+    """device counts past the limits: 4100 proposals on 1030 gts in sample 0, 65 on 5 in sample 1.  Every sampled output equals the
+    restatement of rows [:4096] on gts [:1024]; rows 4096..4099 are of no sample's assignment (-1 / -1 / 0); sample 1 starts after
+    ALL of sample 0's rows and comes out as the restatement has it.  Returns the outputs."""
+    full, want = ref.clamped_call()
+    pc = torch.tensor([4100, 65], dtype=torch.int32, device=dev)
+    gc = torch.tensor([1030, 5], dtype=torch.int32, device=dev)
+    cat = lambda k: torch.cat(full[k]).to(dev)
+    out = amd.pvrcnn_assign_and_sample(cat('proposals'), cat('proposal_labels'), cat('gt_bboxes'), cat('gt_labels'), full['assigner'],
+                                       full['sampler'], prop_batch_cnt=pc, gt_batch_cnt=gc, keys=full['keys'].to(dev),
+                                       fill_keys=full['fill_keys'].to(dev), return_assignment=True)
+    out = {k: v.cpu() for k, v in out.items()}
+    for k in INT_KEYS + ROW_KEYS:
+        g = out[k]
+        if k in ('gt_inds', 'labels', 'max_overlaps'):
+            assert (g[4096:4100] == (0 if k == 'max_overlaps' else -1)).all(), k
+            g = torch.cat([g[:4096], g[4100:]])
+        assert g.dtype == want[k].dtype and torch.equal(g, want[k]), k
+    rows = out['roi_batch_cnt'].tolist()
+    assert rows[0] == 128 and rows[1] > 0 and (out['rois'][128:128 + rows[1], 0] == 1).all() and (out['inds'][:128] < 4096).all()
+    assert (out['pos_assigned_gt_inds'][:int(out['pos_batch_cnt'][0])] < 1024).all()
+    return out
+
+
+def test_device_counts_past_the_limits_are_clamped():
+    check_clamped('cpu')
+
+
+@pytest.mark.parametrize('name', ['dense_two_rounds', 'dense_three_rounds', 'dense_2049', 'dense_4096', 'boundary_pairs'])
+def test_cheap_tests_exclude_only_pairs_without_overlap(name):
+    """the header's claim about `may_overlap`, on the twin (which never takes the shortcut): a pair the numpy restatement of the
+    two cheap tests excludes has a cleaned IoU of exactly 0 in the full sequence"""
+    case, _, _ = ref.reference(name)
+    props, gts = case['proposals'][0], case['gt_bboxes'][0]
+    may = torch.from_numpy(ref.may_overlap_np(props.numpy(), gts.numpy()))
+    iou = amd.bbox_overlaps_3d(props, gts)
+    assert (~may).any() and may.any() and not (iou[~may] > 0).any()
+    print(name, ref.FACTS[name])
 
 
 def check_default_keys(dev):

@@ -1,7 +1,10 @@
 """PV-RCNN's RoI assign-and-sample stage on the MI355X (csrc/roi_sample.hip): the cases of tests/pvrcnn_sample_ref.py on cuda:0.  The
 pairwise IoU within the fp64 bound and bit-identical to the `_cpu` twin; every output of `pvrcnn_assign_and_sample` EQUAL to the
-restatement and to the twin in the list, stacked and padded forms; every output element written and nothing beyond; hostile values;
-default keys; and proposals -> sampled RoIs -> targets -> losses -> gradients captured in one graph."""
+restatement and to the twin in the list, stacked and padded forms — among them the cases that take two and three rounds of the
+pair queue, two to four chunks of proposals, every limit at once and pairs on the edges of the cheap overlap tests; device counts
+past the limits; every output element written and nothing beyond; hostile values, the same bits as the twin; default keys;
+proposals -> sampled RoIs -> targets -> losses -> gradients captured in one graph; and a graph captured on one queue round
+replayed on three."""
 import pytest
 import torch
 
@@ -9,7 +12,8 @@ import mmdet3d_gaussian_amd as amd
 import pvrcnn_sample_ref as ref
 import pvrcnn_train_ref as train_ref
 from mmdet3d_gaussian_amd import _host, _lib, pvrcnn_sample
-from test_cpu_pvrcnn_sample import (PAD_P, check_default_keys, check_equal, check_hostile, check_iou_values, run_package)
+from test_cpu_pvrcnn_sample import (INT_KEYS, PAD_P, ROW_KEYS, check_clamped, check_default_keys, check_equal, check_hostile, check_iou_values,
+                                    run_package, same_bits)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -35,7 +39,8 @@ def test_device_equals_the_restatement_and_the_twin(name):
     check_equal(run_package(case, dev=DEV, form='padded'), want, padded=True)
 
 
-@pytest.mark.parametrize('name', ['b4_tiny', 'b3_middle_empty', 'b1_1025_65'])     # 1, 65 and 1025 proposals
+# 1, 65 and 1025 proposals; three rounds of the pair queue; 4096 proposals on 1024 gts with num = 1024
+@pytest.mark.parametrize('name', ['b4_tiny', 'b3_middle_empty', 'b1_1025_65', 'dense_three_rounds', 'limits'])
 def test_every_output_element_is_written(name):
     """the C entry point on sentinel-filled outputs with a guard row either side: every row is written — the rows past the counts'
     sums as batch id -1 and zeros, the scratch in full — and nothing beyond the arrays"""
@@ -74,7 +79,17 @@ def test_every_output_element_is_written(name):
 
 
 def test_hostile_values_stay_in_bounds():
-    check_hostile(DEV)
+    """in bounds, and bit for bit what the twin makes of the same hostile values"""
+    dev, twin = check_hostile(DEV), check_hostile('cpu')
+    for base in dev:
+        for k in INT_KEYS + ROW_KEYS:
+            assert same_bits(dev[base][k], twin[base][k]), (base, k)
+
+
+def test_device_counts_past_the_limits_are_clamped():
+    dev, twin = check_clamped(DEV), check_clamped('cpu')
+    for k in dev:
+        assert torch.equal(dev[k], twin[k]), k
 
 
 def test_default_keys_follow_the_seed():
@@ -144,6 +159,50 @@ def test_whole_chain_under_graph_capture():
     alone = amd.pvrcnn_head_loss(train_ref.LOSS_CLS, train_ref.LOSS_BBOX, x[:rows], p[:rows], eager[0][:rows], *tg)
     for k, v in zip(train_ref.LOSS_KEYS, eager[14:17]):
         assert torch.allclose(alone[k], v, rtol=1e-5, atol=1e-7), k
+
+
+def test_graph_replay_into_more_queue_rounds():
+    """static buffers of the size of `dense_three_rounds`, captured while they hold a sparse sample (300 proposals on 5 gts: one
+    round of the pair queue), replayed after the dense proposals, gts, counts and keys are copied in (three rounds): the round count
+    is data the kernel reads, not something the capture froze.  The replay equals the eager call and the restatement bit for bit."""
+    case, want, _ = ref.reference('dense_three_rounds')
+    sparse = ref.make_sample(60, ref.mixed(300), 5, C=1)
+    assert max(ref.queued_pairs(sparse, 3)) < ref.WL_CAP
+    n, g = case['proposals'][0].shape[0], case['gt_bboxes'][0].shape[0]
+    props, plab = torch.zeros(n, 7, device=DEV), torch.zeros(n, dtype=torch.int64, device=DEV)
+    gts, glab = torch.zeros(g, 7, device=DEV), torch.zeros(g, dtype=torch.int64, device=DEV)
+    props[:300], plab[:300], gts[:5], glab[:5] = (t.to(DEV) for t in sparse)
+    pc, gc = torch.tensor([300], dtype=torch.int32, device=DEV), torch.tensor([5], dtype=torch.int32, device=DEV)
+    keys, fill = case['keys'].to(DEV).flip(0), case['fill_keys'].to(DEV).flip(0)
+    names = INT_KEYS + ROW_KEYS
+
+    def step():
+        out = amd.pvrcnn_assign_and_sample(props, plab, gts, glab, case['assigner'], case['sampler'], prop_batch_cnt=pc, gt_batch_cnt=gc,
+                                           keys=keys, fill_keys=fill, return_assignment=True)
+        return [out[k] for k in names]
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        first = [t.clone() for t in step()]                # warm-up outside the capture
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        captured = step()
+    props.copy_(case['proposals'][0])
+    plab.copy_(case['proposal_labels'][0])
+    gts.copy_(case['gt_bboxes'][0])
+    glab.copy_(case['gt_labels'][0])
+    pc.fill_(n)
+    gc.fill_(g)
+    keys.copy_(case['keys'])
+    fill.copy_(case['fill_keys'])
+    graph.replay()
+    torch.cuda.synchronize()
+    eager = step()
+    assert int(first[names.index('roi_batch_cnt')][0]) > 0 and not torch.equal(first[names.index('inds')], eager[names.index('inds')])
+    for k, got, exp in zip(names, captured, eager):
+        assert torch.equal(got, exp) and torch.equal(got.cpu(), want[k]), k
 
 
 def test_roi_grid_queries_on_the_padded_rows():
