@@ -880,6 +880,53 @@ int gd3d_roi_assign_sample_cpu(const float* proposals, const int64_t* proposal_l
                                int64_t* pos_assigned_gt_inds, int32_t* pos_batch_cnt, int32_t* roi_batch_cnt,
                                int64_t* gt_inds, float* max_overlaps, int64_t* labels, int32_t* stage);
 
+/* ------------------------------------------------------------------------------------
+ * The keypoint segmentation slice (an addition inside ABI 6): PointwiseMaskHead.loss
+ * (models/roi_heads/mask_heads/pointwise_mask_head.py:124-144) — the loss and its gradient — as one launch of one workgroup, and
+ * the keypoint reweighting of PVRCNNROIHead._bbox_forward (models/roi_heads/pvrcnn_roi_head.py:211-212), forward and backward, as
+ * one streaming launch each.  No workspace, no atomics on floats, no read-back: the same inputs give the same bits on every run.
+ * mmdet's FocalLoss is third party, absent and not pinned by the reference: the math below (mmdet 2.x's published
+ * py_sigmoid_focal_loss, reduction 'sum') is what is computed.
+ *
+ * gd3d_seg_head_loss : seg_preds (N,K) fp32, seg_targets (N) int64 = gd3d_pib_mask_targets' output (-1 ignore, 0..num_classes-1 a
+ *   class, num_classes background).  K must be 1 with class_agnostic != 0, else num_classes; 1 <= K <= 255; gamma >= 0;
+ *   0 <= alpha <= 1 (GD3D_E_BADARG); N <= 2^24 (GD3D_E_TOOLARGE; correct, but one workgroup: not meant to be fast beyond ~10^5).
+ *   Per row i with c = seg_targets[i]:  pos = [0 <= c < num_classes], neg = [c == num_classes], n_pos = sum pos,
+ *   w = (pos + neg) / max(n_pos, 1); a target above num_classes is neither: weight 0 (the reference's one_hot would raise).
+ *   The label l is pos (class agnostic) or c with ignored rows at num_classes; per column k, t = [l == k], p = sigmoid(x):
+ *     t = 1:  loss = -alpha (1-p)^gamma log p,       d/dx = alpha (1-p)^gamma (gamma p log p - (1-p))
+ *     t = 0:  loss = -(1-alpha) p^gamma log(1-p),    d/dx = (1-alpha) p^gamma (p - gamma (1-p) log(1-p))
+ *   with log p = -softplus(-x), log(1-p) = -softplus(x), softplus(x) = max(x, 0) + log1p(exp(-|x|)): finite at |x| = 100.
+ *   Class agnostic, the positives carry label 1 and K = 1, so t = [l == 0]: the one column is trained towards 1 on the
+ *   NON-positive rows — what the reference computes, restated, not repaired.
+ *   out (2) fp32: [0] loss_weight * sum_i w_i sum_k loss (fp64 sum), [1] n_pos.  grad (N,K), nullable: loss_weight * w_i * d/dx,
+ *   every element written (zeros on the rows of weight 0).  N == 0 writes out = (0, 0).
+ * gd3d_keypoint_reweight : out (N,C) = feats (N,C) * s_i, s_i = max_k sigmoid(seg_preds[i,k]) with sigmoid(x) = 1 / (1 + exp(-x))
+ *   in fp32; win (N) uint8, nullable: the winning column, the LOWEST on equal fp32 sigmoid values (as CPU torch's max(dim) routes
+ *   its gradient).  1 <= K <= 255, C >= 1 (GD3D_E_BADARG); N == 0 launches nothing.
+ * gd3d_keypoint_reweight_backward : grad_feats (N,C) = grad_out * s_i;  grad_seg (N,K): column win[i] =
+ *   (sum_c grad_out[i,c] feats[i,c]) * s_i (1 - s_i), the others 0; each nullable, each written in full.  win is the forward's.
+ *   The row sum is fp32 in a fixed order: a group of G lanes (the power of two covering ceil(C / 4), 64 at most) shares a row,
+ *   lane l adds the columns of quads l, l + G, .. in order, and the lanes fold pairwise, l with l + G/2, then G/4, .. 1.
+ *   Both reweight entry points use 16-byte accesses when C % 4 == 0 and the (N,C) base pointers are 16-byte aligned, 4-byte ones
+ *   otherwise; the results are the same bits either way.
+ * `_cpu` twins (csrc/seg_head_cpu.cpp): the same contracts on HOST memory on the calling thread; n_pos and win BIT-IDENTICAL to
+ * the kernels', the other values equal up to the two math libraries' exp / log1p / pow.
+ * ---------------------------------------------------------------------------------- */
+int gd3d_seg_head_loss(const float* seg_preds, const int64_t* seg_targets, int64_t N, int32_t K, int32_t num_classes,
+                       int32_t class_agnostic, float gamma, float alpha, float loss_weight, float* out, float* grad,
+                       void* stream);
+int gd3d_keypoint_reweight(const float* feats, const float* seg_preds, int64_t N, int64_t C, int32_t K, float* out,
+                           uint8_t* win, void* stream);
+int gd3d_keypoint_reweight_backward(const float* grad_out, const float* feats, const float* seg_preds, const uint8_t* win,
+                                    int64_t N, int64_t C, int32_t K, float* grad_feats, float* grad_seg, void* stream);
+int gd3d_seg_head_loss_cpu(const float* seg_preds, const int64_t* seg_targets, int64_t N, int32_t K, int32_t num_classes,
+                           int32_t class_agnostic, float gamma, float alpha, float loss_weight, float* out, float* grad);
+int gd3d_keypoint_reweight_cpu(const float* feats, const float* seg_preds, int64_t N, int64_t C, int32_t K, float* out,
+                               uint8_t* win);
+int gd3d_keypoint_reweight_backward_cpu(const float* grad_out, const float* feats, const float* seg_preds, const uint8_t* win,
+                                        int64_t N, int64_t C, int32_t K, float* grad_feats, float* grad_seg);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

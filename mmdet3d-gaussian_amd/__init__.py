@@ -17,6 +17,9 @@
                                  (pointwise_mask_head.py:62-92) and the RoI grid points (batch_roigrid_extractor.py:56-71)
   * ``pvrcnn_head_get_targets`` / ``pvrcnn_head_loss`` — PVRCNNBboxHead's training slice (pvrcnn_bbox_head.py:140-351): the targets
                                  in one launch, the class, box and corner losses with their gradients in one more, no host sync
+  * ``pvrcnn_seg_loss`` / ``keypoint_reweight`` — the keypoint segmentation slice: PointwiseMaskHead.loss
+                                 (pointwise_mask_head.py:124-144) with its gradient in one launch, and the keypoint reweighting of
+                                 PVRCNNROIHead._bbox_forward (pvrcnn_roi_head.py:211-212), forward and backward, one launch each
   * ``GraphedStep``            — a launch-bound loss slice, forward and backward, captured once as a hipGraph and replayed
 Everything outside §8 that earlier rounds built (frozen, DESIGN_EXTRAS.md) lives in ``mmdet3d_gaussian_amd.extras``.
 
@@ -42,6 +45,7 @@ from .points_in_boxes import (pointwise_mask_targets, points_in_boxes_all, point
                               points_in_boxes_part_stacked, roi_grid_points, roi_grid_queries)
 from .pvrcnn_train import pvrcnn_head_get_targets, pvrcnn_head_loss
 from .pvrcnn_sample import bbox_overlaps_3d, pvrcnn_assign_and_sample
+from .pvrcnn_seg import keypoint_reweight, pvrcnn_seg_loss
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
                         anchor_head_decoded_loss_fused, center_head_gd_loss, center_head_losses)
 from . import extras
@@ -63,4 +67,5 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'center_head_losses', 'Scatter', 'scatter_index', 'scatter_reduce', 'QueryAndGroup', 'ball_query', 'grouping',
            'furthest_point_sample', 'furthest_point_sample_stacked', 'points_in_boxes_part', 'points_in_boxes_all',
            'points_in_boxes_part_stacked', 'points_in_boxes_all_stacked', 'pointwise_mask_targets', 'roi_grid_points', 'roi_grid_queries',
-           'pvrcnn_head_get_targets', 'pvrcnn_head_loss', 'bbox_overlaps_3d', 'pvrcnn_assign_and_sample', 'extras']
+           'pvrcnn_head_get_targets', 'pvrcnn_head_loss', 'bbox_overlaps_3d', 'pvrcnn_assign_and_sample', 'pvrcnn_seg_loss',
+           'keypoint_reweight', 'extras']

@@ -273,6 +273,12 @@ SYMBOLS = {
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gd3d_roi_assign_sample_cpu': (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32,
                                           _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_seg_head_loss': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp]),
+    'gd3d_keypoint_reweight': (_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    'gd3d_keypoint_reweight_backward': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    'gd3d_seg_head_loss_cpu': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp]),
+    'gd3d_keypoint_reweight_cpu': (_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    'gd3d_keypoint_reweight_backward_cpu': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 
