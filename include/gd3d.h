@@ -927,6 +927,61 @@ int gd3d_keypoint_reweight_cpu(const float* feats, const float* seg_preds, int64
 int gd3d_keypoint_reweight_backward_cpu(const float* grad_out, const float* feats, const float* seg_preds, const uint8_t* win,
                                         int64_t N, int64_t C, int32_t K, float* grad_feats, float* grad_seg);
 
+/* ------------------------------------------------------------------------------------
+ * The keypoint BEV interpolation and the voxel-centre sources (an addition inside ABI 6): the statements of
+ * VoxelSetAbstraction.forward outside its MLPs that had no entry here — interpolate_from_bev_features
+ * (models/middle_encoders/voxel_set_abstraction.py:153-177), get_voxel_centers (:179-193) and the per-sample count loop
+ * (:303-305).  No workspace, no read-back.
+ *
+ * gd3d_vsa_bev_interp : out (B,M,C) fp32 contiguous = the bilinear sample of bev (B,C,H,W) fp32 at the keypoints' xy —
+ *   F.grid_sample(align_corners=True, padding_mode='zeros') on the reference's normalised grid, squeezed and permuted.
+ *   keypoints: element [b, m, d] at keypoints[b * kp_stride_b + m * kp_stride_m + d], d = 0 (x), 1 (y); nothing else is read.
+ *   layout 0: bev is contiguous NCHW; layout 1: channels last (element [b,c,y,x] at ((b*H + y)*W + x)*C + c).  The map is read
+ *   where it lies.  (tl_x, tl_y) / (br_x, br_y): the world xy of the centres of cell (0,0) / (H-1,W-1), computed by the caller.
+ *   H, W >= 2, br > tl on both axes, C >= 1, strides >= 0 (GD3D_E_BADARG); H, W <= 2^24 (GD3D_E_TOOLARGE).  B == 0 or M == 0
+ *   launches nothing.  Per keypoint, in fp32, one operation per step, no contraction, correctly rounded division:
+ *     ix = ((x - tl_x) * (float)(W - 1)) / (br_x - tl_x),  iy = ((y - tl_y) * (float)(H - 1)) / (br_y - tl_y)
+ *     reach = ix > -1 && ix < (float)W && iy > -1 && iy < (float)H      (false for NaN and +-inf: compared BEFORE any conversion)
+ *     x0 = floor(ix), y0 = floor(iy) (converted to integers only when reach);  ax = ix - x0, ay = iy - y0, bx = 1 - ax, by = 1 - ay
+ *     weights nw = bx*by, ne = ax*by, sw = bx*ay, se = ax*ay for the cells (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1)
+ *     out[c] = ((v_nw*nw + v_ne*ne) + v_sw*sw) + v_se*se, the value of a cell outside the map being 0.
+ *   Without reach (a cell or more outside, or a non-finite coordinate) the row is 0 — the reference's result for a non-finite
+ *   coordinate is unspecified: restated, not matched.  No index leaves the map for any input; offsets are 64-bit.  Channels last
+ *   with C % 4 == 0 and 16-byte aligned bev / out takes 16-byte accesses, everything else 4-byte ones: the same bits, and the same
+ *   bits for both layouts.
+ * gd3d_vsa_bev_interp_backward : grad_bev (B,C,H,W) in `layout` = sum over the keypoints of grad_out (B,M,C)[b,m,c] * weight into
+ *   the (at most four) cells in the map; EVERY element of grad_bev is written (a fill kernel zeroes it first).  fp32 atomic adds,
+ *   lanes along C: where several keypoints share a cell the last bits depend on the order of arrival.  No gradient for the
+ *   keypoints (grid_sample would return one for its grid).  Same argument checks; B == 0 launches nothing, M == 0 only the fill.
+ * gd3d_vsa_voxel_centers : coors (N,4) int32 (coors_is_int64 == 0) or int64, columns [b, z, y, x].  xyz (N,3) fp32:
+ *     xyz[i][a] = (((float)coors[i][3 - a] * voxel_size[a]) * scale + range_min[a]) + add[a],   a = 0 (x), 1 (y), 2 (z)
+ *   four fp32 operations left to right (the reference's `c * vs * scale + min` and its in-place add of (0.5*vs)*scale for 'half',
+ *   0.5*vs for 'halfmin', which the caller passes as `add`); voxel_size, range_min and add are three floats each in HOST memory,
+ *   read during the call.  xyz_batch_cnt (batch_size) int32: the rows whose b equals the index; zeroed by the entry point, then
+ *   integer adds reduced per wave: exact in any order.  A row with b outside [0, batch_size) is counted nowhere; its centre is
+ *   still written.  N == 0 writes the zero counts only.
+ * `_cpu` twins (csrc/vsa_bev_cpu.cpp): the same contracts on HOST memory on the calling thread.  The forward, xyz and the counts
+ * are BIT-IDENTICAL to the kernels'; the twin's backward is sequential (keypoints in order, neighbours nw, ne, sw, se).
+ * ---------------------------------------------------------------------------------- */
+int gd3d_vsa_bev_interp(const float* keypoints, int64_t kp_stride_b, int64_t kp_stride_m, const float* bev, int32_t layout,
+                        int64_t B, int64_t M, int64_t C, int64_t H, int64_t W, float tl_x, float tl_y, float br_x, float br_y,
+                        float* out, void* stream);
+int gd3d_vsa_bev_interp_backward(const float* grad_out, const float* keypoints, int64_t kp_stride_b, int64_t kp_stride_m,
+                                 int32_t layout, int64_t B, int64_t M, int64_t C, int64_t H, int64_t W, float tl_x, float tl_y,
+                                 float br_x, float br_y, float* grad_bev, void* stream);
+int gd3d_vsa_voxel_centers(const void* coors, int32_t coors_is_int64, int64_t N, const float* voxel_size, float scale,
+                           const float* range_min, const float* add, int32_t batch_size, float* xyz, int32_t* xyz_batch_cnt,
+                           void* stream);
+int gd3d_vsa_bev_interp_cpu(const float* keypoints, int64_t kp_stride_b, int64_t kp_stride_m, const float* bev, int32_t layout,
+                            int64_t B, int64_t M, int64_t C, int64_t H, int64_t W, float tl_x, float tl_y, float br_x,
+                            float br_y, float* out);
+int gd3d_vsa_bev_interp_backward_cpu(const float* grad_out, const float* keypoints, int64_t kp_stride_b, int64_t kp_stride_m,
+                                     int32_t layout, int64_t B, int64_t M, int64_t C, int64_t H, int64_t W, float tl_x,
+                                     float tl_y, float br_x, float br_y, float* grad_bev);
+int gd3d_vsa_voxel_centers_cpu(const void* coors, int32_t coors_is_int64, int64_t N, const float* voxel_size, float scale,
+                               const float* range_min, const float* add, int32_t batch_size, float* xyz,
+                               int32_t* xyz_batch_cnt);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

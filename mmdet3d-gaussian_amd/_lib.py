@@ -279,6 +279,12 @@ SYMBOLS = {
     'gd3d_seg_head_loss_cpu': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp]),
     'gd3d_keypoint_reweight_cpu': (_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'gd3d_keypoint_reweight_backward_cpu': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    'gd3d_vsa_bev_interp': (_int, [_vp, _i64, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp, _vp]),
+    'gd3d_vsa_bev_interp_backward': (_int, [_vp, _vp, _i64, _i64, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp, _vp]),
+    'gd3d_vsa_voxel_centers': (_int, [_vp, _i32, _i64, _vp, _f32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    'gd3d_vsa_bev_interp_cpu': (_int, [_vp, _i64, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp]),
+    'gd3d_vsa_bev_interp_backward_cpu': (_int, [_vp, _vp, _i64, _i64, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp]),
+    'gd3d_vsa_voxel_centers_cpu': (_int, [_vp, _i32, _i64, _vp, _f32, _vp, _vp, _i32, _vp, _vp]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 
