@@ -20,6 +20,8 @@ NOISE_FACTOR = 4.0         # allowed multiple of the fp32 restatement's own devi
 ULP = 2.0 ** -23           # one fp32 ulp of the tensor's largest magnitude: keeps an exactly rounded restatement from setting a bound of 0
 LOGIT_LIMIT = 6.0          # parity cases: |x| <= 6 ...
 TOP_GAP = 1e-3             # ... and every row's top two logits at least this far apart, so fp32 and fp64 pick the same column
+INT64_EXTREMES = (2 ** 40, -2 ** 63, 2 ** 63 - 1)      # seg targets no 32-bit test can hold: weightless, like every target past background
+INT64_EXTREME_ROWS = (11, 12, 13)                       # their rows in the `past_background` cases
 
 
 # ---- the restatement -------------------------------------------------------------------------------------------------------------
@@ -93,7 +95,11 @@ def _loss_case(n, agnostic, seed, kind='mixed', cfg=None):
         t = torch.randint(-1, NUM_CLASSES + 1, (n,), generator=g)
         t[::5] = 4
         t[2::7] = 7
+        for row, v in zip(INT64_EXTREME_ROWS, INT64_EXTREMES):     # rows that neither of the two strides above touches: no draw moves
+            assert row % 5 != 0 and row % 7 != 2
+            t[row] = v
         assert (t == 4).any() and (t == 7).any() and ((t >= 0) & (t < NUM_CLASSES)).any() and (t == NUM_CLASSES).any()
+        assert all((t == v).any() for v in INT64_EXTREMES)
     elif kind == 'saturated':
         t = torch.randint(-1, NUM_CLASSES + 1, (n,), generator=g)
         x = torch.tensor([30.0, -30.0, 100.0, -100.0])[torch.randint(0, 4, (n, k), generator=g)]
@@ -182,9 +188,24 @@ def _reweight_case(n, c, k, seed, kind='parity'):
     elif kind == 'saturated':
         assert k == 1
         x = torch.tensor([30.0, -30.0, 100.0, -100.0])[torch.arange(n) % 4].reshape(n, 1)
+    elif kind == 'forced_winner':
+        # the row's largest logit — gapped_logits keeps it 0.1 above the next — changes places with the value of the column the row is
+        # to pick: columns 0, K / 2 - 1, K / 2 (the first winner byte >= 128 at K = 255) and K - 1 in turn
+        assert k >= 4
+        want = torch.tensor(forced_columns(k))[torch.arange(n) % 4]
+        top = x.argmax(dim=1)
+        rows = torch.arange(n)
+        hi, lo = x[rows, top].clone(), x[rows, want].clone()
+        x[rows, top], x[rows, want] = lo, hi
+        check_gap(x)
+        assert torch.equal(x.argmax(dim=1), want) and torch.equal(x.double().argmax(dim=1), want)
     else:
         raise KeyError(kind)
     return dict(feats=feats, seg_preds=x, grad_out=grad_out)
+
+
+def forced_columns(k):
+    return (0, (k + 1) // 2 - 1, (k + 1) // 2, k - 1)
 
 
 REWEIGHT_CASES = {
@@ -198,10 +219,32 @@ REWEIGHT_CASES = {
     'exact_ties': (66, 8, 3, 'exact_ties'),
     'saturated': (64, 8, 1, 'saturated'),
 }
+# Cases added after the table above, with seeds of their own (the committed ones are indexed by sorted(REWEIGHT_CASES): they do not
+# move): name -> (N, C, K, kind, seed).
+#   The two sweeps are the smallest N at which a workgroup of reweight_kernel / reweight_backward_kernel takes a second trip of its
+#   grid-stride loop: C = 256 and C = 255 are 64 quads, so group_lanes = 64 and a workgroup of 256 threads holds 256 / 64 = 4 rows;
+#   the grid is capped at 8192 workgroups, so one sweep covers 8192 * 4 = 32768 rows and N = 32773 = 32768 + 5 leaves 5 rows to the
+#   second trip — workgroup 0 takes four, workgroup 1 one (three of its four row slots are past N: in the backward those lanes still
+#   reach the group shuffles), and every other workgroup's second trip does not start.  C = 256 takes the 16-byte path; C = 255 the
+#   4-byte path, with the last quad of every row clipped to three columns.
+#   K = 255 is the documented maximum: the winner is a byte, and columns 128 and 254 have its top bit set.
+EXTRA_REWEIGHT_CASES = {
+    'n32773_c256_k3': (32773, 256, 3, 'parity', 2501),
+    'n32773_c255_k1': (32773, 255, 1, 'parity', 2502),
+    'n130_c8_k255': (130, 8, 255, 'forced_winner', 2503),
+}
+SWEEP_CASES = ('n32773_c256_k3', 'n32773_c255_k1')
+SWEEP_CAP, SWEEP_ROWS = 8192, 4                   # reweight_grid's cap and RW_BLOCK / group_lanes(C) of both sweep cases
+for _name in SWEEP_CASES:
+    assert EXTRA_REWEIGHT_CASES[_name][0] > SWEEP_CAP * SWEEP_ROWS and (EXTRA_REWEIGHT_CASES[_name][1] + 3) // 4 >= 64
+ALL_REWEIGHT_CASES = sorted(REWEIGHT_CASES) + list(EXTRA_REWEIGHT_CASES)
 MISALIGNED_OF = 'n130_c128_k3'                    # `misaligned_base`: this case's operands viewed one float into a larger buffer
 
 
 def make_reweight(name):
+    if name in EXTRA_REWEIGHT_CASES:
+        n, c, k, kind, seed = EXTRA_REWEIGHT_CASES[name]
+        return _reweight_case(n, c, k, seed, kind)
     n, c, k, kind = REWEIGHT_CASES[name]
     return _reweight_case(n, c, k, 2000 + sorted(REWEIGHT_CASES).index(name), kind)
 

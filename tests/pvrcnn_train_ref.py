@@ -272,6 +272,178 @@ def tie_margins(name, clockwise):
     return float((d1 - d2).abs().min()), float(torch.minimum(d1, d2).min())
 
 
+# ---- scattered positives: the loss kernel's positive-row scan ---------------------------------------------------------------------
+# `draw` puts a sample's positives first, and so does targets_kernel: every mask the cases above hand to the loss is two or three
+# contiguous runs.  Here the rows of a drawn case are permuted so that its P positives land on chosen slots, in their order (target
+# row j stays with the j-th positive): loss_kernel's rank — a ballot and popcount inside the wave, the waves' totals through LDS, a
+# running offset across its chunks of 1024 rows — is then checked against the restatement's boolean indexing.
+
+LOSS_INPUT_KEYS = ('cls_score', 'bbox_pred', 'rois', 'label', 'bbox_targets', 'pos_gt_bboxes', 'reg_mask', 'label_weights', 'bbox_weights')
+ROW_KEYS = ('cls_score', 'bbox_pred', 'rois', 'label', 'reg_mask', 'label_weights', 'bbox_weights')     # (R, ...) operands: permuted together
+LOSS_VALUE_KEYS = ('grad_cls', 'grad_bbox')
+
+
+def slot_candidates(R, pattern):
+    """the rows a pattern may make positive"""
+    rows = torch.arange(R)
+    if pattern in ('random', 'all_positive', 'random_head'):
+        return rows[:R - R // 5] if pattern == 'random_head' else rows      # random_head: the last fifth stays free (the mismatch tests)
+    if pattern == 'odd_lanes':                                                # interleaved inside every wave
+        return rows[rows % 2 == 1]
+    if pattern == 'odd_waves':                                                # only the odd waves of every chunk of 1024 rows
+        return rows[(rows % 1024) // 64 % 2 == 1]
+    if pattern == 'from_1024':                                                # the first chunk is empty: the running offset starts at 0 for chunk 2
+        return rows[rows >= 1024]
+    if pattern == 'last64_and_2048':                                          # the last wave of the second chunk, and the one row of the third
+        return torch.cat([rows[1984:2048], rows[2048:2049]])
+    raise KeyError(pattern)
+
+
+# (R, pattern) -> case id.  R = 2049 is three chunks (1024 + 1024 + 1); R = 65 one chunk of two waves, where only the patterns that
+# need no second chunk exist.
+SCATTER_CASES = {f'r{R}_{pattern}': (R, pattern)
+                 for R, patterns in ((2049, ('random', 'odd_lanes', 'odd_waves', 'from_1024', 'last64_and_2048', 'all_positive')),
+                                     (65, ('random', 'odd_lanes', 'odd_waves', 'all_positive')))
+                 for pattern in patterns}
+MISMATCH_BASES = {'r2049_random_head': (2049, 'random_head'), 'r65_random_head': (65, 'random_head')}
+SCATTER_ALL = {**SCATTER_CASES, **MISMATCH_BASES}
+SCATTER_SEEDS = {name: 7000 + 2 * k for k, name in enumerate(SCATTER_ALL)}      # a scheme of its own: SEEDS above does not move
+
+
+def choose_slots(R, pattern, g):
+    """the sorted rows that become positive: every candidate for the patterns that say so, else a random 3 in 10 of the rows (at least
+    one, at most the candidates)"""
+    cand = slot_candidates(R, pattern)
+    if pattern in ('all_positive', 'last64_and_2048') or cand.numel() <= 2:
+        return cand
+    P = max(1, min(cand.numel(), (3 * R) // 10))
+    return cand[torch.randperm(cand.numel(), generator=g)[:P]].sort().values
+
+
+def scatter(inputs, targets, slots):
+    """the loss operands of a drawn case (`inputs` of `draw`, `targets` of `get_targets` on it) with their R rows permuted: the
+    positives — in their order — onto the sorted rows `slots`, the others — in theirs — onto the rows left -> dict over LOSS_INPUT_KEYS"""
+    _, _, _, rois, cls_score, bbox_pred = inputs
+    label, bbox_targets, pos_gt_bboxes, reg_mask, label_weights, bbox_weights = targets
+    R = rois.size(0)
+    positive = reg_mask > 0
+    assert slots.numel() == int(positive.sum()) == bbox_targets.size(0) and torch.equal(slots, slots.unique())
+    taken = torch.zeros(R, dtype=torch.bool)
+    taken[slots] = True
+    src = torch.empty(R, dtype=torch.int64)
+    src[taken] = torch.arange(R)[positive]                 # boolean assignment goes in row order: the j-th slot takes the j-th positive
+    src[~taken] = torch.arange(R)[~positive]
+    rows = dict(cls_score=cls_score, bbox_pred=bbox_pred, rois=rois, label=label, reg_mask=reg_mask, label_weights=label_weights,
+                bbox_weights=bbox_weights)
+    out = {k: v[src].contiguous() for k, v in rows.items()}
+    out.update(bbox_targets=bbox_targets, pos_gt_bboxes=pos_gt_bboxes)
+    assert torch.equal(torch.arange(R)[out['reg_mask'] > 0], slots)
+    assert torch.equal(out['bbox_pred'][slots], bbox_pred[positive])          # target row j still belongs to the j-th positive
+    return out
+
+
+def make_scattered(name):
+    """the scattered loss operands of case `name`, fp32: a fresh draw of one sample of R RoIs, P = the pattern's slots, its targets from
+    the fp32 restatement"""
+    R, pattern = SCATTER_ALL[name]
+    g = torch.Generator().manual_seed(SCATTER_SEEDS[name] + 1)
+    slots = choose_slots(R, pattern, g)
+    inputs = draw(((R, slots.numel()),), SCATTER_SEEDS[name])
+    pos, gts, ious = inputs[:3]
+    case = scatter(inputs, get_targets(pos, gts, ious, CFG), slots)
+    case['drawn'] = (pos, gts)               # for the generator's margins, which a permutation of rows leaves as they are
+    return case
+
+
+def evaluate_loss(case, dtype, with_corner_loss=True):
+    """`loss` of the restatement on loss operands in `dtype` -> the losses and the gradients of their sum"""
+    cast = lambda t: t.to(dtype) if t.dtype.is_floating_point else t      # noqa: E731
+    x = cast(case['cls_score']).clone().requires_grad_(True)
+    p = cast(case['bbox_pred']).clone().requires_grad_(True)
+    losses = loss(x, p, cast(case['rois']), cast(case['label']), cast(case['bbox_targets']), cast(case['pos_gt_bboxes']), case['reg_mask'],
+                  cast(case['label_weights']), cast(case['bbox_weights']), with_corner_loss=with_corner_loss)
+    sum(losses.values()).backward()
+    out = {k: v.detach() for k, v in losses.items()}
+    out['grad_cls'] = x.grad
+    out['grad_bbox'] = p.grad if p.grad is not None else torch.zeros_like(p)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def scattered_reference(name):
+    """(loss operands, fp32 restatement, fp64 restatement) of a scattered case, computed once and shared (never modify the tensors)"""
+    case = make_scattered(name)
+    return case, evaluate_loss(case, torch.float32), evaluate_loss(case, torch.float64)
+
+
+def scattered_margins(case):
+    """`tie_margins` for loss operands: on their fp64 decode, over every corner of every paired positive"""
+    pos_inds = case['reg_mask'] > 0
+    pred = decode_positive(case['rois'].double()[:, 1:][pos_inds], case['bbox_pred'].double()[pos_inds])
+    d1, d2 = corner_distances(pred, case['pos_gt_bboxes'].double()[:pred.size(0)])
+    return float((d1 - d2).abs().min()), float(torch.minimum(d1, d2).min())
+
+
+def loss_bounds(r32, r64):
+    """`bounds` for the two gradients of a loss-only evaluation: key -> (the fp32 restatement's deviation, NOISE_FACTOR times it)"""
+    out = {}
+    for k in LOSS_VALUE_KEYS:
+        dev = float((r32[k].double() - r64[k]).abs().max()) if r64[k].numel() else 0.0
+        out[k] = (dev, NOISE_FACTOR * dev)
+    return out
+
+
+def with_mask_values(case):
+    """the same operands with a mask that is not 0 / 1: positives carry 1, 2, 7 in turn, every third other row -1 (the rule is > 0)"""
+    out = dict(case)
+    mask = case['reg_mask'].clone()
+    pos = torch.arange(mask.numel())[mask > 0]
+    rest = torch.arange(mask.numel())[mask <= 0]
+    mask[pos] = torch.tensor([1, 2, 7])[torch.arange(pos.numel()) % 3]
+    mask[rest[::3]] = -1
+    assert torch.equal(mask > 0, case['reg_mask'] > 0) and (mask == 7).any() == (pos.numel() >= 3) and ((mask == -1).any() or rest.numel() == 0)
+    out['reg_mask'] = mask
+    return out
+
+
+def with_extra_positives(case, n):
+    """n more mask positives than target rows, all after the P-th positive in row order -> (operands, the extra rows)"""
+    mask = case['reg_mask'].clone()
+    last = int(torch.arange(mask.numel())[mask > 0].max())
+    free = torch.arange(mask.numel())[last + 1:]
+    assert free.numel() >= 2 * n
+    extra = free[::2][:n]                                    # every other row past the last positive
+    mask[extra] = 1
+    out = dict(case)
+    out['reg_mask'] = mask
+    assert int((mask > 0).sum()) == case['bbox_targets'].size(0) + n
+    return out, extra
+
+
+def with_fewer_positives(case, n):
+    """the last n mask positives cleared; the target buffers keep their P rows -> (operands, the operands the restatement takes: the
+    targets cut to P - n rows, the cleared rows)"""
+    mask = case['reg_mask'].clone()
+    cleared = torch.arange(mask.numel())[mask > 0][-n:]
+    mask[cleared] = 0
+    P = case['bbox_targets'].size(0)
+    assert cleared.numel() == n and P > n
+    ours, theirs = dict(case), dict(case)
+    ours['reg_mask'] = theirs['reg_mask'] = mask
+    theirs['bbox_targets'], theirs['pos_gt_bboxes'] = case['bbox_targets'][:P - n], case['pos_gt_bboxes'][:P - n]
+    return ours, theirs, cleared
+
+
+def with_longer_target_buffer(case, rows):
+    """the target buffers padded with `rows` rows no positive pairs with (P + rows > R when rows >= R)"""
+    g = torch.Generator().manual_seed(31)
+    out = dict(case)
+    for k in ('bbox_targets', 'pos_gt_bboxes'):
+        out[k] = torch.cat([case[k], torch.rand(rows, 7, generator=g) + 0.5])
+    assert out['bbox_targets'].size(0) > case['reg_mask'].numel()
+    return out
+
+
 VALUE_KEYS = ('bbox_targets', 'label_weights', 'bbox_weights', 'grad_cls', 'grad_bbox')
 LOSS_KEYS = ('loss_cls', 'loss_bbox', 'loss_corner')
 LOSS_RTOL = 1e-5           # the project's bar for a loss value (README)

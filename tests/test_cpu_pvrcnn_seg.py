@@ -60,6 +60,13 @@ def check_loss_case(got, name, what):
         assert float(got['loss']) == 0.0 and not got['grad'].any()
     if name.startswith('no_positive'):
         assert float(got['n_pos']) == 0.0 and float(got['loss']) > 0.0      # the normaliser clamps to 1
+    if name.startswith('targets_past_background'):
+        # 2^40, -2^63 and 2^63 - 1 are targets like any other past background: not counted, no gradient (a 32-bit read of the target
+        # would see 0, 0 and -1: a positive of class 0 twice)
+        t = case['seg_targets']
+        rows = torch.tensor(ref.INT64_EXTREME_ROWS)
+        assert t[rows].tolist() == list(ref.INT64_EXTREMES) and not got['grad'][rows].any()
+        assert float(got['n_pos']) == float(((t >= 0) & (t < ref.NUM_CLASSES)).sum())
     return figures
 
 
@@ -77,6 +84,11 @@ def check_reweight_case(got, name, what):
         flat = (s == 0) | (s == 1)
         assert flat[0] and flat[2] and flat[3] and not flat[1]
         assert not got['grad_seg'].reshape(-1)[flat].any()
+    if name == 'n130_c8_k255':
+        k = case['seg_preds'].size(1)
+        want = torch.tensor(ref.forced_columns(k))[torch.arange(got['win'].numel()) % 4]
+        assert ref.forced_columns(k) == (0, 127, 128, 254) and torch.equal(got['win'], want)      # the byte's top bit included
+        assert got['grad_seg'].gather(1, want[:, None]).ne(0).all() and r64['grad_seg'].gather(1, want[:, None]).ne(0).all()
     return figures
 
 
@@ -90,7 +102,7 @@ def test_seg_loss_twin_matches_the_restatement(name):
         assert torch.equal(got[k], again[k]), k
 
 
-@pytest.mark.parametrize('name', sorted(ref.REWEIGHT_CASES))
+@pytest.mark.parametrize('name', ref.ALL_REWEIGHT_CASES)
 def test_reweight_twin_matches_the_restatement(name):
     case = ref.reweight_reference(name)[0]
     got = run_reweight(case)
@@ -106,6 +118,130 @@ def test_reweight_misaligned_base_equals_the_aligned_case():
     aligned, shifted = run_reweight(case), run_reweight(case, view=ref.offset_view)
     for k in aligned:
         assert torch.equal(aligned[k], shifted[k]), k
+
+
+SENTINEL = -77.0
+SINGLE_SHIFTS = ('fwd.feats', 'fwd.out', 'bwd.grad_out', 'bwd.feats', 'bwd.grad_feats')     # every pointer either entry reads as float4
+
+
+def reweight_entries(case, dev='cpu', shift=(), win=None):
+    """`gd3d_keypoint_reweight` and `gd3d_keypoint_reweight_backward` (or their twins) on sentinel-filled outputs with a guard row either
+    side.  An operand named in `shift` ('fwd.' / 'bwd.' + feats, out, grad_out, grad_feats) starts one float into a larger buffer: its
+    pointer is 4-byte aligned only; every other pointer is 16-byte aligned when C % 4 == 0.  `win`: a byte the backward reads as every
+    row's winner instead of the forward's.  Asserts that every output element is written and no guard is -> dict like run_reweight's"""
+    N, C = case['feats'].shape
+    K = case['seg_preds'].size(1)
+
+    def operand(t, name):
+        t = t.to(dev).contiguous()
+        t = ref.offset_view(t) if name in shift else t
+        assert t.data_ptr() % 16 == (4 if name in shift else 0)
+        return t
+
+    def guarded(cols, name):
+        off = 1 if name in shift else 0
+        buf = torch.full(((N + 2) * cols + 8,), SENTINEL, device=dev)
+        rows = buf[off:off + (N + 2) * cols].view(N + 2, cols)
+        if cols % 4 == 0:
+            assert rows[1:].data_ptr() % 16 == 4 * off
+        return rows
+
+    x = case['seg_preds'].to(dev).contiguous()
+    out, gf, gx = guarded(C, 'fwd.out'), guarded(C, 'bwd.grad_feats'), guarded(K, 'bwd.grad_seg')
+    won = torch.full((N + 2,), 200, dtype=torch.uint8, device=dev)
+    f_fwd, f_bwd, g = operand(case['feats'], 'fwd.feats'), operand(case['feats'], 'bwd.feats'), operand(case['grad_out'], 'bwd.grad_out')   # kept alive
+    _host.call('gd3d_keypoint_reweight', x.device, (f_fwd.data_ptr(), x.data_ptr(), N, C, K, out[1:].data_ptr(), won[1:].data_ptr()))
+    assert won[0] == 200 and won[-1] == 200 and (won[1:-1] < K).all()
+    used = won if win is None else torch.full_like(won, win)
+    _host.call('gd3d_keypoint_reweight_backward', x.device,
+               (g.data_ptr(), f_bwd.data_ptr(), x.data_ptr(), used[1:].data_ptr(), N, C, K, gf[1:].data_ptr(), gx[1:].data_ptr()))
+    for buf in (out, gf, gx):
+        assert (buf[0] == SENTINEL).all() and (buf[-1] == SENTINEL).all(), 'a guard row was written'
+        assert not (buf[1:-1] == SENTINEL).any(), 'an output element was left unwritten'
+    return dict(out=out[1:-1].cpu().contiguous(), win=won[1:-1].cpu().long(), grad_feats=gf[1:-1].cpu().contiguous(), grad_seg=gx[1:-1].cpu().contiguous())
+
+
+def check_entries_equal_the_wrapper(name, dev='cpu'):
+    """every element of the four arrays written, the guard rows either side intact, and the wrapper's bits"""
+    case = ref.reweight_reference(name)[0]
+    got, want = reweight_entries(case, dev), run_reweight(case, dev=dev)
+    for k in want:
+        assert torch.equal(got[k], want[k]), k
+
+
+def check_single_misaligned_operand(shift, dev='cpu'):
+    """ONE operand one float into a larger buffer, every other pointer 16-byte aligned, C = 128: the launch has to leave the 16-byte
+    path on that pointer alone, and gives the all-aligned run's bits (a decision that looked at another pointer only would read or
+    write a float4 at an address that is no multiple of 16)"""
+    case = ref.reweight_reference(ref.MISALIGNED_OF)[0]
+    assert case['feats'].size(1) % 4 == 0 and shift in SINGLE_SHIFTS
+    aligned, shifted = reweight_entries(case, dev), reweight_entries(case, dev, shift=(shift,))
+    for k in aligned:
+        assert torch.equal(aligned[k], shifted[k]), (shift, k)
+
+
+def check_foreign_winner_bytes(name, dev='cpu'):
+    """a winner array from elsewhere holding 200 where K = 3: the backward clamps the byte to K - 1 (the kernel's comment), so the
+    gradient lands in the last column, computed with that column's sigmoid, and nothing is accessed past the row (reweight_entries
+    asserts the guard rows either side of grad_seg and that every element between them is written)"""
+    case = ref.reweight_reference(name)[0]
+    K = case['seg_preds'].size(1)
+    assert K == 3
+    got, last = reweight_entries(case, dev, win=200), reweight_entries(case, dev, win=K - 1)
+    for k in got:
+        assert torch.equal(got[k], last[k]), k
+    assert not got['grad_seg'][:, :K - 1].any() and got['grad_seg'][:, K - 1].ne(0).all()
+    want = {}
+    for dtype in (torch.float32, torch.float64):            # what "column K - 1 won" means, in plain torch
+        f, x, g = (case[k].to(dtype) for k in ('feats', 'seg_preds', 'grad_out'))
+        s = x[:, K - 1].sigmoid()
+        gx = torch.zeros_like(x)
+        gx[:, K - 1] = (g * f).sum(dim=1) * (s * (1 - s))
+        want[dtype] = dict(grad_feats=g * s[:, None], grad_seg=gx)
+    ref.check_values(got, want[torch.float32], want[torch.float64], ('grad_feats', 'grad_seg'), f'{dev} {name} winner byte 200')
+
+
+def check_one_sided_backward(name, dev='cpu'):
+    """only `feats`, then only `seg_preds`, requires a gradient: the other gradient pointer is null (the kernel skips the dot product,
+    or leaves the loop before its shuffles) and the one computed has the two-sided run's bits"""
+    case = ref.reweight_reference(name)[0]
+    both = run_reweight(case, dev=dev)
+    for key, wanted in (('grad_feats', 'feats'), ('grad_seg', 'seg_preds')):
+        ops = {k: case[k].to(dev).clone() for k in ('feats', 'seg_preds')}
+        ops[wanted].requires_grad_(True)
+        amd.keypoint_reweight(ops['feats'], ops['seg_preds']).backward(case['grad_out'].to(dev))
+        other = 'seg_preds' if wanted == 'feats' else 'feats'
+        assert ops[other].grad is None and torch.equal(ops[wanted].grad.cpu(), both[key]), key
+
+
+@pytest.mark.parametrize('name', ['n65_c3_k3', 'n67_c260_k3', 'n130_c8_k255'] + list(ref.SWEEP_CASES))
+def test_reweight_entry_points_write_every_element_and_nothing_beyond(name):
+    check_entries_equal_the_wrapper(name)
+
+
+@pytest.mark.parametrize('shift', SINGLE_SHIFTS)
+def test_reweight_single_misaligned_operand_equals_the_aligned_run(shift):
+    check_single_misaligned_operand(shift)
+
+
+@pytest.mark.parametrize('name', ['n65_c3_k3', 'n130_c128_k3'])
+def test_reweight_backward_clamps_a_foreign_winner_byte(name):
+    check_foreign_winner_bytes(name)
+
+
+def test_reweight_one_sided_backward_equals_the_two_sided_run():
+    check_one_sided_backward('n130_c128_k3')
+
+
+def test_sweep_cases_pass_the_grid_cap():
+    """the arithmetic the sweep cases stand on, from the shapes themselves: N rows > 8192 workgroups x 4 rows per workgroup"""
+    for name in ref.SWEEP_CASES:
+        case = ref.reweight_reference(name)[0]
+        N, C = case['feats'].shape
+        rows = 256 // min(64, 1 << max(0, ((C + 3) // 4 - 1).bit_length()))       # RW_BLOCK / group_lanes(C)
+        assert rows == ref.SWEEP_ROWS and N > ref.SWEEP_CAP * rows and N - ref.SWEEP_CAP * rows == 5
+    assert ref.reweight_reference('n32773_c256_k3')[0]['feats'].size(1) % 4 == 0      # the 16-byte path
+    assert ref.reweight_reference('n32773_c255_k1')[0]['feats'].size(1) % 4 == 3      # the 4-byte path, a clipped last quad
 
 
 def test_reweight_empty_and_forward_only(monkeypatch):

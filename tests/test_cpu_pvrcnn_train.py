@@ -5,7 +5,9 @@ against the statement-by-statement torch restatement of the reference (tests/pvr
   * loss values within 1e-5 (relative) of the fp64 restatement;
   * bbox_targets, the normalised weights and both gradients within 4x the fp32 restatement's own largest deviation from the fp64 one
     on the same inputs (printed per case; DESIGN.md §3.10 records the figures);
-on the smallest shapes that cross a boundary (pvrcnn_train_ref.CASES), both rotation senses, both input forms."""
+on the smallest shapes that cross a boundary (pvrcnn_train_ref.CASES), both rotation senses, both input forms; and the loss alone on
+scattered positives (pvrcnn_train_ref.SCATTER_CASES), other mask values, count mismatches and the C entry's RoI layouts — the checks
+tests/test_gpu_pvrcnn_train.py repeats on the device, with every generator condition asserted here."""
 import math
 
 import pytest
@@ -92,6 +94,244 @@ def test_cpu_twin_matches_the_restatement(name, clockwise):
     again = run_package(inputs, clockwise, form='lists')
     for k in lists:                                  # and the same bits on every run
         assert torch.equal(lists[k], again[k]), k
+
+
+# ---- scattered positives, mask values, count mismatches, the C entry's RoI layout, B = MAX_SAMPLES ------------------------------------
+
+SENTINEL = -77.0
+MISMATCHES = ('more_positives', 'fewer_positives', 'longer_target_buffer')
+
+
+def run_loss(case, dev='cpu'):
+    """`pvrcnn_head_loss` and the gradients of the summed losses on loss operands (pvrcnn_train_ref.scatter's dict) -> dict on the CPU"""
+    t = {k: case[k].to(dev) for k in ref.LOSS_INPUT_KEYS}
+    x, p = t['cls_score'].clone().requires_grad_(True), t['bbox_pred'].clone().requires_grad_(True)
+    losses = amd.pvrcnn_head_loss(ref.LOSS_CLS, ref.LOSS_BBOX, x, p, t['rois'], t['label'], t['bbox_targets'], t['pos_gt_bboxes'], t['reg_mask'],
+                                  t['label_weights'], t['bbox_weights'])
+    sum(losses.values()).backward()
+    out = {k: v.detach().cpu() for k, v in losses.items()}
+    out['grad_cls'], out['grad_bbox'] = x.grad.cpu(), p.grad.cpu()
+    return out
+
+
+def check_loss_against(got, r32, r64, what):
+    """the project's rule on a loss-only evaluation: loss values within LOSS_RTOL of fp64, gradients within NOISE_FACTOR times the fp32
+    restatement's own deviation; prints every figure before it asserts -> {key: (error, fp32 restatement's deviation, bound)}"""
+    failures, figures = [], {}
+    for k, (dev32, bound) in ref.loss_bounds(r32, r64).items():
+        assert got[k].shape == r64[k].shape and got[k].dtype == torch.float32, (k, got[k].shape, r64[k].shape)
+        err = float((got[k].double() - r64[k]).abs().max())
+        print(f'{what} {k}: |ours - fp64| = {err:.3e}; fp32 restatement {dev32:.3e}; bound {bound:.3e}; ratio to bound {err / bound if bound else 0.0:.3f}')
+        figures[k] = (err, dev32, bound)
+        if not err <= bound:
+            failures.append((k, err, bound))
+    for k in ref.LOSS_KEYS:
+        want = float(r64[k])
+        err = abs(float(got[k]) - want)
+        print(f'{what} {k}: ours {float(got[k]):.9g}, fp64 {want:.9g}, relative error {err / abs(want) if want else err:.3e} (bar {ref.LOSS_RTOL:g})')
+        figures[k] = (err / abs(want) if want else err, 0.0, ref.LOSS_RTOL)
+        if not err <= ref.LOSS_RTOL * abs(want):
+            failures.append((k, err, ref.LOSS_RTOL * abs(want)))
+    assert not failures, f'{what}: (key, error, bound) {failures}'
+    return figures
+
+
+def same_bits(a, b, keys=None):
+    for k in keys or a:
+        assert torch.equal(a[k], b[k]), k
+
+
+def check_scattered(name, dev='cpu'):
+    """a scattered case on `dev`: within the bounds of the restatement on the same permuted operands, a bbox_pred gradient on exactly the
+    positive rows, and the same bits on a second run -> (the result, the figures)"""
+    case, r32, r64 = ref.scattered_reference(name)
+    got = run_loss(case, dev)
+    figures = check_loss_against(got, r32, r64, f'{dev} {name}')
+    assert torch.equal(got['grad_bbox'].ne(0).any(dim=1), case['reg_mask'] > 0), 'the rows that pair with a target are the positive rows'
+    assert torch.equal(r64['grad_bbox'].ne(0).any(dim=1), case['reg_mask'] > 0)
+    same_bits(got, run_loss(case, dev))
+    return got, figures
+
+
+def check_mask_values(name, dev='cpu'):
+    """positives carry 1, 2, 7, every third other row -1: the rule is reg_mask > 0, so the result has the 0 / 1 mask's bits"""
+    case, r32, r64 = ref.scattered_reference(name)
+    valued = ref.with_mask_values(case)
+    v64 = ref.evaluate_loss(valued, torch.float64)
+    same_bits(v64, r64)                                       # the expectation is unchanged
+    got = run_loss(valued, dev)
+    check_loss_against(got, r32, r64, f'{dev} {name} mask values 1, 2, 7, -1')
+    same_bits(got, run_loss(case, dev))
+    return got
+
+
+def check_mismatch(kind, name, dev='cpu'):
+    """the documented behaviour of `pvrcnn_head_loss` when mask positives and target rows do not match in number"""
+    case, r32, r64 = ref.scattered_reference(name)
+    matched = run_loss(case, dev)
+    P, R = case['bbox_targets'].size(0), case['reg_mask'].numel()
+    n = 10 if R > 1000 else 5
+    if kind == 'more_positives':            # positives past the P-th are ignored
+        more, extra = ref.with_extra_positives(case, n)
+        got = run_loss(more, dev)
+        same_bits(got, matched, ref.LOSS_KEYS)              # the three losses: the matched call's bits (the corner mean runs over P rows)
+        assert not got['grad_bbox'][extra].any() and not matched['grad_bbox'][extra].any()
+        same_bits(got, matched, ('grad_cls', 'grad_bbox'))  # every gradient row, the extra ones included (zeros in both)
+        check_loss_against(got, r32, r64, f'{dev} {name} {n} extra positives')
+    elif kind == 'fewer_positives':         # the paired rows are the positives there are: the corner mean runs over P - n rows
+        ours, theirs, cleared = ref.with_fewer_positives(case, n)
+        got = run_loss(ours, dev)
+        t32, t64 = ref.evaluate_loss(theirs, torch.float32), ref.evaluate_loss(theirs, torch.float64)
+        check_loss_against(got, t32, t64, f'{dev} {name} {n} positives cleared')
+        assert not got['grad_bbox'][cleared].any() and matched['grad_bbox'][cleared].ne(0).any(dim=1).all()
+        same_bits(got, run_loss(theirs, dev))               # and the same bits as the call with the buffers cut to P - n rows
+        assert not torch.equal(got['loss_corner'], matched['loss_corner'])
+    elif kind == 'longer_target_buffer':    # P > R: rows of the buffers no positive reaches
+        longer = ref.with_longer_target_buffer(case, R)
+        assert longer['bbox_targets'].size(0) == P + R > R
+        same_bits(run_loss(longer, dev), matched)
+    else:
+        raise KeyError(kind)
+
+
+def loss_entry(case, dev='cpu', stride=8, first=1):
+    """`gd3d_roi_head_loss` (or its twin) on sentinel-filled outputs with a guard row either side, the RoI boxes at column `first` of rows
+    of `stride` floats (the other columns hold a value no box has).  Asserts every element written and no guard -> dict on the CPU"""
+    t = {k: case[k].to(dev).contiguous() for k in ref.LOSS_INPUT_KEYS}
+    R, P = t['reg_mask'].numel(), t['bbox_targets'].size(0)
+    rois = torch.full((R, stride), 1e6, device=dev)
+    rois[:, first:first + 7] = t['rois'][:, 1:8]
+    losses = torch.full((5,), SENTINEL, device=dev)
+    gc = torch.full((R + 2,), SENTINEL, device=dev)
+    gb, g1, g2 = (torch.full((R + 2, 7), SENTINEL, device=dev) for _ in range(3))
+    _host.call('gd3d_roi_head_loss', rois.device,
+               (t['cls_score'].data_ptr(), t['bbox_pred'].data_ptr(), rois.data_ptr(), stride, first, t['label'].data_ptr(), t['bbox_targets'].data_ptr(),
+                t['pos_gt_bboxes'].data_ptr(), t['reg_mask'].data_ptr(), t['label_weights'].data_ptr(), t['bbox_weights'].data_ptr(), R, P,
+                ref.LOSS_BBOX['beta'], 1.0, 1.0, 1, 0, losses[1:].data_ptr(), gc[1:].data_ptr(), gb[1:].data_ptr(), g1[1:].data_ptr(), g2[1:].data_ptr()))
+    for buf in (losses, gc, gb, g1, g2):
+        assert (buf[0] == SENTINEL).all() and (buf[-1] == SENTINEL).all(), 'a guard was written'
+        assert not (buf[1:-1] == SENTINEL).any(), 'an output element was left unwritten'
+    out = dict(zip(ref.LOSS_KEYS, losses[1:-1].cpu()))
+    out.update(grad_cls=gc[1:-1].cpu().reshape(-1, 1), grad_bbox=gb[1:-1].cpu(), grad_l1=g1[1:-1].cpu(), grad_corner=g2[1:-1].cpu())
+    return out
+
+
+def check_loss_entry(name, dev='cpu'):
+    """a scattered case through the C entry: every output element written and nothing beyond, the wrapper's bits, and the RoI layouts
+    7 / 0 and 10 / 2 giving the bits of the reference's 8 / 1"""
+    case = ref.scattered_reference(name)[0]
+    want = run_loss(case, dev)
+    base = loss_entry(case, dev, 8, 1)
+    same_bits(base, want, ref.LOSS_KEYS + ('grad_cls',))
+    assert torch.equal(base['grad_bbox'], base['grad_l1'] + base['grad_corner'])
+    other = case['reg_mask'] <= 0
+    assert not base['grad_l1'][other].any() and not base['grad_corner'][other].any() and base['grad_corner'][~other].ne(0).any(dim=1).all()
+    for stride, first in ((7, 0), (10, 2)):
+        same_bits(loss_entry(case, dev, stride, first), base)
+
+
+def check_targets_at_max_samples(dev='cpu'):
+    """B = MAX_SAMPLES = 1024 samples over the 2049 rows of case r2049: its three samples at indices 3, 511 and 1023, every other one
+    with roi_cnt = pos_cnt = 0.  Equal to the list form over the non-empty samples — the restatement's decisions, its values within the
+    case's bounds, and the list form's bits"""
+    name = 'r2049'
+    pos, gts, ious = ref.reference(name, False)[0][:3]
+    _, r32, r64 = ref.reference(name, False)
+    pc, rc = torch.zeros(1024, dtype=torch.int32), torch.zeros(1024, dtype=torch.int32)
+    for at, p, i in zip((3, 511, 1023), pos, ious):
+        pc[at], rc[at] = p.size(0), i.size(0)
+    assert int((rc > 0).sum()) == 3 and int(rc.sum()) == 2049 and int((pc > 0).sum()) == 3
+    keys = ('label', 'bbox_targets', 'pos_gt_bboxes', 'reg_mask', 'label_weights', 'bbox_weights')
+    got = dict(zip(keys, (t.cpu() for t in amd.pvrcnn_head_get_targets(torch.cat(pos).to(dev), torch.cat(gts).to(dev), torch.cat(ious).to(dev), ref.CFG,
+                                                                       pos_batch_cnt=pc.to(dev), roi_batch_cnt=rc.to(dev)))))
+    lists = dict(zip(keys, (t.cpu() for t in amd.pvrcnn_head_get_targets([p.to(dev) for p in pos], [g.to(dev) for g in gts], [i.to(dev) for i in ious], ref.CFG))))
+    same_bits(got, lists)
+    for k in ('label', 'reg_mask', 'pos_gt_bboxes'):
+        assert torch.equal(got[k], r32[k]), k
+    assert torch.equal(got['label_weights'] > 0, r32['label_weights'] > 0)
+    for k in ('bbox_targets', 'label_weights', 'bbox_weights'):
+        dev32, bound = ref.bounds(name, False)[k]
+        err = float((got[k].double() - r64[k]).abs().max())
+        print(f'{dev} {name} over 1024 samples {k}: |ours - fp64| = {err:.3e}; fp32 restatement {dev32:.3e}; bound {bound:.3e}')
+        assert err <= bound, (k, err, bound)
+    return got
+
+
+@pytest.mark.parametrize('name', list(ref.SCATTER_CASES) + list(ref.MISMATCH_BASES))
+def test_scattered_generator_keeps_its_margins(name):
+    """a permutation of rows leaves the generator's margins where test_generator_keeps_its_margins finds them; asserted on the permuted
+    operands all the same, and the pattern's own condition with them"""
+    case = ref.scattered_reference(name)[0]
+    tie, zero = ref.scattered_margins(case)
+    assert tie > ref.TIE_MARGIN and zero > ref.TIE_MARGIN, (tie, zero)
+    pos, gts = case['drawn']
+    u = torch.remainder(torch.cat(gts)[:, 6].double() - torch.cat(pos)[:, 6].double(), 2 * math.pi)
+    for border in (math.pi / 2, math.pi, 3 * math.pi / 2):
+        assert float((u - border).abs().min()) >= 1e-3
+    if u.numel() >= 64:
+        assert sorted(set((u / (math.pi / 2)).floor().long().tolist())) == [0, 1, 2, 3]
+    R, pattern = ref.SCATTER_ALL[name]
+    rows = torch.arange(R)[case['reg_mask'] > 0]
+    P = rows.numel()
+    assert R == case['reg_mask'].numel() and P == case['bbox_targets'].size(0) >= 1
+    if pattern == 'random':
+        assert (rows % 2 == 0).any() and (rows % 2 == 1).any() and (P >= 19) and not torch.equal(rows, torch.arange(P))
+    if pattern == 'odd_lanes':
+        assert (rows % 64 % 2 == 1).all() and P >= 19
+    if pattern == 'odd_waves':
+        assert (rows // 64 % 2 == 1).all() and (P == 1 or (rows < 1024).any() and (rows >= 1024).any())
+    if pattern == 'from_1024':
+        assert (rows >= 1024).all() and P > 1
+    if pattern == 'last64_and_2048':
+        assert rows.tolist() == list(range(1984, 2049))
+    if pattern == 'all_positive':
+        assert P == R
+    if pattern == 'random_head':
+        assert R - 1 - int(rows.max()) >= 10
+
+
+@pytest.mark.parametrize('name', list(ref.SCATTER_CASES))
+def test_loss_twin_on_scattered_positives(name):
+    check_scattered(name)
+
+
+@pytest.mark.parametrize('name', ['r2049_random', 'r65_random'])
+def test_loss_twin_takes_any_mask_value_above_zero(name):
+    check_mask_values(name)
+
+
+@pytest.mark.parametrize('name', list(ref.MISMATCH_BASES))
+@pytest.mark.parametrize('kind', MISMATCHES)
+def test_loss_twin_on_count_mismatches(kind, name):
+    check_mismatch(kind, name)
+
+
+@pytest.mark.parametrize('name', ['r2049_random', 'r65_odd_lanes'])
+def test_loss_twin_entry_writes_every_element_and_takes_any_roi_layout(name):
+    check_loss_entry(name)
+
+
+def test_targets_twin_at_max_samples():
+    check_targets_at_max_samples()
+
+
+def test_targets_twin_with_more_target_rows_than_rois():
+    check_targets_longer_than_rois()
+
+
+def check_targets_longer_than_rois(dev='cpu'):
+    """stacked inputs whose positive buffers are padded past the RoI rows (P = 73 > R = 64: the launch is sized by the larger): the
+    covered rows are the exact call's, the target rows past the counts zeros"""
+    pos, gts, ious = ref.reference('r64_all_positive', False)[0][:3]
+    exact = amd.pvrcnn_head_get_targets([p.to(dev) for p in pos], [g.to(dev) for g in gts], [i.to(dev) for i in ious], ref.CFG)
+    g = torch.Generator().manual_seed(6)
+    pb = torch.cat(pos + [torch.rand(9, 7, generator=g) + 0.5]).to(dev)
+    pg = torch.cat(gts + [torch.rand(9, 7, generator=g) + 0.5]).to(dev)
+    cnt = torch.tensor([64], dtype=torch.int32, device=dev)
+    got = amd.pvrcnn_head_get_targets(pb, pg, torch.cat(ious).to(dev), ref.CFG, pos_batch_cnt=cnt, roi_batch_cnt=cnt)
+    assert got[1].shape == (73, 7) and torch.equal(got[1][:64], exact[1]) and not got[1][64:].any()
+    for k in (0, 3, 4, 5):
+        assert got[k].shape == (64,) and torch.equal(got[k], exact[k]), k
 
 
 def _single(roi_yaw, gt_yaw, clockwise=False):
@@ -240,6 +480,9 @@ def test_argument_checks():
         amd.pvrcnn_head_get_targets(pos[0], gts[0], ious[0], ref.CFG, pos_batch_cnt=torch.tensor([20.0]), roi_batch_cnt=torch.tensor([63]))
     with pytest.raises(RuntimeError, match='shape mismatch'):
         amd.pvrcnn_head_get_targets(pos[0], gts[0], ious[0], ref.CFG, pos_batch_cnt=torch.tensor([20, 0]), roi_batch_cnt=torch.tensor([63]))
+    too_many = torch.zeros(1025, dtype=torch.int32)                                     # one sample more than MAX_SAMPLES: refused before any launch
+    with pytest.raises(RuntimeError, match='too large'):
+        amd.pvrcnn_head_get_targets(pos[0], gts[0], ious[0], ref.CFG, pos_batch_cnt=too_many, roi_batch_cnt=too_many)
     meta = torch.device('meta')
     with pytest.raises(RuntimeError, match='different devices'):
         amd.pvrcnn_head_get_targets([pos[0].to(meta)], gts, ious, ref.CFG)

@@ -30,12 +30,15 @@ def geometry(case):
     return case['voxel_size'], case['point_cloud_range'], case['scale'], case['align']
 
 
-def run_interp(case, layout, dev='cpu', view=lambda t: t):
-    """the package's features and map gradient of a case on `dev` -> dict like vsa_bev_ref.evaluate_interp's (on the CPU)"""
-    bev = view(in_layout(case['bev'].to(dev), layout).clone()).requires_grad_(True)     # never the shared case tensor itself
+def run_interp(case, layout, dev='cpu', view=lambda t: t, backward=True):
+    """the package's features and map gradient of a case on `dev` -> dict like vsa_bev_ref.evaluate_interp's (on the CPU); `backward`
+    False: the features alone"""
+    bev = view(in_layout(case['bev'].to(dev), layout).clone()).requires_grad_(backward)     # never the shared case tensor itself
     kp = case['keypoints'].to(dev)
     out = amd.bev_interpolate(kp[..., :3], bev, *geometry(case))
-    assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == case['grad_out'].shape
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == (kp.size(0), kp.size(1), bev.size(1))
+    if not backward:
+        return dict(out=out.detach().cpu())
     out.backward(view(case['grad_out'].to(dev)))
     assert bev.grad.stride() == bev.stride(), 'the gradient comes in the caller\'s layout'
     with torch.no_grad():
@@ -84,6 +87,99 @@ def test_bev_interpolate_misaligned_base_equals_the_aligned_case():
         aligned, shifted = run_interp(case, layout), run_interp(case, layout, view=shift)
         for k in aligned:
             assert torch.equal(aligned[k], shifted[k]), (layout, k)
+
+
+SENTINEL = -77.0
+
+
+def interp_forward_entry(case, layout, dev='cpu', shift=()):
+    """`gd3d_vsa_bev_interp` (or its twin) on a sentinel-filled output with a guard row either side; an operand named in `shift` ('bev',
+    'out') starts one float into a larger buffer, every other pointer is 16-byte aligned.  Asserts that every row is written — the zero
+    rows too — and no guard is -> out (B, M, C) on the CPU"""
+    kp = case['keypoints'].to(dev)
+    bev = in_layout(case['bev'].to(dev), layout)
+    B, C, H, W = bev.shape
+    M = kp.size(1)
+    flag = int(layout == 'channels_last')
+    dense = bev.permute(0, 2, 3, 1) if flag else bev                 # the map as it lies in memory
+    assert dense.is_contiguous()
+    dense = ref.offset_view(dense) if 'bev' in shift else dense
+    off = 1 if 'out' in shift else 0
+    buf = torch.full(((B * M + 2) * C + 8,), SENTINEL, device=dev)
+    out = buf[off:off + (B * M + 2) * C].view(B * M + 2, C)
+    if C % 4 == 0:
+        assert dense.data_ptr() % 16 == (4 if 'bev' in shift else 0) and out[1:].data_ptr() % 16 == 4 * off
+    corners = vsa_bev._corners(case['voxel_size'][:2], case['point_cloud_range'][:2], case['point_cloud_range'][3:5], case['scale'], case['align'])
+    _host.call('gd3d_vsa_bev_interp', kp.device, (kp.data_ptr(), kp.stride(0), kp.stride(1), dense.data_ptr(), flag, B, M, C, H, W, *corners,
+                                                  out[1:].data_ptr()))
+    assert (out[0] == SENTINEL).all() and (out[-1] == SENTINEL).all(), 'a guard row was written'
+    assert not (out[1:-1] == SENTINEL).any(), 'an output element was left unwritten'
+    return out[1:-1].reshape(B, M, C).cpu().contiguous()
+
+
+def check_sweep_forward(name, dev='cpu'):
+    """a forward-only sweep case (vsa_bev_ref.SWEEP_CASES: B * M = 65542 > 16384 workgroups x 4 keypoints): within the bounds against
+    fp64, bit-identical to the twin, between the layouts and from run to run; through the C entry every row is written, the zero rows
+    included, and nothing past the last"""
+    case, r32, r64 = ref.sweep_reference(name)
+    layouts = ref.SWEEP_CASES[name][1]
+    got = {layout: run_interp(case, layout, dev=dev, backward=False) for layout in layouts}
+    figures = {layout: ref.check_values(got[layout], r32, r64, ('out',), f'{dev} {layout} {name}') for layout in layouts}
+    first = got[layouts[0]]['out']
+    zero_rows = r64['out'].eq(0).all(dim=-1)
+    assert bool(zero_rows.any()) and not first[zero_rows].any() and first[~zero_rows].ne(0).any(dim=-1).all()
+    twin = first if dev == 'cpu' else run_interp(case, layouts[0], dev='cpu', backward=False)['out']
+    for layout in layouts:
+        assert torch.equal(got[layout]['out'], twin), f'{layout}: the forward has the bits of the twin, in every layout'
+        assert torch.equal(run_interp(case, layout, dev=dev, backward=False)['out'], twin), f'{layout}: run to run'
+        assert torch.equal(interp_forward_entry(case, layout, dev), twin), f'{layout}: the C entry'
+    return figures
+
+
+def check_sweep_exact(dev='cpu'):
+    """the order-free sweep case, forward and backward, both layouts: the features and the map's gradient EQUAL the exact fp64
+    interpolation — a keypoint row skipped or taken twice by the grid-stride loop of interp_backward_kernel changes a sum"""
+    case, r32, r64, exact = ref.sweep_exact_reference()
+    figures = {}
+    for layout in LAYOUTS:
+        got = run_interp(case, layout, dev=dev)
+        figures[layout] = ref.check_values(got, r32, r64, ref.INTERP_KEYS, f'{dev} {layout} {ref.SWEEP_EXACT}')
+        assert torch.equal(got['out'].double(), exact['out']), layout
+        assert torch.equal(got['grad_bev'].double(), exact['grad_bev']), f'{layout}: sums of multiples of 2^-8 below 2^16 are exact in any order'
+    return figures
+
+
+def check_interp_single_misaligned_operand(shift, dev='cpu'):
+    """channels last, C = 64, ONE of the two pointers the launch reads as float4 one float into a larger buffer: the 4-byte path's
+    bits equal the all-aligned run's"""
+    case = ref.interp_reference(ref.MISALIGNED_OF)[0]
+    assert case['bev'].size(1) == 64 and shift in ('bev', 'out')
+    assert torch.equal(interp_forward_entry(case, 'channels_last', dev, shift=(shift,)), interp_forward_entry(case, 'channels_last', dev))
+
+
+@pytest.mark.parametrize('name', sorted(ref.SWEEP_CASES))
+def test_bev_interpolate_sweep_forward(name):
+    check_sweep_forward(name)
+
+
+def test_bev_interpolate_sweep_generators_keep_their_conditions():
+    """the spilled rows of the mixed sweeps hold a keypoint inside the map and one out of reach (asserted by the builders, on the fp64
+    restatement too); the order-free case keeps fp32 pixel coordinates equal to fp64 and sum |g w| x 256 < 2^24"""
+    for name, (C, layouts, _) in ref.SWEEP_CASES.items():
+        case = ref.sweep_reference(name)[0]
+        R = case['keypoints'].size(0) * case['keypoints'].size(1)
+        assert R > ref.SWEEP_CAP * ref.SWEEP_ROWS and case['spilled'].tolist() == list(range(65536, 65542)) and case['bev'].size(1) == C
+    case = ref.sweep_exact_reference()[0]
+    assert case['keypoints'].size(0) * case['keypoints'].size(1) > ref.SWEEP_CAP * ref.SWEEP_ROWS and case['bev'].size(1) == 64
+
+
+def test_bev_interpolate_sweep_backward_is_exact():
+    check_sweep_exact()
+
+
+@pytest.mark.parametrize('shift', ['bev', 'out'])
+def test_bev_interpolate_single_misaligned_operand_equals_the_aligned_run(shift):
+    check_interp_single_misaligned_operand(shift)
 
 
 def test_other_striding_takes_a_copy_and_keypoint_views_are_read_in_place():
@@ -197,12 +293,12 @@ def test_other_dtypes_are_evaluated_in_fp32_and_cast_back(dtype):
 
 # ---- voxel_centers ---------------------------------------------------------------------------------------------------------------
 
-def check_centres(coors, align, scale, dev='cpu'):
+def check_centres(coors, align, scale, dev='cpu', batch_size=3):
     rng = ref.point_cloud_range(1600, 1408, 1)
-    xyz, cnt = amd.voxel_centers(coors.to(dev), ref.VOXEL_SIZE, rng, scale, align, 3)
+    xyz, cnt = amd.voxel_centers(coors.to(dev), ref.VOXEL_SIZE, rng, scale, align, batch_size)
     want = ref.get_voxel_centers(coors, ref.VOXEL_SIZE, rng, scale, align)
-    want_cnt = ref.count_loop(coors, want, 3)
-    assert xyz.dtype == torch.float32 and xyz.shape == (coors.size(0), 3) and cnt.dtype == torch.int32 and cnt.shape == (3,)
+    want_cnt = ref.count_loop(coors, want, batch_size)
+    assert xyz.dtype == torch.float32 and xyz.shape == (coors.size(0), 3) and cnt.dtype == torch.int32 and cnt.shape == (batch_size,)
     assert torch.equal(xyz.cpu(), want), 'the fp32 statements\' bits'
     assert torch.equal(cnt.cpu(), want_cnt)
     return xyz, cnt
@@ -217,6 +313,64 @@ def test_voxel_centers_twin_equals_the_torch_statements(n, dtype):
         assert int(cnt[1]) == 0 and int(cnt.sum()) == n - (2 if n >= 65 else 0)        # the empty middle sample; ids -1 and B counted nowhere
     big = torch.tensor([[0, 1 << 20, (1 << 24) + 1, -5]], dtype=dtype)                  # a coordinate past 2^24 rounds as .float() does; a negative one
     check_centres(big, 'half', 8)
+
+
+def centres_entry(coors, align, scale, batch_size, dev='cpu'):
+    """`gd3d_vsa_voxel_centers` (or its twin) on sentinel-filled outputs with a guard either side -> (xyz, cnt) on the CPU, after
+    asserting that every centre is written and no guard is"""
+    c = coors.to(dev).contiguous()
+    N = c.size(0)
+    rng = ref.point_cloud_range(1600, 1408, 1)
+    size, lo, add = vsa_bev._centre_terms(ref.VOXEL_SIZE, rng[:3], scale, align)
+    xyz = torch.full((N + 2, 3), SENTINEL, device=dev)
+    cnt = torch.full((batch_size + 2,), -5, dtype=torch.int32, device=dev)
+    _host.call('gd3d_vsa_voxel_centers', c.device, (c.data_ptr(), int(c.dtype == torch.int64), N, size, float(scale), lo, add, batch_size,
+                                                    xyz[1:].data_ptr(), cnt[1:].data_ptr()))
+    assert (xyz[0] == SENTINEL).all() and (xyz[-1] == SENTINEL).all() and not (xyz[1:-1] == SENTINEL).any()
+    assert cnt[0] == -5 and cnt[-1] == -5
+    return xyz[1:-1].cpu().contiguous(), cnt[1:-1].cpu().contiguous()
+
+
+def host_bincount(coors, batch_size):
+    ids = coors[:, 0].long()
+    return torch.bincount(ids[(ids >= 0) & (ids < batch_size)], minlength=batch_size).int()
+
+
+def check_centre_sweep(dtype, dev='cpu'):
+    """N = 4096 x 256 + 65 rows (vsa_bev_ref.CENTRE_SWEEP_N): workgroup 0's second trip holds one full wave and one wave with a single
+    row.  Centres: the fp32 torch statements' bits; counts: a host bincount; the guards either side intact"""
+    N = ref.CENTRE_SWEEP_N
+    assert N > 4096 * 256 and (N - 4096 * 256) % 64 == 1
+    coors = ref.make_coors(N, 3, 77 + int(dtype == torch.int64), dtype)          # with the stray ids -1 and 3
+    xyz, cnt = centres_entry(coors, 'half', 8, 3, dev)
+    assert torch.equal(xyz, ref.get_voxel_centers(coors, ref.VOXEL_SIZE, ref.point_cloud_range(1600, 1408, 1), 8, 'half'))
+    assert torch.equal(cnt, host_bincount(coors, 3)) and int(cnt.sum()) == N - 2 and int(cnt[1]) == 0
+    return xyz, cnt
+
+
+def check_centres_many_ids(dtype, dev='cpu'):
+    """63, and with the ids moved on by one row 64, distinct counted batch ids in one wave (vsa_bev_ref.make_coors_many_ids): the counts
+    are exact -> the counts of both forms"""
+    counts = []
+    for shift in (0, 1):
+        coors = ref.make_coors_many_ids(dtype, shift)
+        _, cnt = check_centres(coors, 'halfmin', 2, dev=dev, batch_size=ref.MANY_IDS_B)
+        stray = int(((coors[:, 0] < 0) | (coors[:, 0] >= ref.MANY_IDS_B)).sum())
+        assert torch.equal(cnt.cpu(), host_bincount(coors, ref.MANY_IDS_B)) and int(cnt.sum()) == 2049 - stray and stray >= 56
+        _, cnt2 = centres_entry(coors, 'halfmin', 2, ref.MANY_IDS_B, dev)          # the guards either side of the 70 counts
+        assert torch.equal(cnt2, cnt.cpu())
+        counts.append(cnt.cpu())
+    return torch.stack(counts)
+
+
+@pytest.mark.parametrize('dtype', [torch.int32, torch.int64])
+def test_voxel_centers_sweep(dtype):
+    check_centre_sweep(dtype)
+
+
+@pytest.mark.parametrize('dtype', [torch.int32, torch.int64])
+def test_voxel_centers_many_distinct_ids_in_a_wave(dtype):
+    check_centres_many_ids(dtype)
 
 
 def test_voxel_centers_reads_coors_through_a_copy_when_strided():

@@ -11,7 +11,8 @@ import torch
 import mmdet3d_gaussian_amd as amd
 import pvrcnn_seg_ref as ref
 from mmdet3d_gaussian_amd import _lib
-from test_cpu_pvrcnn_seg import check_loss_case, check_reweight_case, run_loss, run_reweight
+from test_cpu_pvrcnn_seg import (SINGLE_SHIFTS, check_entries_equal_the_wrapper, check_foreign_winner_bytes, check_loss_case,
+                                  check_one_sided_backward, check_reweight_case, check_single_misaligned_operand, run_loss, run_reweight)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -29,8 +30,10 @@ def test_seg_loss_on_the_device(name):
         assert torch.equal(got[k], again[k]), k
 
 
-@pytest.mark.parametrize('name', sorted(ref.REWEIGHT_CASES))
+@pytest.mark.parametrize('name', ref.ALL_REWEIGHT_CASES)
 def test_reweight_on_the_device(name):
+    """with the two sweep cases (pvrcnn_seg_ref.EXTRA_REWEIGHT_CASES: N = 32773 > 8192 workgroups x 4 rows) the second trip of the
+    grid-stride loop of reweight_kernel<true>, reweight_kernel<false> and both reweight_backward_kernel instances runs here"""
     case = ref.reweight_reference(name)[0]
     got = run_reweight(case, dev=DEV)
     check_reweight_case(got, name, 'gfx950')
@@ -94,6 +97,28 @@ def test_every_reweight_output_element_is_written(name):
     assert win[0] == 200 and win[-1] == 200 and (win[1:-1] < K).all()
     assert torch.equal(out[1:-1].cpu(), want['out']) and torch.equal(win[1:-1].cpu().long(), want['win'])
     assert torch.equal(gf[1:-1].cpu(), want['grad_feats']) and torch.equal(gx[1:-1].cpu(), want['grad_seg'])
+
+
+@pytest.mark.parametrize('name', ['n130_c8_k255'] + list(ref.SWEEP_CASES))
+def test_reweight_entry_points_write_every_element_and_nothing_beyond(name):
+    """as test_every_reweight_output_element_is_written, on K = 255 and on the two sweep cases: the rows of the second trip (N = 32773 =
+    8192 workgroups x 4 rows + 5) are written like every other row, and the guard row past them is not"""
+    check_entries_equal_the_wrapper(name, DEV)
+
+
+@pytest.mark.parametrize('shift', SINGLE_SHIFTS)
+def test_reweight_single_misaligned_operand_equals_the_aligned_run(shift):
+    check_single_misaligned_operand(shift, DEV)
+
+
+@pytest.mark.parametrize('name', ['n65_c3_k3', 'n130_c128_k3'])
+def test_reweight_backward_clamps_a_foreign_winner_byte(name):
+    """run on the `_cpu` twin first (tests/test_cpu_pvrcnn_seg.py): the clamp is documented behaviour, checked with guard rows"""
+    check_foreign_winner_bytes(name, DEV)
+
+
+def test_reweight_one_sided_backward_equals_the_two_sided_run():
+    check_one_sided_backward('n130_c128_k3', DEV)
 
 
 def test_keypoint_step_under_graph_capture():

@@ -1,14 +1,19 @@
 """PVRCNNBboxHead's training slice on the MI355X (csrc/roi_head.hip): the shapes and seeds of tests/test_cpu_pvrcnn_train.py on cuda:0.
 Decisions bit-identical to the `_cpu` twin and to the fp32 restatement, values and gradients within the same bounds against the fp64
 restatement (computed on the CPU, once per case), run-to-run bit identity, every output element written, and the whole step —
-targets, losses, backward — captured in one graph."""
+targets, losses, backward — captured in one graph.  And the loss's positive-row scan on masks the targets kernel never writes
+(pvrcnn_train_ref.SCATTER_CASES: positives scattered over lanes, waves and chunks), mask values other than 0 / 1, more and fewer
+mask positives than target rows, the C entry's RoI layouts, and the targets kernel with MAX_SAMPLES samples.
+
+Figures of the scattered cases: DESIGN.md §3.10's second table."""
 import pytest
 import torch
 
 import mmdet3d_gaussian_amd as amd
 import pvrcnn_train_ref as ref
 from mmdet3d_gaussian_amd import _host, _lib
-from test_cpu_pvrcnn_train import check_against_restatement, run_package
+from test_cpu_pvrcnn_train import (MISMATCHES, check_against_restatement, check_loss_entry, check_mask_values, check_mismatch, check_scattered,
+                                    check_targets_at_max_samples, check_targets_longer_than_rois, run_package)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -72,6 +77,46 @@ def test_every_output_element_is_written(name):
     assert torch.equal(gb[1:-1].cpu(), (g1[1:-1] + g2[1:-1]).cpu())
     positive = want['reg_mask'] > 0
     assert not g1[1:-1].cpu()[~positive].any() and not g2[1:-1].cpu()[~positive].any()
+
+
+@pytest.mark.parametrize('name', list(ref.SCATTER_CASES))
+def test_loss_on_scattered_positives(name):
+    """loss_kernel's positive-row scan — ballot and popcount inside the wave, the waves' totals through LDS, a running offset across the
+    chunks of 1024 rows — on positives interleaved inside a wave, confined to some waves, absent from the first chunk, or in the last
+    rows only: the restatement's result on the same permuted operands, the rows the twin pairs, the same bits on a second run"""
+    got, _ = check_scattered(name, DEV)
+    twin, _ = check_scattered(name, 'cpu')
+    assert torch.equal(got['grad_bbox'].ne(0), twin['grad_bbox'].ne(0)) and torch.equal(got['grad_cls'].ne(0), twin['grad_cls'].ne(0))
+
+
+@pytest.mark.parametrize('name', ['r2049_random', 'r65_random'])
+def test_loss_takes_any_mask_value_above_zero(name):
+    got, twin = check_mask_values(name, DEV), check_mask_values(name, 'cpu')
+    assert torch.equal(got['grad_bbox'].ne(0), twin['grad_bbox'].ne(0))
+
+
+@pytest.mark.parametrize('name', list(ref.MISMATCH_BASES))
+@pytest.mark.parametrize('kind', MISMATCHES)
+def test_loss_on_count_mismatches(kind, name):
+    check_mismatch(kind, name, DEV)
+
+
+@pytest.mark.parametrize('name', ['r2049_random', 'r65_odd_lanes'])
+def test_loss_entry_writes_every_element_and_takes_any_roi_layout(name):
+    """test_every_output_element_is_written's sentinels and guard rows on a scattered mask, and roi_stride / first_col of 7 / 0 and
+    10 / 2 against the wrapper's 8 / 1"""
+    check_loss_entry(name, DEV)
+
+
+def test_targets_at_max_samples():
+    """targets_kernel with both LDS tables full (B = MAX_SAMPLES = 1024): the twin's bits"""
+    got, twin = check_targets_at_max_samples(DEV), check_targets_at_max_samples('cpu')
+    for k in ('label', 'reg_mask', 'label_weights', 'bbox_weights', 'pos_gt_bboxes'):   # decisions and the normalisers: the same bits
+        assert torch.equal(got[k], twin[k]), k
+
+
+def test_targets_with_more_target_rows_than_rois():
+    check_targets_longer_than_rois(DEV)
 
 
 def test_whole_step_under_graph_capture():

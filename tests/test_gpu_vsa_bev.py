@@ -12,8 +12,9 @@ import torch
 import mmdet3d_gaussian_amd as amd
 import vsa_bev_ref as ref
 from mmdet3d_gaussian_amd import _lib, vsa_bev
-from test_cpu_vsa_bev import (LAYOUTS, check_centres, check_interp_case, check_robustness, check_sample_keypoints, geometry, in_layout,
-                              run_interp)
+from test_cpu_vsa_bev import (LAYOUTS, check_centre_sweep, check_centres, check_centres_many_ids, check_interp_case,
+                              check_interp_single_misaligned_operand, check_robustness, check_sample_keypoints, check_sweep_exact,
+                              check_sweep_forward, geometry, in_layout, run_interp)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -74,6 +75,37 @@ def test_every_interp_output_element_is_written(name, layout):
     got = dict(out=out[1:-1].view(B, M, C).cpu(), grad_bev=(body.permute(0, 3, 1, 2) if flag else body).cpu().contiguous())
     check_interp_case(got, name, f'gfx950 {layout} C entry')
     assert torch.equal(got['out'], run_interp(case, layout, dev=DEV)['out'])
+
+
+@pytest.mark.parametrize('name', sorted(ref.SWEEP_CASES))
+def test_bev_interpolate_sweep_forward(name):
+    """B * M = 2 x 32771 = 65542 keypoints > 16384 workgroups x 4 keypoints (L = 64 lanes each): six keypoints fall to the second trip of
+    interp_kernel<false> (C = 64, NCHW) and of interp_kernel<true> (C = 256, channels last)"""
+    check_sweep_forward(name, DEV)
+
+
+def test_bev_interpolate_sweep_backward_is_exact():
+    """the same 65542 keypoints, C = 64 (L = 64, 4 keypoints per workgroup), through interp_backward_kernel in both layouts: the second
+    trip's six rows add into the map exactly once"""
+    check_sweep_exact(DEV)
+
+
+@pytest.mark.parametrize('shift', ['bev', 'out'])
+def test_bev_interpolate_single_misaligned_operand_equals_the_aligned_run(shift):
+    check_interp_single_misaligned_operand(shift, DEV)
+
+
+@pytest.mark.parametrize('dtype', [torch.int32, torch.int64])
+def test_voxel_centers_sweep(dtype):
+    """N = 1 048 641 > 4096 workgroups x 256 rows: voxel_centers_kernel's second trip, its last wave one row wide"""
+    xyz, cnt = check_centre_sweep(dtype, DEV)
+    twin_xyz, twin_cnt = check_centre_sweep(dtype, 'cpu')
+    assert torch.equal(xyz, twin_xyz) and torch.equal(cnt, twin_cnt)
+
+
+@pytest.mark.parametrize('dtype', [torch.int32, torch.int64])
+def test_voxel_centers_many_distinct_ids_in_a_wave(dtype):
+    assert torch.equal(check_centres_many_ids(dtype, DEV), check_centres_many_ids(dtype, 'cpu'))
 
 
 def test_non_finite_and_huge_coordinates_give_zero_rows():

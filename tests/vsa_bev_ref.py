@@ -150,7 +150,7 @@ def _place(kind, m, H, W, scale, align, g):
     return xy
 
 
-def _interp_case(H, W, M, C, align, scale, kind, seed):
+def _interp_case(H, W, M, C, align, scale, kind, seed, with_grad=True):
     g = torch.Generator().manual_seed(seed)
     kinds = PLACEMENTS if kind == 'mixed' else (kind,)
     if kind == 'mixed':
@@ -162,7 +162,7 @@ def _interp_case(H, W, M, C, align, scale, kind, seed):
             rows = torch.arange(j, M, len(kinds))
             kp[b, rows, :2] = _place(k, rows.numel(), H, W, scale, align, g)
     bev = torch.randn(B, C, H, W, generator=g)
-    grad_out = torch.randn(B, M, C, generator=g)
+    grad_out = torch.randn(B, M, C, generator=g) if with_grad else None      # the last draw: leaving it out moves nothing
     assert kp.shape == (B, M, 3) and bool(torch.isfinite(kp).all())
     return dict(keypoints=kp, bev=bev, grad_out=grad_out, voxel_size=VOXEL_SIZE, point_cloud_range=point_cloud_range(H, W, scale),
                 scale=scale, align=align, H=H, W=W, kind=kind)
@@ -227,6 +227,132 @@ def interp_reference(name):
     return case, r32, r64
 
 
+# ---- the second sweep of the interpolation kernels ---------------------------------------------------------------------------------
+# row_grid caps a launch at 16384 workgroups; a workgroup of 256 threads holds 256 / L keypoints, L = row_lanes(items) lanes each.
+#   interp_kernel<false>, NCHW, C = 64:          L = row_lanes(64 channels) = 64 -> 4 keypoints per workgroup
+#   interp_kernel<true>, channels last, C = 256:  L = row_lanes(256 / 4 = 64 quads) = 64 -> 4 keypoints per workgroup
+#   interp_backward_kernel, C = 64, both layouts: L = row_lanes(64) = 64 -> 4 keypoints per workgroup
+# so one sweep covers 16384 * 4 = 65536 keypoints, and B * M = 2 * 32771 = 65542 leaves 6 to the second trip: workgroup 0 takes four,
+# workgroup 1 two.  (Channels last at C = 64 has L = row_lanes(16 quads) = 16, 16 keypoints per workgroup: one trip.)  These are the
+# smallest shapes that get there; the map stays 5 x 7.
+SWEEP_M = 32771
+SWEEP_CAP, SWEEP_ROWS = 16384, 4
+SWEEP_SPILL = B * SWEEP_M - SWEEP_CAP * SWEEP_ROWS
+assert SWEEP_SPILL == 6
+SWEEP_CASES = {
+    # name: (C, layouts the forward is checked in, seed) — `mixed` placement, forward only: M keypoints around 35 cells make the
+    # backward's sums long enough for the order of the float atomics to show; the order-free case below is the backward's
+    'sweep_m32771_c64': (64, ('nchw', 'channels_last'), 3501),
+    'sweep_m32771_c256': (256, ('channels_last',), 3502),
+}
+SWEEP_EXACT = 'sweep_m32771_c64_sixteenths'
+
+
+def make_sweep(name):
+    C, _, seed = SWEEP_CASES[name]
+    case = _interp_case(5, 7, SWEEP_M, C, 'half', 8, 'mixed', seed, with_grad=False)
+    spilled = torch.arange(SWEEP_CAP * SWEEP_ROWS, B * SWEEP_M)                  # the flat keypoint rows of the second trip
+    ix, iy = pixel_coords(case['keypoints'].reshape(-1, 3)[spilled], 5, 7, 8, 'half')
+    inside = (ix >= 0) & (ix <= 6) & (iy >= 0) & (iy <= 4)
+    far = (ix < -1) | (ix > 7) | (iy < -1) | (iy > 5)
+    assert bool(inside.any()) and bool(far.any()), 'the spilled rows hold a keypoint inside the map and one out of its reach'
+    case['spilled'] = spilled
+    return case
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_reference(name):
+    """(case, fp32 restatement, fp64 restatement) of a forward-only sweep case: `out` alone"""
+    case = make_sweep(name)
+    with torch.no_grad():
+        r32, r64 = ({'out': interpolate_from_bev_features(case['keypoints'].to(d), case['bev'].to(d), case['voxel_size'], case['point_cloud_range'],
+                                                          case['scale'], case['align'])} for d in (torch.float32, torch.float64))
+    rows = r64['out'].reshape(-1, r64['out'].size(-1))[case['spilled']]
+    assert bool(rows.eq(0).all(dim=1).any()) and bool(rows.ne(0).any(dim=1).any()), 'a zero row and a non-zero row among the spilled'
+    return case, r32, r64
+
+
+def kernel_pixel_coords(case):
+    """the fp32 pixel coordinates as csrc/vsa_bev_common.h takes them: ((v - tl) * (n - 1)) / (br - tl), tl and br from the reference's
+    fp32 statements :157-166"""
+    vs = torch.tensor(case['voxel_size'][:2], dtype=torch.float32)
+    tl = torch.tensor(case['point_cloud_range'][:2], dtype=torch.float32)
+    br = torch.tensor(case['point_cloud_range'][3:5], dtype=torch.float32)
+    if case['align'] == 'half':
+        tl.add_(0.5 * vs * case['scale'])
+        br.sub_(0.5 * vs * case['scale'])
+    else:
+        tl.add_(0.5 * vs)
+        br.sub_(vs * (case['scale'] - 0.5))
+    k = case['keypoints']
+    assert k.dtype == torch.float32
+    n = (case['W'], case['H'])
+    return tuple(((k[..., a] - tl[a]) * float(n[a] - 1)) / (br[a] - tl[a]) for a in (0, 1))
+
+
+def exact_interp(case, absolute=False):
+    """bilinear interpolation and its map gradient written out in fp64 on the EXACT pixel coordinates of `pixel_coords` (the kernel's rule
+    for reach and padding: within (-1, n), neighbours outside the map contribute nothing) -> dict(out, grad_bev).  `absolute`: the
+    sums of |g * w| instead, the magnitude every partial sum of grad_bev stays below"""
+    H, W = case['H'], case['W']
+    ix, iy = pixel_coords(case['keypoints'], H, W, case['scale'], case['align'])
+    bev, g = case['bev'].double(), case['grad_out'].double()
+    Bn, C = bev.shape[:2]
+    out, grad = torch.zeros(Bn, ix.size(1), C, dtype=torch.float64), torch.zeros(Bn, H * W, C, dtype=torch.float64)
+    flat = bev.permute(0, 2, 3, 1).reshape(Bn, H * W, C)
+    reach = (ix > -1) & (ix < W) & (iy > -1) & (iy < H)
+    x0, y0 = ix.floor(), iy.floor()
+    ax, ay = ix - x0, iy - y0
+    for dx, dy in ((0, 0), (1, 0), (0, 1), (1, 1)):
+        xj, yj = x0.long() + dx, y0.long() + dy
+        w = (ax if dx else 1 - ax) * (ay if dy else 1 - ay)
+        use = reach & (xj >= 0) & (xj < W) & (yj >= 0) & (yj < H)
+        w = torch.where(use, w, torch.zeros_like(w))
+        cell = torch.where(use, yj * W + xj, torch.zeros_like(xj))
+        for b in range(Bn):
+            out[b] += flat[b][cell[b]] * w[b][:, None]
+            gw = g[b] * w[b][:, None]
+            grad[b].index_add_(0, cell[b], gw.abs() if absolute else gw)
+    return dict(out=out, grad_bev=grad.reshape(Bn, H, W, C).permute(0, 3, 1, 2).contiguous())
+
+
+def make_sweep_exact():
+    """the sweep's backward, order-free (as `shared_cell` and the graph test are): B * M = 65542 keypoints on sixteenths of a cell of the
+    5 x 7 map — within a cell of it on every side, so partial padding is there too — small-integer upstream gradients and map values.
+    Every weight is a multiple of 2^-8 and every product g * w too; the builder asserts the two conditions under which every partial
+    sum of the gradient, taken in any order, is exact in fp32."""
+    H, W, M, C, scale, align = 5, 7, SWEEP_M, 64, 8, 'half'
+    g = torch.Generator().manual_seed(3503)
+    first, step = cell_grid(H, W, scale, align)
+    sx = torch.randint(-15, 16 * (W - 1) + 16, (B, M), generator=g)              # sixteenths: pixel coordinates in (-1, n - 1 + 15/16]
+    sy = torch.randint(-15, 16 * (H - 1) + 16, (B, M), generator=g)
+    kp = torch.zeros(B, M, 3)
+    kp[..., 0] = (first[0] + sx.double() / 16 * step[0]).float()
+    kp[..., 1] = (first[1] + sy.double() / 16 * step[1]).float()
+    case = dict(keypoints=kp, bev=torch.randint(-8, 9, (B, C, H, W), generator=g).float(), grad_out=torch.randint(-8, 9, (B, M, C), generator=g).float(),
+                voxel_size=VOXEL_SIZE, point_cloud_range=point_cloud_range(H, W, scale), scale=scale, align=align, H=H, W=W, kind='sixteenths')
+    ix, iy = pixel_coords(kp, H, W, scale, align)
+    assert torch.equal(ix * 16, sx.double()) and torch.equal(iy * 16, sy.double())                     # the keypoints ARE the sixteenths drawn
+    kx, ky = kernel_pixel_coords(case)
+    assert torch.equal(kx.double(), ix) and torch.equal(ky.double(), iy), 'condition 1: the fp32 and the fp64 pixel coordinates coincide'
+    assert bool((ix < 0).any()) and bool((ix > W - 1).any()) and bool((iy < 0).any()) and bool((iy > H - 1).any())
+    return case
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_exact_reference():
+    """(case, fp32 restatement, fp64 restatement, exact fp64 interpolation) of the order-free sweep case"""
+    case = make_sweep_exact()
+    exact = exact_interp(case)
+    bound_sum = float(exact_interp(case, absolute=True)['grad_bev'].max())
+    assert bound_sum * 256 < 2 ** 24, f'condition 2: sum |g * w| * 256 = {bound_sum * 256} must stay below 2^24'
+    assert torch.equal(exact['grad_bev'] * 256, (exact['grad_bev'] * 256).round()) and torch.equal(exact['out'] * 256, (exact['out'] * 256).round())
+    r32, r64 = evaluate_interp(case, torch.float32), evaluate_interp(case, torch.float64)
+    for k in INTERP_KEYS:      # the exact form IS the restatement: grid_sample in fp64 differs from it by its own rounding of the grid only
+        assert float((r64[k] - exact[k]).abs().max()) <= 1e-9 * max(1.0, float(exact[k].abs().max())), k
+    return case, r32, r64, exact
+
+
 def robustness_keypoints():
     """(B, M, 3) keypoints whose xy are NaN, +-inf, +-1e30 — the rows that must come out as zeros — interleaved with ordinary ones"""
     bad = [float('nan'), float('inf'), float('-inf'), 1e30, -1e30]
@@ -245,6 +371,25 @@ def robustness_keypoints():
 
 CENTRE_N = (0, 1, 65, 2049)
 CENTRE_GEOMETRY = (('half', 1), ('half', 8), ('halfmin', 2), ('halfmin', 8), ('half', 1.5))
+
+
+# voxel_centers_kernel: the grid is capped at 4096 workgroups of 256 rows, so one sweep covers 4096 * 256 = 1 048 576 rows and
+# N = 1 048 641 leaves 65 to the second trip of workgroup 0: one full wave and one wave with a single row, whose other 63 lanes still
+# have to reach the ballots.  The smallest N that gets there with a partly filled wave.
+CENTRE_SWEEP_N = 4096 * 256 + 65
+MANY_IDS_B = 70
+
+
+def make_coors_many_ids(dtype=torch.int32, shift=0):
+    """(2049, 4) rows whose batch id is (row + shift) % 72 - 1: -1 .. 70 with B = 70, so -1 and 70 are counted nowhere and a wave of 64
+    consecutive rows holds 62 or 63 DISTINCT counted ids (a wave starts on a multiple of 8 of the cycle, so it always meets -1 or 70)
+    — with shift = 1 the first wave holds ids 0 .. 63: the kernel's ballot loop, once per distinct id, runs its full 64 times"""
+    c = make_coors(2049, 3, 4242, torch.int64, stray=False)
+    c[:, 0] = (torch.arange(2049) + shift) % (MANY_IDS_B + 2) - 1
+    per_wave = [len(set(v for v in c[w:w + 64, 0].tolist() if 0 <= v < MANY_IDS_B)) for w in range(0, 2048, 64)]
+    assert max(per_wave) == (64 if shift == 1 else 63) and min(per_wave) >= 62
+    assert int((c[:, 0] == -1).sum()) > 0 and int((c[:, 0] == MANY_IDS_B).sum()) > 0
+    return c.to(dtype)
 
 
 def make_coors(n, batch_size, seed, dtype=torch.int32, stray=True):
