@@ -982,6 +982,60 @@ int gd3d_vsa_voxel_centers_cpu(const void* coors, int32_t coors_is_int64, int64_
                                const float* range_min, const float* add, int32_t batch_size, float* xyz,
                                int32_t* xyz_batch_cnt);
 
+/* ------------------------------------------------------------------------------------
+ * Hard voxelization, dynamic voxelization and the mean voxel encoder (an addition inside ABI 6): PVRCNN.voxelize and the
+ * HardSimpleVFE call of extract_feat (models/detectors/pv_rcnn.py:43-49, 66-86) — mmdet3d's `Voxelization` op per sample, a cat, an
+ * F.pad per sample and a host read of coors[-1, 0] — for the whole stacked batch in one stream-ordered call that reads nothing back.
+ * mmdet3d is not pinned by the reference; its published `hard_voxelize` is restated here, in the DETERMINISTIC order of its CPU op
+ * and of its deterministic=True GPU path (deterministic=False only means that its fast path returns some arbitrary order).
+ *
+ * Operands: points (N, >= C) fp32, row i at points + i * row_stride, columns 0, 1, 2 = x, y, z; points_batch_cnt (B) int32: the
+ * stack's rows per sample, in order (negative counts count as 0; rows past the last sample belong to no sample and are dropped).
+ * voxel_size, range_min (3 floats, x y z) and grid_size (3 int32, x y z) lie in HOST memory and are read during the call; the caller
+ * computes grid_size = round((range_max - range_min) / voxel_size) in fp32 as mmdet3d's module does.
+ * The cell of a point on axis j, in fp32, one operation per step, no contraction, correctly rounded division:
+ *     f_j = floor((p_j - range_min_j) / voxel_size_j);   kept iff f_j >= 0 && f_j < (float)grid_j on all three axes,
+ * compared as FLOATS before any conversion: NaN, +-inf and 1e30 are dropped and no conversion overflows.
+ * gd3d_hard_voxelize : walk the kept points of each sample in index order: a cell not seen before becomes the sample's next voxel
+ *   if fewer than max_voxels are numbered, else the point is skipped (a `continue`: later points of numbered voxels still join them);
+ *   a point joins slot num_points[v] of its voxel if that is < max_num_points, else it is skipped.  Outputs, each of
+ *   R = min(N, B * max_voxels) rows, the samples' voxels one after the other as torch.cat lays them:
+ *     voxels (R, max_num_points, C) fp32, nullable: columns 0 .. C-1 of the point in each slot, unused slots 0;
+ *     coors (R, 4) int32: (b, z, y, x);   num_points (R) int32;
+ *     mean (R, num_features) fp32, nullable: HardSimpleVFE — per column, slots 0, 1, 2, .. of the voxel added IN SEQUENCE to +0 in
+ *       fp32, then ONE division by num_points (the unused slots are zeros and are not added: the same bits);
+ *     voxel_batch_cnt (B) int32: voxels per sample;   num (2) int64: [0] the total V, [1] the dropped points (outside the grid, non-
+ *       finite or of no sample; points skipped by the two limits are not counted).
+ *   Rows at and past V: coors -1, num_points 0, voxels and mean 0.  workspace: gd3d_hard_voxelize_workspace_bytes(N, B, max_voxels)
+ *   bytes, 256-byte aligned.  C == 4 with row_stride % 4 == 0 and 16-byte aligned points / voxels / mean takes 16-byte row accesses,
+ *   everything else 4-byte ones: the same bits.  max_num_points < 1, max_voxels < 1, C < 3, row_stride < C, num_features outside
+ *   [1, C] with a mean: GD3D_E_BADARG; N > 2^31 - 1, a grid axis > 2^24, B * cells >= 2^62, B > 1024, C > 256: GD3D_E_TOOLARGE.
+ *   N == 0 or B == 0 writes the zero counts only.
+ * gd3d_dynamic_voxelize : coors (N, 4) int32 = (b, z, y, x) of every point, all -1 for a dropped one, in one launch: the `coors`
+ *   operand of vox_index_build.
+ * gd3d_voxel_mean : the encoder alone on caller-held voxels (V, P, C) and num_points (V) -> mean (V, num_features): the first
+ *   min(max(num_points, 0), P) slots added in sequence as above (slots past num_points are not read); num_points == 0 gives 0.
+ * `_cpu` twins (csrc/hard_voxel_cpu.cpp): the same contracts on HOST memory on the calling thread, the hard one as the sequential
+ *   walk above over a hash map; `workspace` is ignored.  Every output is BIT-IDENTICAL to the kernels'.
+ * ---------------------------------------------------------------------------------- */
+size_t gd3d_hard_voxelize_workspace_bytes(int64_t N, int32_t B, int32_t max_voxels);
+int gd3d_hard_voxelize(const float* points, int64_t N, int64_t row_stride, int32_t C, const int32_t* points_batch_cnt, int32_t B,
+                       const float* voxel_size, const float* range_min, const int32_t* grid_size, int32_t max_num_points,
+                       int32_t max_voxels, int32_t num_features, void* workspace, float* voxels, float* mean, int32_t* coors,
+                       int32_t* num_points, int32_t* voxel_batch_cnt, int64_t* num, void* stream);
+int gd3d_dynamic_voxelize(const float* points, int64_t N, int64_t row_stride, const int32_t* points_batch_cnt, int32_t B,
+                          const float* voxel_size, const float* range_min, const int32_t* grid_size, int32_t* coors, void* stream);
+int gd3d_voxel_mean(const float* voxels, const int32_t* num_points, int64_t V, int32_t P, int32_t C, int32_t num_features,
+                    float* mean, void* stream);
+int gd3d_hard_voxelize_cpu(const float* points, int64_t N, int64_t row_stride, int32_t C, const int32_t* points_batch_cnt, int32_t B,
+                           const float* voxel_size, const float* range_min, const int32_t* grid_size, int32_t max_num_points,
+                           int32_t max_voxels, int32_t num_features, void* workspace, float* voxels, float* mean, int32_t* coors,
+                           int32_t* num_points, int32_t* voxel_batch_cnt, int64_t* num);
+int gd3d_dynamic_voxelize_cpu(const float* points, int64_t N, int64_t row_stride, const int32_t* points_batch_cnt, int32_t B,
+                              const float* voxel_size, const float* range_min, const int32_t* grid_size, int32_t* coors);
+int gd3d_voxel_mean_cpu(const float* voxels, const int32_t* num_points, int64_t V, int32_t P, int32_t C, int32_t num_features,
+                        float* mean);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

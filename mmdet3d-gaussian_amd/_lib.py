@@ -285,6 +285,13 @@ SYMBOLS = {
     'gd3d_vsa_bev_interp_cpu': (_int, [_vp, _i64, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp]),
     'gd3d_vsa_bev_interp_backward_cpu': (_int, [_vp, _vp, _i64, _i64, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp]),
     'gd3d_vsa_voxel_centers_cpu': (_int, [_vp, _i32, _i64, _vp, _f32, _vp, _vp, _i32, _vp, _vp]),
+    'gd3d_hard_voxelize_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'gd3d_hard_voxelize': (_int, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_dynamic_voxelize': (_int, [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_voxel_mean': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    'gd3d_hard_voxelize_cpu': (_int, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_dynamic_voxelize_cpu': (_int, [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'gd3d_voxel_mean_cpu': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 
