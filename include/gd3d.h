@@ -1036,6 +1036,65 @@ int gd3d_dynamic_voxelize_cpu(const float* points, int64_t N, int64_t row_stride
 int gd3d_voxel_mean_cpu(const float* voxels, const int32_t* num_points, int64_t V, int32_t P, int32_t C, int32_t num_features,
                         float* mean);
 
+/* ------------------------------------------------------------------------------------
+ * The pillar encoders' point decoration (an addition inside ABI 6): what the pillar detectors run between voxelization and their
+ * first nn.Linear.  No gradient (the inputs are raw points), no float atomics, no host read; every output element is written exactly
+ * once.  Every multiply, add, subtract, divide and root below is ONE correctly rounded fp32 operation, never contracted.
+ * voxel_size and offset (3 floats each, x y z) lie in HOST memory and are read during the call; the caller computes
+ * offset_k = voxel_size_k / 2 + range_min_k in double and rounds it once.
+ *
+ * gd3d_point_voxel_stats : PointVoxelStatsCalculator.forward (models/voxel_encoders/utils.py:48-89) and the cat of
+ *   DynamicPillarFeatureNet.forward (pillar_encoder.py:215-216), two launches (one when no flag needs the table).
+ *   points (N, >= C) fp32, row i at points + i * row_stride, columns 0, 1, 2 = x, y, z.  coors (N, ndim) int32 or int64
+ *   (coors_is_int64), 3 <= ndim <= 8: the last three columns are z, y, x.  map (N) / counts (V) / order (N) / seg (V + 1): what
+ *   vox_index_build returns — the voxel of each point (-1, or anything outside [0, V): a dropped point), the points per voxel, the
+ *   point ids grouped by voxel in ascending id, and the bounds of each voxel's run in `order`.
+ *   Output row i at out + i * out_stride, the columns in this order, each group present iff its flag is set:
+ *     3  always                    x, y, z
+ *     3  GD3D_PVS_CLUSTER_CENTER   c = the mean of the xyz rows of the point's voxel: the voxel's points in ascending point index
+ *                                  added IN SEQUENCE to +0, then ONE division by (float)count — the bits of vox_scatter_reduce's mean
+ *     3  GD3D_PVS_CLUSTER_OFFSET   d = xyz - c
+ *     9  GD3D_PVS_COVARIANCE       at 3a + b the mean, same sequence, of d_a * d_b, d taken from the ROUNDED c (two passes)
+ *     3  GD3D_PVS_VOXEL_CENTER     ctr_k = (float)coor_k * voxel_size_k + offset_k, x y z from coors columns -1, -2, -3
+ *     3  GD3D_PVS_VOXEL_OFFSET     xyz - ctr
+ *     1  GD3D_PVS_POINT_COUNT      (float)count of the point's voxel
+ *   C-3  GD3D_PVS_APPEND           columns 3 .. C-1 of the point copied through
+ *   A dropped point gets c = +0, d = xyz - 0, covariance +0, count 0, and ctr from ITS OWN coors row, whatever it holds.  NaN and inf
+ *   propagate as written: a NaN point poisons the means of its own voxel only.
+ *   table: V * (12 with the covariance, else 3) floats of workspace (voxel row: mean xyz, then the covariance); NULL when neither of
+ *   the first three flags is set.  16-byte stores where out is 16-byte aligned and either contiguous (out_stride == width) or both the
+ *   width and out_stride are multiples of 4; 4-byte stores otherwise: the same bits.
+ *   C < 3, row_stride < C, ndim < 3, out_stride < width, an unknown flag, V > N: GD3D_E_BADARG; N > 2^31 - 1, C > 256, ndim > 8:
+ *   GD3D_E_TOOLARGE.
+ * gd3d_pillar_decorate : the decoration of PillarFeatureNet.forward (pillar_encoder.py:105-153, legacy=False), one launch.
+ *   features (V, P, C) fp32, num_points (V) int32, coors (V, 4) int32 = (b, z, y, x) -> out (V, P, width), width = C +
+ *   3 (GD3D_PD_CLUSTER_CENTER) + 3 (GD3D_PD_VOXEL_CENTER) + 1 (GD3D_PD_DISTANCE).  For slots p < n = min(max(num_points, 0), P): the C
+ *   columns copied; xyz - mean, the mean being slots 0, 1, 2, .. added in sequence to +0, then one division by (float)n
+ *   (gd3d_voxel_mean's sequence); xyz - ((float)coor * voxel_size + offset) with x, y, z from coors columns 3, 2, 1;
+ *   sqrt((x*x + y*y) + z*z).  Every other slot is written as +0 and its input is NOT read (the reference multiplies by a 0 / 1 mask:
+ *   -0, or NaN for garbage and for voxels without points).  P < 1, C < 3, an unknown flag: GD3D_E_BADARG; V > 2^31 - 1, C > 256,
+ *   P * (C + 7) > 2^30: GD3D_E_TOOLARGE.
+ * `_cpu` twins (csrc/pillar_feat_cpu.cpp): the same contracts on HOST memory on the calling thread; every output is BIT-IDENTICAL to
+ *   the kernels' (NaN payloads aside).
+ * ---------------------------------------------------------------------------------- */
+enum {
+  GD3D_PVS_CLUSTER_CENTER = 1, GD3D_PVS_CLUSTER_OFFSET = 2, GD3D_PVS_COVARIANCE = 4, GD3D_PVS_VOXEL_CENTER = 8,
+  GD3D_PVS_VOXEL_OFFSET = 16, GD3D_PVS_POINT_COUNT = 32, GD3D_PVS_APPEND = 64, GD3D_PVS_ALL = 127
+};
+enum { GD3D_PD_CLUSTER_CENTER = 1, GD3D_PD_VOXEL_CENTER = 2, GD3D_PD_DISTANCE = 4, GD3D_PD_ALL = 7 };
+int gd3d_point_voxel_stats(const float* points, int64_t N, int64_t row_stride, int32_t C, const void* coors, int32_t coors_is_int64,
+                           int32_t ndim, const int32_t* map, const int32_t* counts, const int32_t* order, const int32_t* seg,
+                           int64_t V, const float* voxel_size, const float* offset, int32_t flags, float* table, float* out,
+                           int64_t out_stride, void* stream);
+int gd3d_pillar_decorate(const float* features, const int32_t* num_points, const int32_t* coors, int64_t V, int32_t P, int32_t C,
+                         const float* voxel_size, const float* offset, int32_t flags, float* out, void* stream);
+int gd3d_point_voxel_stats_cpu(const float* points, int64_t N, int64_t row_stride, int32_t C, const void* coors,
+                               int32_t coors_is_int64, int32_t ndim, const int32_t* map, const int32_t* counts, const int32_t* order,
+                               const int32_t* seg, int64_t V, const float* voxel_size, const float* offset, int32_t flags,
+                               float* table, float* out, int64_t out_stride);
+int gd3d_pillar_decorate_cpu(const float* features, const int32_t* num_points, const int32_t* coors, int64_t V, int32_t P, int32_t C,
+                             const float* voxel_size, const float* offset, int32_t flags, float* out);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

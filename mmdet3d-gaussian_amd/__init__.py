@@ -26,6 +26,9 @@
   * ``hard_voxelize`` / ``dynamic_voxelize`` / ``Voxelization`` / ``HardSimpleVFE`` / ``voxel_mean`` / ``pvrcnn_voxelize`` — the first
                                  stage: mmdet3d's hard Voxelization op and the mean voxel encoder for the whole batch in one
                                  stream-ordered call (pv_rcnn.py:43-49, 66-86), in the deterministic first-appearance order
+  * ``point_voxel_stats`` / ``PointVoxelStatsCalculator`` / ``pillar_decorate`` / ``PillarFeatureDecorator`` — the pillar encoders'
+                                 point decoration between voxelization and the first nn.Linear (voxel_encoders/utils.py:48-89,
+                                 pillar_encoder.py:105-153, 214-216): two launches and one, fixed fp32 sequences
   * ``GraphedStep``            — a launch-bound loss slice, forward and backward, captured once as a hipGraph and replayed
 Everything outside §8 that earlier rounds built (frozen, DESIGN_EXTRAS.md) lives in ``mmdet3d_gaussian_amd.extras``.
 
@@ -54,6 +57,7 @@ from .pvrcnn_sample import bbox_overlaps_3d, pvrcnn_assign_and_sample
 from .pvrcnn_seg import keypoint_reweight, pvrcnn_seg_loss
 from .vsa_bev import bev_interpolate, sample_keypoints, voxel_centers
 from .voxelize import HardSimpleVFE, Voxelization, dynamic_voxelize, hard_voxelize, pvrcnn_voxelize, voxel_mean
+from .pillar_feat import PillarFeatureDecorator, PointVoxelStatsCalculator, pillar_decorate, point_voxel_stats
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
                         anchor_head_decoded_loss_fused, center_head_gd_loss, center_head_losses)
 from . import extras
@@ -77,4 +81,5 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'points_in_boxes_part_stacked', 'points_in_boxes_all_stacked', 'pointwise_mask_targets', 'roi_grid_points', 'roi_grid_queries',
            'pvrcnn_head_get_targets', 'pvrcnn_head_loss', 'bbox_overlaps_3d', 'pvrcnn_assign_and_sample', 'pvrcnn_seg_loss',
            'keypoint_reweight', 'bev_interpolate', 'voxel_centers', 'sample_keypoints', 'hard_voxelize', 'dynamic_voxelize', 'Voxelization',
-           'HardSimpleVFE', 'voxel_mean', 'pvrcnn_voxelize', 'extras']
+           'HardSimpleVFE', 'voxel_mean', 'pvrcnn_voxelize', 'point_voxel_stats', 'PointVoxelStatsCalculator',
+           'pillar_decorate', 'PillarFeatureDecorator', 'extras']

@@ -292,6 +292,10 @@ SYMBOLS = {
     'gd3d_hard_voxelize_cpu': (_int, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gd3d_dynamic_voxelize_cpu': (_int, [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     'gd3d_voxel_mean_cpu': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    'gd3d_point_voxel_stats': (_int, [_vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _vp]),
+    'gd3d_pillar_decorate': (_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    'gd3d_point_voxel_stats_cpu': (_int, [_vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64]),
+    'gd3d_pillar_decorate_cpu': (_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 
