@@ -1095,6 +1095,95 @@ int gd3d_point_voxel_stats_cpu(const float* points, int64_t N, int64_t row_strid
 int gd3d_pillar_decorate_cpu(const float* features, const int32_t* num_points, const int32_t* coors, int64_t V, int32_t P, int32_t C,
                              const float* voxel_size, const float* offset, int32_t flags, float* out);
 
+/* ------------------------------------------------------------------------------------
+ * The multi-view pillar encoder's view ops (an addition inside ABI 6): PillarODCenterPoint.voxelize / voxelize_view with the
+ * to_cylindrical / to_spherical transforms (models/detectors/pillar_od.py:24-70), mmdet3d's PointPillarsScatter (restated: mmdet3d is
+ * not pinned) and the per-sample grid_sample loop of SingleViewNet.forward (models/voxel_encoders/pillar_mvf_encoder.py:88-105).  No
+ * host read-back.  Every multiply, add, subtract, divide and root below is ONE correctly rounded fp32 operation, never contracted.
+ *
+ * gd3d_multi_view_voxelize : one launch; every point is read once and all views are written.
+ *   points (N, >= C) fp32, row i at points + i * row_stride, columns 0, 1, 2 = x, y, z; points_batch_cnt (B) int32 as for
+ *   gd3d_hard_voxelize.  Per view k < num_views (1 .. 4), in HOST memory, read during the call: view_kinds[k] = GD3D_VIEW_*,
+ *   voxel_sizes / range_mins / grid_sizes (3 values per view: x y z of the TRANSFORMED coordinates; grid as for gd3d_hard_voxelize),
+ *   view_points[k] (N, C) fp32 or NULL, view_coors[k] (N, 4) int32 or NULL (the three geometry arrays may be NULL when every
+ *   view_coors[k] is).  The transformed point (t0, t1, t2):
+ *     cartesian   : (x, y, z)
+ *     cylindrical : s = x*x + y*y;  rho = sqrtf(s);  phi = fx_atan2f(y, x)                                -> (phi, z, rho)
+ *     spherical   : s2 = x*x + y*y;  r2 = sqrtf(s2);  rho = sqrtf(s2 + z*z);  yaw = fx_atan2f(y, x);
+ *                   pitch = fx_atan2f(z, r2)                                                               -> (yaw, pitch, rho)
+ *   fx_atan2f is the library's fixed-sequence polynomial (csrc/rbox_device.h), the same on both targets; fx_atan2f(0, 0) = 0.  The
+ *   reference's pitch is asin(z / rho) — the same angle, NaN at the origin where this form gives 0: restated, not matched.
+ *   view_points row i = (t0, t1, t2, columns 3 .. C-1 of the point copied).  view_coors row i = [b, z, y, x] with b the row's sample
+ *   and the cell f_j = floor((t_j - range_min_j) / voxel_size_j) of gd3d_hard_voxelize, kept iff 0 <= f_j < grid_j on all three axes,
+ *   compared as floats before any conversion; a dropped point (outside the grid, or a non-finite transformed coordinate) is
+ *   [b, -1, -1, -1] — the reference's F.pad writes the id into every row of a sample — and only a row of NO sample (past the counts'
+ *   sum) is all -1.  NOT gd3d_dynamic_voxelize's layout, which is all -1 for every dropped point.  For a row with a non-finite input
+ *   coordinate the three transformed values are unspecified, its coors are [b, -1, -1, -1], its trailing columns are copied.
+ *   num_views outside [1, 4], an unknown kind, C < 3, row_stride < C: GD3D_E_BADARG; N > 2^31 - 1, C > 256, B > 1024, a grid axis >
+ *   2^24: GD3D_E_TOOLARGE.  N == 0 launches nothing.
+ * gd3d_pillar_scatter : canvas (B, C, ny, nx) fp32 in `layout` (0: contiguous NCHW, 1: channels last) = zeros, then
+ *   canvas[b, :, y, x] = voxel_features (V, C)[v] for every row v of coors (V, coors_cols) int32 / int64: coors_cols 4 = [b, z, y, x],
+ *   3 = [z, y, x] with b = 0 (B must be 0 or 1).  z is not read.  A row with b outside [0, B), y outside [0, ny) or x outside [0, nx)
+ *   is skipped.  A fill and one launch; every element is written.  Rows must be unique per (b, y, x): the value at a duplicated cell
+ *   is one of its rows (the twin: the last).  Channels last with C % 4 == 0 and 16-byte aligned bases takes 16-byte accesses,
+ *   everything else 4-byte ones; NCHW stages 64 voxels x 64 channels through LDS.  The same values in every form.
+ *   ny, nx >= 1, C >= 1 (GD3D_E_BADARG); V > 2^31 - 1, ny or nx > 2^24 (GD3D_E_TOOLARGE).  B == 0 launches nothing, V == 0 only the fill.
+ * gd3d_pillar_scatter_backward : grad_features (V, C)[v] = grad_canvas[b, :, y, x], zeros for a skipped row: one launch, a gather, no
+ *   atomics; every element is written.
+ * gd3d_view_sample : out (N, C) fp32 contiguous = the bilinear sample of view_map (B, C, H, W) fp32 in `layout` at each point's xy —
+ *   grid_sample(align_corners=False, padding_mode='zeros') on the reference's grid, for all samples in one launch.  Point n: x, y at
+ *   pts_xyz[n * xyz_stride + 0 | 1]; its sample at ids[n * id_stride] (int32, or int64 with ids_is_int64) — column 0 of the (N, 4)
+ *   coors with id_stride 4, or an id vector with id_stride 1.  half_x = (float)((hi_x - lo_x) / 2.0) computed by the caller in double
+ *   and rounded once; likewise half_y.  Per point, per axis (n = W for x, H for y):
+ *     g   = (v - lo) / half - 1
+ *     pix = ((g + 1) * (float)n - 1) / 2
+ *   reach = ix > -1 && ix < (float)W && iy > -1 && iy < (float)H && 0 <= id < B     (floats compared BEFORE any conversion)
+ *     x0 = floor(ix), x1 = x0 + 1, y0 = floor(iy), y1 = y0 + 1
+ *     w_nw = (x1 - ix) * (y1 - iy),  w_ne = (ix - x0) * (y1 - iy),  w_sw = (x1 - ix) * (iy - y0),  w_se = (ix - x0) * (iy - y0)
+ *     out[c] = ((v_nw*w_nw + v_ne*w_ne) + v_sw*w_sw) + v_se*w_se, the value of a cell outside the map being 0.
+ *   Without reach (outside, a non-finite coordinate, an id outside [0, B)) the row is 0 — for the id case the reference leaves
+ *   uninitialised memory: restated, not matched.  No index leaves the map for any input.  H, W >= 1, half > 0 and finite, C >= 1,
+ *   strides >= 0 (GD3D_E_BADARG); N > 2^31 - 1, H or W > 2^24 (GD3D_E_TOOLARGE).  Channels last with C % 4 == 0 and 16-byte aligned
+ *   view_map / out takes 16-byte accesses, everything else 4-byte ones: the same bits, and the same bits for both layouts.
+ * gd3d_view_sample_backward : grad_map (B, C, H, W) in `layout` = sum over the points of grad_out (N, C)[n, c] * weight into the (at
+ *   most four) cells in the map; EVERY element is written.  A fill and one launch of fp32 atomic adds, lanes along C: where several
+ *   points share a cell the last bits depend on the order of arrival.  workspace: NULL, or B*C*H*W floats; with layout 0 and a
+ *   workspace the sums are made in the workspace in channels-last order (256 contiguous bytes per wave-instruction at C = 64) and one
+ *   tiled transpose then writes every element of the NCHW gradient (three launches).  No gradient for the points.  B == 0 launches
+ *   nothing, N == 0 only the fill.
+ * `_cpu` twins (csrc/view_net_cpu.cpp): the same contracts on HOST memory on the calling thread; every output BIT-IDENTICAL to the
+ *   kernels', except the sampling backward, which is sequential (points in order, neighbours nw, ne, sw, se); workspace is ignored.
+ * ---------------------------------------------------------------------------------- */
+enum { GD3D_VIEW_CARTESIAN = 0, GD3D_VIEW_CYLINDRICAL = 1, GD3D_VIEW_SPHERICAL = 2 };
+int gd3d_multi_view_voxelize(const float* points, int64_t N, int64_t row_stride, int32_t C, const int32_t* points_batch_cnt, int32_t B,
+                             int32_t num_views, const int32_t* view_kinds, const float* voxel_sizes, const float* range_mins,
+                             const int32_t* grid_sizes, float* const* view_points, int32_t* const* view_coors, void* stream);
+int gd3d_pillar_scatter(const float* voxel_features, const void* coors, int32_t coors_is_int64, int32_t coors_cols, int32_t layout,
+                        int64_t V, int64_t C, int64_t B, int64_t ny, int64_t nx, float* canvas, void* stream);
+int gd3d_pillar_scatter_backward(const float* grad_canvas, const void* coors, int32_t coors_is_int64, int32_t coors_cols,
+                                 int32_t layout, int64_t V, int64_t C, int64_t B, int64_t ny, int64_t nx, float* grad_features,
+                                 void* stream);
+int gd3d_view_sample(const float* pts_xyz, int64_t xyz_stride, const void* ids, int32_t ids_is_int64, int64_t id_stride,
+                     const float* view_map, int32_t layout, int64_t N, int64_t B, int64_t C, int64_t H, int64_t W, float lo_x,
+                     float half_x, float lo_y, float half_y, float* out, void* stream);
+int gd3d_view_sample_backward(const float* grad_out, const float* pts_xyz, int64_t xyz_stride, const void* ids, int32_t ids_is_int64,
+                              int64_t id_stride, int32_t layout, int64_t N, int64_t B, int64_t C, int64_t H, int64_t W, float lo_x,
+                              float half_x, float lo_y, float half_y, float* workspace, float* grad_map, void* stream);
+int gd3d_multi_view_voxelize_cpu(const float* points, int64_t N, int64_t row_stride, int32_t C, const int32_t* points_batch_cnt,
+                                 int32_t B, int32_t num_views, const int32_t* view_kinds, const float* voxel_sizes,
+                                 const float* range_mins, const int32_t* grid_sizes, float* const* view_points,
+                                 int32_t* const* view_coors);
+int gd3d_pillar_scatter_cpu(const float* voxel_features, const void* coors, int32_t coors_is_int64, int32_t coors_cols, int32_t layout,
+                            int64_t V, int64_t C, int64_t B, int64_t ny, int64_t nx, float* canvas);
+int gd3d_pillar_scatter_backward_cpu(const float* grad_canvas, const void* coors, int32_t coors_is_int64, int32_t coors_cols,
+                                     int32_t layout, int64_t V, int64_t C, int64_t B, int64_t ny, int64_t nx, float* grad_features);
+int gd3d_view_sample_cpu(const float* pts_xyz, int64_t xyz_stride, const void* ids, int32_t ids_is_int64, int64_t id_stride,
+                         const float* view_map, int32_t layout, int64_t N, int64_t B, int64_t C, int64_t H, int64_t W, float lo_x,
+                         float half_x, float lo_y, float half_y, float* out);
+int gd3d_view_sample_backward_cpu(const float* grad_out, const float* pts_xyz, int64_t xyz_stride, const void* ids,
+                                  int32_t ids_is_int64, int64_t id_stride, int32_t layout, int64_t N, int64_t B, int64_t C, int64_t H,
+                                  int64_t W, float lo_x, float half_x, float lo_y, float half_y, float* workspace, float* grad_map);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

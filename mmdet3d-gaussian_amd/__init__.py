@@ -29,6 +29,9 @@
   * ``point_voxel_stats`` / ``PointVoxelStatsCalculator`` / ``pillar_decorate`` / ``PillarFeatureDecorator`` — the pillar encoders'
                                  point decoration between voxelization and the first nn.Linear (voxel_encoders/utils.py:48-89,
                                  pillar_encoder.py:105-153, 214-216): two launches and one, fixed fp32 sequences
+  * ``multi_view_voxelize`` / ``to_cylindrical`` / ``to_spherical`` / ``pillar_scatter`` / ``PointPillarsScatter`` / ``view_sample`` — the
+                                 multi-view pillar encoder's view ops (pillar_od.py:24-70, pillar_mvf_encoder.py:80-107): every view's
+                                 transform and cells in one launch, the dense pillar canvas, the per-point view-map sampling
   * ``GraphedStep``            — a launch-bound loss slice, forward and backward, captured once as a hipGraph and replayed
 Everything outside §8 that earlier rounds built (frozen, DESIGN_EXTRAS.md) lives in ``mmdet3d_gaussian_amd.extras``.
 
@@ -58,6 +61,7 @@ from .pvrcnn_seg import keypoint_reweight, pvrcnn_seg_loss
 from .vsa_bev import bev_interpolate, sample_keypoints, voxel_centers
 from .voxelize import HardSimpleVFE, Voxelization, dynamic_voxelize, hard_voxelize, pvrcnn_voxelize, voxel_mean
 from .pillar_feat import PillarFeatureDecorator, PointVoxelStatsCalculator, pillar_decorate, point_voxel_stats
+from .view_net import PointPillarsScatter, multi_view_voxelize, pillar_scatter, to_cylindrical, to_spherical, view_sample
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
                         anchor_head_decoded_loss_fused, center_head_gd_loss, center_head_losses)
 from . import extras
@@ -82,4 +86,5 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'pvrcnn_head_get_targets', 'pvrcnn_head_loss', 'bbox_overlaps_3d', 'pvrcnn_assign_and_sample', 'pvrcnn_seg_loss',
            'keypoint_reweight', 'bev_interpolate', 'voxel_centers', 'sample_keypoints', 'hard_voxelize', 'dynamic_voxelize', 'Voxelization',
            'HardSimpleVFE', 'voxel_mean', 'pvrcnn_voxelize', 'point_voxel_stats', 'PointVoxelStatsCalculator',
-           'pillar_decorate', 'PillarFeatureDecorator', 'extras']
+           'pillar_decorate', 'PillarFeatureDecorator', 'multi_view_voxelize', 'to_cylindrical', 'to_spherical', 'pillar_scatter',
+           'PointPillarsScatter', 'view_sample', 'extras']

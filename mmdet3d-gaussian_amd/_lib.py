@@ -296,6 +296,18 @@ SYMBOLS = {
     'gd3d_pillar_decorate': (_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     'gd3d_point_voxel_stats_cpu': (_int, [_vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64]),
     'gd3d_pillar_decorate_cpu': (_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp]),
+    'gd3d_multi_view_voxelize': (_int, [_vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_pillar_scatter': (_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    'gd3d_pillar_scatter_backward': (_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    'gd3d_view_sample': (_int, [_vp, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp, _vp]),
+    'gd3d_view_sample_backward': (_int, [_vp, _vp, _i64, _vp, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp,
+                                         _vp, _vp]),
+    'gd3d_multi_view_voxelize_cpu': (_int, [_vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_pillar_scatter_cpu': (_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _vp]),
+    'gd3d_pillar_scatter_backward_cpu': (_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _vp]),
+    'gd3d_view_sample_cpu': (_int, [_vp, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp]),
+    'gd3d_view_sample_backward_cpu': (_int, [_vp, _vp, _i64, _vp, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp,
+                                             _vp]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 
