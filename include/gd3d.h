@@ -1184,6 +1184,64 @@ int gd3d_view_sample_backward_cpu(const float* grad_out, const float* pts_xyz, i
                                   int32_t ids_is_int64, int64_t id_stride, int32_t layout, int64_t N, int64_t B, int64_t C, int64_t H,
                                   int64_t W, float lo_x, float half_x, float lo_y, float half_y, float* workspace, float* grad_map);
 
+/* ------------------------------------------------------------------------------------
+ * The SimOTA BEV assigner (an addition inside ABI 6): SimOTABEVAssigner.assign (core/bbox/assigners/sim_ota_3d_assigner.py:34-211)
+ * for a whole batch as a fill and three launches — no host read, no data-dependent allocation, no priors x gts matrix in memory,
+ * the same under graph capture and replay, independent of the workgroup schedule.  Every multiply, add, subtract, divide and root
+ * below is ONE correctly rounded fp32 operation, never contracted; sin / cos / atan2 / log are the library's fixed polynomial
+ * sequences (fx_sincosf, fx_atan2f: csrc/rbox_device.h; fx_logf: csrc/fx_log.h), the same on both targets.
+ *   fx_logf: exponent extraction, s = f / (2 + f), a degree-4 polynomial in s^2.  Against fp64 log, correctly rounded, on 2^20
+ *   log-uniform values of [1e-8, 2], every binade edge and the 4096 values next below 1: at most 0.80 ulp (measured 0.795; the host
+ *   libm's logf on the same sample: 0.795).
+ *
+ * Stacked operands: pred_scores (P, C) probabilities, decoded_bboxes (P, 7), gt_bboxes (G, 7) rows [x, y, z, dx, dy, dz, yaw] with z
+ * the BOTTOM face, gt_labels (G) int64; prior_batch_cnt / gt_batch_cnt (B) int32 on the device cut the rows into samples, every
+ * count clamped to the rows left and never read back; rows past the counts' sum belong to no sample (all background).  priors:
+ * row r at priors + r * prior_stride, columns 0 and 1 = x, y.  shared_priors 0: prior_rows == P, one row per stacked row;
+ * shared_priors 1: ONE grid of prior_rows rows for every sample, prior n of a sample reads row n (a sample's rows past prior_rows
+ * are background).  Of a sample's gts only the first G_cap take part.
+ * Per sample, prior p (index within the sample) and gt g:
+ *   1. in_gt = the x / y part of the points-in-boxes test (gd3d_pib_all) on the gt's BEV rectangle: sx = x - gx, sy = y - gy,
+ *      (s, c) = fx_sincosf(-yaw), lx = sx*c + sy*(-s), ly = sx*s + sy*c, |lx| < dx/2 and |ly| < dy/2 STRICTLY; z is not read.
+ *      in_ct = |x - gx| < center_radius and |y - gy| < center_radius.  A NaN coordinate is in nothing.  (A yaw of NaN or +-inf: in
+ *      nothing, no overlap.  A finite |yaw| beyond 2^31 quarter turns leaves fx_sincosf's quadrant unspecified.)
+ *      p is a CANDIDATE when some g has in_gt | in_ct; V = the sample's candidates.  both = in_gt & in_ct.
+ *   2. iou = the bits of gd3d_roi_iou3d(decoded[p], gt[g]), NaN and negative values mapped to +0.
+ *   3. cls = the sum over c = 0 .. C-1, ascending, into +0 of -(t*max(fx_logf(s), -100) + (1 - t)*max(fx_logf(1 - s), -100)),
+ *      s = sqrtf(score clamped into [0, 1], NaN to 0), t = 1 if c == label[g] else 0 (a label outside [0, C): t = 0 throughout).
+ *   4. cost = cls*cls_weight + (-fx_logf(iou + 1e-8f))*iou_weight; where `both`: cost < match_init ? cost : match_init (so a NaN
+ *      cost becomes match_init there).
+ *   5. K = min(candidate_topk, V); sum = the K largest iou of g over the candidates, added in descending order to +0;
+ *      k = 1 if !(sum >= 1), K if sum >= K, else (int)sum.
+ *   6. g takes the k candidates of smallest cost: costs ordered as fp32 values with -0 == +0 and NaN above everything, ties to the
+ *      LOWER prior index.
+ *   7. a prior taken by more than one gt goes to the gt of smallest cost over ALL (first G_cap) gts of the sample, ties to the LOWER
+ *      gt index.
+ * Outputs, EVERY element written by every call: gt_inds (P) int64 0 = background, g + 1 otherwise (g within the sample); labels (P)
+ * int64 = label[g] or -1; max_overlaps (P) = iou with the assigned gt or -1e8; pos_cnt (B) int32; pos_inds / pos_gt_inds
+ * (B, G_cap * candidate_topk) int64: the sample's positives in ascending prior index as ROWS of the stacked operands
+ * (decoded_bboxes[pos_inds], gt_bboxes[pos_gt_inds]), padded with -1.  A sample without gts, priors or candidates is background.
+ * workspace: gd3d_simota_workspace_bytes(P, B, G_cap, candidate_topk) bytes, O(P + B * G_cap * candidate_topk), from shapes alone;
+ * the call writes nothing outside it.  B < 1, C < 1, candidate_topk < 1, prior_stride < 2, a NaN parameter, prior_rows != P
+ * without shared_priors, a short workspace: GD3D_E_BADARG.  P, G > 2^24, B > 1024, C > 32, candidate_topk > 32, G_cap > 1024,
+ * G_cap * candidate_topk > 16384: GD3D_E_TOOLARGE.
+ * `_cpu` twin (csrc/simota_cpu.cpp): the same contract on HOST memory on the calling thread, every output BIT-IDENTICAL to the
+ *   kernels'; workspace is ignored.
+ * ---------------------------------------------------------------------------------- */
+size_t gd3d_simota_workspace_bytes(int64_t P, int32_t B, int32_t G_cap, int32_t candidate_topk);
+int gd3d_simota_assign(const float* pred_scores, const float* decoded_bboxes, const float* priors, int64_t prior_rows,
+                       int64_t prior_stride, int32_t shared_priors, const int32_t* prior_batch_cnt, int64_t P, const float* gt_bboxes,
+                       const int64_t* gt_labels, const int32_t* gt_batch_cnt, int64_t G, int32_t B, int32_t C, int32_t G_cap,
+                       float center_radius, int32_t candidate_topk, float iou_weight, float cls_weight, float match_init,
+                       int64_t* gt_inds, int64_t* labels, float* max_overlaps, int32_t* pos_cnt, int64_t* pos_inds,
+                       int64_t* pos_gt_inds, void* workspace, size_t workspace_bytes, void* stream);
+int gd3d_simota_assign_cpu(const float* pred_scores, const float* decoded_bboxes, const float* priors, int64_t prior_rows,
+                           int64_t prior_stride, int32_t shared_priors, const int32_t* prior_batch_cnt, int64_t P,
+                           const float* gt_bboxes, const int64_t* gt_labels, const int32_t* gt_batch_cnt, int64_t G, int32_t B,
+                           int32_t C, int32_t G_cap, float center_radius, int32_t candidate_topk, float iou_weight, float cls_weight,
+                           float match_init, int64_t* gt_inds, int64_t* labels, float* max_overlaps, int32_t* pos_cnt,
+                           int64_t* pos_inds, int64_t* pos_gt_inds, void* workspace, size_t workspace_bytes);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

@@ -62,6 +62,7 @@ from .vsa_bev import bev_interpolate, sample_keypoints, voxel_centers
 from .voxelize import HardSimpleVFE, Voxelization, dynamic_voxelize, hard_voxelize, pvrcnn_voxelize, voxel_mean
 from .pillar_feat import PillarFeatureDecorator, PointVoxelStatsCalculator, pillar_decorate, point_voxel_stats
 from .view_net import PointPillarsScatter, multi_view_voxelize, pillar_scatter, to_cylindrical, to_spherical, view_sample
+from .simota import Point3DRangeGenerator, SimOTABEVAssigner, simota_assign
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
                         anchor_head_decoded_loss_fused, center_head_gd_loss, center_head_losses)
 from . import extras
@@ -87,4 +88,4 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'keypoint_reweight', 'bev_interpolate', 'voxel_centers', 'sample_keypoints', 'hard_voxelize', 'dynamic_voxelize', 'Voxelization',
            'HardSimpleVFE', 'voxel_mean', 'pvrcnn_voxelize', 'point_voxel_stats', 'PointVoxelStatsCalculator',
            'pillar_decorate', 'PillarFeatureDecorator', 'multi_view_voxelize', 'to_cylindrical', 'to_spherical', 'pillar_scatter',
-           'PointPillarsScatter', 'view_sample', 'extras']
+           'PointPillarsScatter', 'view_sample', 'simota_assign', 'SimOTABEVAssigner', 'Point3DRangeGenerator', 'extras']

@@ -308,6 +308,11 @@ SYMBOLS = {
     'gd3d_view_sample_cpu': (_int, [_vp, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp]),
     'gd3d_view_sample_backward_cpu': (_int, [_vp, _vp, _i64, _vp, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _f32, _vp,
                                              _vp]),
+    'gd3d_simota_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
+    'gd3d_simota_assign': (_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _f32, _f32,
+                                  _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'gd3d_simota_assign_cpu': (_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _f32,
+                                      _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 

@@ -40,6 +40,7 @@ SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'hard_voxel.hip': ['-ffp-contract=off'],  # a point's cell and the voxel mean replay bit for bit in hard_voxel_cpu.cpp; rocPRIM sort + scans as voxel_index.hip
     'pillar_feat.hip': ['-ffp-contract=off'],  # the voxel table, the centres, the offsets and the distance replay bit for bit in pillar_feat_cpu.cpp
     'view_net.hip': ['-ffp-contract=off'],     # the view transforms, the cells, the canvas and the sampled features replay bit for bit in view_net_cpu.cpp
+    'simota.hip': ['-ffp-contract=off'],       # memberships, the IoU, the costs on fx_logf, both selections and every match replay bit for bit in simota_cpu.cpp
 }
 # The frozen round-3 extras OUTSIDE §8 (DESIGN_EXTRAS.md; include/gd3d_extras.h): a library of their own since round 6,
 # libgd3d_extras.so, linked against libgd3d.so (the inference slices call its rnms_* entry points) and loaded only by
@@ -72,6 +73,7 @@ HOST_SOURCES = {
     'hard_voxel_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],   # same for hard_voxel.hip: every output bit-identical
     'pillar_feat_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],  # same for pillar_feat.hip: every output bit-identical
     'view_net_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],     # same for view_net.hip: every forward output bit-identical
+    'simota_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],       # same for simota.hip: every output bit-identical
 }
 HOST_COMMON = ['-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 
