@@ -51,7 +51,10 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ f
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (REDUCE == GD3D_REDUCE_MAX) {
-          if (x[u] > acc) {  // strict: the first (smallest) point index wins ties; NaN never wins (fmaxf semantics)
+          // strict: the first (smallest) point index wins ties; NaN never wins (fmaxf semantics).  arg < 0: nothing has won yet,
+          // acc is the initial -inf and a -inf value EQUALS it — the reference's trace-back is an equality test
+          // (scatter_points_cuda.cu:156-157), so a channel of -inf (and NaN) gives its gradient to its first -inf point.
+          if (x[u] > acc || (arg < 0 && x[u] == acc)) {
             acc = x[u];
             arg = pid[u];
           }
@@ -64,7 +67,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ f
       const int pid = order[k];
       const float x = feats[(long long)pid * c + ch];
       if (REDUCE == GD3D_REDUCE_MAX) {
-        if (x > acc) {
+        if (x > acc || (arg < 0 && x == acc)) {
           acc = x;
           arg = pid;
         }
@@ -112,7 +115,8 @@ __global__ __launch_bounds__(256) void reduce_v4_kernel(const float* __restrict_
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (REDUCE == GD3D_REDUCE_MAX) {
-          if (xv[j] > acc[j]) {  // strict: the first (smallest) point index wins ties; NaN never wins
+          // strict: the first (smallest) point index wins ties; NaN never wins; the first -inf takes an unclaimed channel (reduce_kernel)
+          if (xv[j] > acc[j] || (arg[j] < 0 && xv[j] == acc[j])) {
             acc[j] = xv[j];
             arg[j] = pid[u];
           }
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(256) void reduce_v4_kernel(const float* __restrict_
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (REDUCE == GD3D_REDUCE_MAX) {
-        if (xv[j] > acc[j]) {
+        if (xv[j] > acc[j] || (arg[j] < 0 && xv[j] == acc[j])) {
           acc[j] = xv[j];
           arg[j] = pid;
         }

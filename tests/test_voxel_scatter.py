@@ -264,8 +264,9 @@ def test_gpu_scatter_all_points_outside_and_single_voxel(host_glue):
 @pytest.mark.parametrize('red', ['sum', 'mean', 'max'])
 def test_gpu_narrow_rows_long_runs_and_same_bits_as_the_vector_kernels(host_glue, c, red):
     """Rows that are not whole 16-byte vectors, and narrow rows, on a skewed cloud: three voxels hold 40 % of the points (runs of
-    thousands of points; in the voxel-ordered backward several LDS tiles per workgroup), the rest are singletons and small
-    voxels.  Every kernel visits a voxel's points in ascending point id: the c channels embedded in the first columns of a
+    thousands of points), the rest are singletons and small voxels.  The backward here is the node's choice for c < 32, the
+    map-ordered gather (max: the fill and max_grad_kernel), NOT the voxel-ordered LDS kernel: its tiles are the business of
+    test_gpu_spread_lds_tiles_and_workgroup_sizes.  Every kernel visits a voxel's points in ascending point id: the c channels embedded in the first columns of a
     64-channel array (which takes the 16-byte vector kernels) give bit-identical sums / means / maxima."""
     from mmdet3d_gaussian_amd.scatter import Scatter
     rng = np.random.default_rng(c)
@@ -355,3 +356,345 @@ def test_gpu_backward_with_its_zero_fill_replays_in_a_hipgraph(host_glue):
         torch.cuda.synchronize()
         assert torch.equal(got, want)
         assert (none == 0).all() and lsum.item() == 0.0
+
+
+# ---- the dispatch paths of csrc/voxel_scatter.hip, case by case (tests/voxel_scatter_cases.py) ------------------------------------------
+
+import voxel_scatter_cases as vc  # noqa: E402
+
+_ID = lambda k: k.id if isinstance(k, vc.Case) else None
+RED = vc.REDS.index
+F_GUARD, I_GUARD, BAND = -77.0, -7, 64        # sentinels no result can equal (arg max >= -1), guard elements either side
+
+
+@pytest.mark.parametrize('case', vc.ALL_CASES, ids=_ID)
+def test_case_table_reaches_the_paths_it_names(case):
+    """every case's predicate, from its own sizes and the oracle's index: the kernel, the index form, the voxels per workgroup and the
+    tile starts it is in the table for; dropped points and a voxel of several points in every cloud, a run beyond one tile in the long ones"""
+    assert vc.reaches(case) == []
+
+
+def test_case_table_notices_a_size_that_misses_its_path(monkeypatch):
+    """the same predicates on sizes one step off: n = 4103 takes the multiply-high, n = 4106 is no longer the first division, 67 000
+    voxels of 31 channels fit one sweep, a cloud of short runs has one tile per workgroup"""
+    monkeypatch.setitem(vc.CLOUDS, 'off_4103', lambda: vc._uniform(1, 4103, 300))
+    monkeypatch.setitem(vc.CLOUDS, 'off_4106', lambda: vc._uniform(1, 4106, 300))
+    for case in vc.DIV_CASES:
+        assert vc.reaches(case._replace(cloud='off_4103')) and vc.reaches(case._replace(cloud='off_4106'))
+    assert vc.reaches(vc.SWEEP_CASE._replace(c=30)) and vc.reaches(vc.SWEEP_CASE._replace(c=32))
+    assert vc.reaches(vc.LDS_CASES[0]._replace(cloud='wide')) and vc.reaches(vc.LDS_CASES[0]._replace(c=4))
+    assert vc.reaches(vc.WIDE_CASES[0]._replace(c=128)) and vc.reaches(vc.WIDE_CASES[3]._replace(c=256))
+    assert vc.reaches(vc.MISALIGNED_CASE._replace(c=66)) and vc.reaches(vc.GUARD_CASES[0]._replace(cloud='lds_c'))
+
+
+def test_nonfinite_plants_as_the_oracle_sees_them():
+    """what the non-finite cloud holds, by the oracle alone: a voxel-channel of NaN reduces to -inf and routes no gradient; one of -inf
+    (also behind a leading NaN) gives its gradient to its smallest -inf point (the reference's trace-back is an equality test); +inf
+    ties go to the first +inf; a NaN among finite values changes nothing"""
+    for case in vc.NONFINITE_CASES:
+        c = case.c
+        _, _, mo, co = vc.cloud(case.cloud)
+        feats, want, where = vc.inputs(case.cloud, c), vc.expected(case.cloud, c, 'max'), vc.plants(c)
+        pts = lambda v: np.flatnonzero(mo == v)
+        v, ch = where['all_nan']
+        assert np.isnan(feats[pts(v), ch]).all() and want['out'][v, ch] == -np.inf and (want['grad'][pts(v), ch] == 0).all()
+        v, ch = where['all_ninf']
+        assert (feats[pts(v), ch] == -np.inf).all() and want['out'][v, ch] == -np.inf
+        assert want['grad'][pts(v)[0], ch] == want['gv'][v, ch] != 0 and (want['grad'][pts(v)[1:], ch] == 0).all()
+        v, ch = where['nan_then_ninf']
+        assert np.isnan(feats[pts(v)[0], ch]) and want['grad'][pts(v)[0], ch] == 0 and want['grad'][pts(v)[1], ch] == want['gv'][v, ch]
+        v, ch = where['inf_ties']
+        assert want['out'][v, ch] == np.inf and want['grad'][pts(v)[1], ch] == want['gv'][v, ch] and (want['grad'][pts(v)[2:], ch] == 0).all()
+        assert np.isnan(feats[:, 4:]).sum() > 100 and not np.isnan(want['out']).any() and np.isfinite(want['grad']).all()
+
+
+_DEVICE = {}
+
+
+def _gpu(a):
+    """a frozen array of the case table as a device tensor of its own"""
+    return torch.tensor(a, device='cuda')
+
+
+def _on_gpu(name):
+    """the cloud's Scatter (its index checked against the oracle's once) and the grouping the C entry points take"""
+    if name not in _DEVICE:
+        from mmdet3d_gaussian_amd.scatter import Scatter
+        coors, uo, mo, co = vc.cloud(name)
+        sc = Scatter(_gpu(coors))
+        np.testing.assert_array_equal(sc.voxel_coors.cpu().numpy(), uo)
+        np.testing.assert_array_equal(sc.pts_voxel_maps.cpu().numpy(), mo)
+        np.testing.assert_array_equal(sc.voxel_pts_counts.cpu().numpy(), co)
+        _DEVICE[name] = (sc,) + tuple(sc._grouping)
+    return _DEVICE[name]
+
+
+def _shifted(t):
+    """the same values in a contiguous view that starts 4 bytes past a 16-byte boundary"""
+    buf = torch.empty(t.numel() + 8, dtype=t.dtype, device=t.device)
+    view = buf[1:1 + t.numel()].view(t.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4
+    return view
+
+
+def _bits(a):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _check_forward(got, want, red, what):
+    """max: the oracle's bits.  sum / mean: the sequential-summation bound of the case (voxel_scatter_cases.expected), per element;
+    the largest error / bound ratio is printed, the bound itself is derived and not tuned"""
+    got = got.detach().cpu().numpy()
+    if red == 'max':
+        np.testing.assert_array_equal(_bits(got), _bits(want['out']), err_msg=what)
+        return
+    err = np.abs(got.astype(np.float64) - want['out'])
+    pos = want['bound'] > 0
+    print(f'SUMBOUND {what} {red}: largest error / bound = {(err[pos] / want["bound"][pos]).max():.4f}')
+    assert (err <= want['bound']).all(), (what, float((err - want['bound']).max()))
+
+
+def _check_backward(got, want, red, what):
+    """sum and max: copies of grad_vox rows or zeros, the oracle's bits.  mean: one fp32 division against fp64"""
+    if red == 'mean':
+        np.testing.assert_allclose(got.detach().cpu().numpy(), want['grad'], rtol=2e-6, atol=1e-7, err_msg=what)
+    else:
+        np.testing.assert_array_equal(_bits(got), _bits(want['grad']), err_msg=what)
+
+
+def _through_the_node(case, red, shift=False):
+    sc = _on_gpu(case.cloud)[0]
+    want = vc.expected(case.cloud, case.c, red)
+    f = _gpu(vc.inputs(case.cloud, case.c))
+    f = (_shifted(f) if shift else f).requires_grad_(True)
+    out, _ = sc.reduce(f, red)
+    _check_forward(out, want, red, case.id)
+    out.backward(_gpu(want['gv']))
+    _check_backward(f.grad, want, red, case.id)
+    return sc, f, out.detach(), want
+
+
+def _forward(case, red, out=None, arg=None, feats=None):
+    """vox_scatter_reduce on the case's cloud -> (out, arg max | None)"""
+    import mmdet3d_gaussian_amd as amd
+    lib = amd.load_library()
+    sc, order, seg = _on_gpu(case.cloud)
+    n, c, v = sc.pts_voxel_maps.numel(), case.c, sc.voxel_coors.shape[0]
+    f = _gpu(vc.inputs(case.cloud, c)) if feats is None else feats
+    out = torch.full((v, c), float('nan'), device='cuda') if out is None else out
+    if red == 'max' and arg is None:
+        arg = torch.full((v, c), I_GUARD, dtype=torch.int32, device='cuda')
+    assert lib.vox_scatter_reduce(f.data_ptr(), order.data_ptr(), seg.data_ptr(), n, c, v, RED(red), out.data_ptr(),
+                                  arg.data_ptr() if red == 'max' else None, None) == 0
+    return out, (arg if red == 'max' else None)
+
+
+def _backward(case, red, gv, arg, grouped, gf=None):
+    """vox_scatter_backward | vox_scatter_backward_grouped into a NaN-poisoned (or the given) buffer -> (return code, grad_feats)"""
+    import mmdet3d_gaussian_amd as amd
+    lib = amd.load_library()
+    sc, order, seg = _on_gpu(case.cloud)
+    n, c, v = sc.pts_voxel_maps.numel(), case.c, sc.voxel_coors.shape[0]
+    gf = torch.full((n, c), float('nan'), device='cuda') if gf is None else gf
+    am = arg.data_ptr() if red == 'max' else None
+    if grouped:
+        rc = lib.vox_scatter_backward_grouped(gv.data_ptr(), order.data_ptr(), seg.data_ptr(), am, n, c, v, RED(red), gf.data_ptr(), None)
+    else:
+        rc = lib.vox_scatter_backward(gv.data_ptr(), sc.pts_voxel_maps.data_ptr(), sc.voxel_pts_counts.data_ptr(), am, n, c, v, RED(red),
+                                      gf.data_ptr(), None)
+    torch.cuda.synchronize()
+    return rc, gf
+
+
+def _banded(shape, dtype):
+    """a sentinel-filled buffer and the view of `shape` inside it, BAND elements from either end (16-byte aligned, as the buffer is)"""
+    numel = int(np.prod(shape))
+    buf = torch.full((numel + 2 * BAND,), F_GUARD if dtype == torch.float32 else I_GUARD, dtype=dtype, device='cuda')
+    inner = buf[BAND:BAND + numel].view(shape)
+    assert inner.data_ptr() % 16 == 0
+    return buf, inner
+
+
+def _bands_intact_and_inside_written(buf, what):
+    guard = F_GUARD if buf.dtype == torch.float32 else I_GUARD
+    assert (buf[:BAND] == guard).all() and (buf[-BAND:] == guard).all(), f'{what}: a guard band was written'
+    assert (buf[BAND:-BAND] != guard).all(), f'{what}: an element inside was not written'
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('red', vc.REDS)
+@pytest.mark.parametrize('case', vc.DIV_CASES, ids=_ID)
+def test_gpu_gather_index_by_division_and_by_the_last_exact_multiply_high(host_glue, case, red):
+    """gather_grad_kernel turns a flat index into (point, lane) with a shift, ONE multiply-high, or — from n * cv >= floor(2^32 / cv) on —
+    a 64-bit division.  cv = 1023 lanes a row, scalar (c = 1023) and vector (c = 4092): n = 4105 is the first size that divides,
+    n = 4104 the last that multiplies, so its last rows are the hardest indices of that form.  Forward (the scalar multi-pass kernel)
+    and backward through the node against the fp64 oracle."""
+    _through_the_node(case, red)
+
+
+@pytest.mark.gpu
+def test_gpu_max_backward_beyond_one_sweep_of_its_capped_grid(host_glue):
+    """max_grad_kernel's grid stops at 8192 workgroups: with 68 000 voxels of 31 channels the grid-stride loop goes round again, and
+    the voxels of the second sweep get their gradient only there.  72 000 points with exact ties for the max and dropped points;
+    forward and backward are exact."""
+    _through_the_node(vc.SWEEP_CASE, 'max')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('red', vc.REDS)
+@pytest.mark.parametrize('case', vc.LDS_CASES, ids=_ID)
+def test_gpu_spread_lds_tiles_and_workgroup_sizes(case, red):
+    """spread_lds_kernel called directly (the node never picks it): workgroups shrunk by lds_plan's run-length term, by 512 / c, to ONE
+    voxel and at the cap of 128; runs of several 1024-point tiles whose boundaries fall inside a voxel and exactly between two.  The same
+    bits as the map-ordered backward on NaN-poisoned buffers, zero rows for the dropped points, and the fp64 oracle's gradient."""
+    want = vc.expected(case.cloud, case.c, red)
+    _, arg = _forward(case, red)
+    gv = _gpu(want['gv'])
+    rc_a, a = _backward(case, red, gv, arg, grouped=False)
+    rc_b, b = _backward(case, red, gv if case.aligned else _shifted(gv), arg, grouped=True)
+    assert rc_a == 0 and rc_b == 0
+    assert not torch.isnan(b).any() and torch.equal(a, b)
+    assert (b[_on_gpu(case.cloud)[0].pts_voxel_maps < 0] == 0).all()
+    _check_backward(b, want, red, case.id)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('red', vc.REDS)
+@pytest.mark.parametrize('case', vc.WIDE_CASES, ids=_ID)
+def test_gpu_rows_wider_than_128_channels_through_the_node(host_glue, case, red):
+    """128 < c <= 256 with c % 4 == 0: one voxel per wave in reduce_v4_kernel and spread_grad_v4_kernel, the lanes beyond c / 4 idle;
+    c = 260: the scalar multi-pass forward and the vector gather at 65 lanes a row.  Against the oracle, and — every kernel visits a
+    voxel's points in ascending id — the same bits as the same channels in a (c + 1)-wide array on the scalar path."""
+    sc, f, out, _ = _through_the_node(case, red)
+    if case.c <= vc.VEC_C_MAX:
+        wide = torch.zeros((f.shape[0], case.c + 1), device='cuda')
+        wide[:, :case.c] = f.detach()
+        ref, _ = sc.reduce(wide, red)
+        assert torch.equal(out, ref[:, :case.c].contiguous())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('red', vc.REDS)
+@pytest.mark.parametrize('case', vc.WIDE_CASES, ids=_ID)
+def test_gpu_rows_wider_than_128_channels_both_backward_entries(case, red):
+    """the two backward entry points on the wide rows: the vector gather at 33 .. 65 lanes a row against the oracle; the voxel-ordered
+    form bit-equal to it where it accepts the shape (c <= 256), GD3D_E_BADARG and nothing written at c = 260"""
+    want = vc.expected(case.cloud, case.c, red)
+    out, arg = _forward(case, red)
+    _check_forward(out, want, red, case.id)
+    gv = _gpu(want['gv'])
+    rc_a, a = _backward(case, red, gv, arg, grouped=False)
+    rc_b, b = _backward(case, red, gv, arg, grouped=True)
+    assert rc_a == 0
+    _check_backward(a, want, red, case.id)
+    if case.c <= vc.VEC_C_MAX:
+        assert rc_b == 0 and torch.equal(a, b)
+    else:
+        assert rc_b == vc.BADARG and torch.isnan(b).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('red', vc.REDS)
+def test_gpu_features_four_bytes_off_alignment_through_the_node(host_glue, red):
+    """a contiguous (n, 64) view that starts 4 bytes into its buffer: the forward must leave the 16-byte kernels for the scalar one
+    (same visiting order, same bits as the aligned run), and the gradient comes back the same"""
+    case = vc.MISALIGNED_CASE
+    _, f0, out0, _ = _through_the_node(case, red)
+    _, f1, out1, _ = _through_the_node(case, red, shift=True)
+    assert f1.data_ptr() % 16 == 4 and f0.data_ptr() % 16 == 0
+    assert torch.equal(out0, out1) and torch.equal(f0.grad, f1.grad)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('red', vc.REDS)
+def test_gpu_gradient_four_bytes_off_alignment_at_the_entry_points(red):
+    """a misaligned grad_vox, which the node's own copy never produces: the map-ordered backward falls back to the dword gather, the
+    voxel-ordered one to spread_lds_kernel at c = 64 — both with the aligned run's bits — and returns GD3D_E_BADARG at c = 132, where
+    it has no dword form, without writing anything; a misaligned grad_feats takes the same fallbacks"""
+    case = vc.MISALIGNED_CASE
+    want = vc.expected(case.cloud, case.c, red)
+    _, arg = _forward(case, red)
+    gv = _gpu(want['gv'])
+    rc, aligned = _backward(case, red, gv, arg, grouped=False)
+    assert rc == 0
+    _check_backward(aligned, want, red, case.id)
+    for grouped in (False, True):
+        rc, got = _backward(case, red, _shifted(gv), arg, grouped)
+        assert rc == 0 and torch.equal(got, aligned), grouped
+        rc, got = _backward(case, red, gv, arg, grouped, gf=_shifted(torch.full_like(aligned, float('nan'))))
+        assert rc == 0 and torch.equal(got, aligned), grouped
+    bad = vc.MISALIGNED_BADARG
+    want = vc.expected(bad.cloud, bad.c, red)
+    _, arg = _forward(bad, red)
+    gv = _gpu(want['gv'])
+    rc, got = _backward(bad, red, _shifted(gv), arg, grouped=True)
+    assert rc == vc.BADARG and torch.isnan(got).all()
+    rc, got = _backward(bad, red, _shifted(gv), arg, grouped=False)
+    assert rc == 0
+    _check_backward(got, want, red, bad.id)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('red', vc.REDS)
+@pytest.mark.parametrize('case', vc.GUARD_CASES, ids=_ID)
+def test_gpu_nothing_is_written_beyond_out_argmax_and_grad_feats(case, red):
+    """the three C entry points on sentinel-filled buffers with a guard band either side of out, argmax and grad_feats, at v = 1237 and
+    n = 4999 (no multiple of any per-wave or per-workgroup count): float4 / int4 and nontemporal stores at computed row offsets, the
+    fill + max_grad_kernel route (max, c = 10) and spread_lds_kernel (grouped, c = 10) among them.  Every element inside is written,
+    no guard is touched, and the values are the oracle's."""
+    want = vc.expected(case.cloud, case.c, red)
+    v, n = want['out'].shape[0], want['grad'].shape[0]
+    obuf, out = _banded((v, case.c), torch.float32)
+    abuf, arg = _banded((v, case.c), torch.int32)
+    _forward(case, red, out=out, arg=arg)
+    torch.cuda.synchronize()
+    _bands_intact_and_inside_written(obuf, 'out')
+    if red == 'max':
+        _bands_intact_and_inside_written(abuf, 'argmax')
+    else:
+        assert (abuf == I_GUARD).all()
+    _check_forward(out, want, red, case.id)
+    gv = _gpu(want['gv'])
+    for grouped in (False, True):
+        gbuf, gf = _banded((n, case.c), torch.float32)
+        rc, _ = _backward(case, red, gv, arg, grouped, gf=gf)
+        assert rc == 0
+        _bands_intact_and_inside_written(gbuf, f'grad_feats, grouped={grouped}')
+        _check_backward(gf, want, red, case.id)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', vc.NONFINITE_CASES, ids=_ID)
+def test_gpu_max_of_nan_and_infinite_features(case):
+    """NaN among finite values, a voxel-channel of NaN (reduces to -inf, arg max -1, no gradient: the rows a missing guard would store
+    at point -1, into the band in front of grad_feats), a voxel-channel of -inf (the reference's equality trace-back gives the gradient
+    to its smallest point id, and so does the tie rule of the reduce kernels), +inf ties: the oracle's bits forward, and backward on
+    every route — fill + max_grad_kernel, the voxel-ordered vector kernel (c = 16) or LDS kernel (c = 10), and the LDS kernel by way
+    of a misaligned gradient — inside guard bands"""
+    want = vc.expected(case.cloud, case.c, 'max')
+    v, n = want['out'].shape[0], want['grad'].shape[0]
+    obuf, out = _banded((v, case.c), torch.float32)
+    abuf, arg = _banded((v, case.c), torch.int32)
+    _forward(case, 'max', out=out, arg=arg)
+    torch.cuda.synchronize()
+    _bands_intact_and_inside_written(obuf, 'out')
+    _bands_intact_and_inside_written(abuf, 'argmax')
+    _check_forward(out, want, 'max', case.id)
+    where = vc.plants(case.c)
+    at = lambda k: int(arg[int(where[k][0]), where[k][1]])
+    assert at('all_nan') == -1 and at('all_ninf') >= 0 and at('nan_then_ninf') >= 0
+    gv = _gpu(want['gv'])
+    for grouped, g in ((False, gv), (True, gv), (True, _shifted(gv))):
+        gbuf, gf = _banded((n, case.c), torch.float32)
+        rc, _ = _backward(case, 'max', g, arg, grouped, gf=gf)
+        assert rc == 0
+        _bands_intact_and_inside_written(gbuf, f'grad_feats, grouped={grouped}')
+        _check_backward(gf, want, 'max', case.id)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', vc.NONFINITE_CASES, ids=_ID)
+def test_gpu_max_of_nan_and_infinite_features_through_the_node(host_glue, case):
+    _through_the_node(case, 'max')
