@@ -304,6 +304,20 @@ int gd3d_loss_fused_one_launch(const gd3d_params* params, const gd3d_prologue* p
                                float scale, float* loss_sum, int32_t* any_positive, float* grad_pred,
                                float* grad_target, void* workspace, int32_t* ticket, void* stream);
 
+/* Several losses on ONE target in one fused launch and one second-stage launch (count = 2 or 3): the target tile is read
+ * once per 256 rows instead of once per loss.  Loss k is params[k] on (preds[k], target) with scale scales[k]; it writes
+ * *loss_sums[k] and grad_preds[k] (nullable), bit-identical to gd3d_loss_fused(&params[k], preds[k], target, NULL, n,
+ * scales[k], NULL, loss_sums[k], grad_preds[k], NULL, ...).  No weights, no prologue, no target gradient.
+ *   Every params[k] must satisfy gd3d_loss_fused_multi_eligible (the kernel is compiled for those instances only: gwd3d, kld3d
+ *   and bd3d with fun log1p and their flag set; any order, repeats allowed), else GD3D_E_BADARG; so is count outside [2, 3].
+ *   workspace: gd3d_loss_fused_multi_workspace_bytes(count, n) bytes, 16-byte aligned (<= gd3d_loss_workspace_bytes(n)).
+ *   n == 0: every *loss_sums[k] = 0.  The launch after it on this stream gets no target reuse from the Infinity Cache. */
+size_t gd3d_loss_fused_multi_workspace_bytes(int32_t count, int64_t n);
+int gd3d_loss_fused_multi_eligible(const gd3d_params* params);
+int gd3d_loss_fused_multi(int32_t count, const gd3d_params* params, const float* const* preds, const float* target,
+                          int64_t n, const float* scales, float* const* loss_sums, float* const* grad_preds,
+                          void* workspace, void* stream);
+
 /* Autograd backward of a reduced call; g is the upstream gradient (device scalar).
  *   any_positive == NULL or *any_positive != 0 : grad_pred *= g, grad_target *= g (the grid leaves after two scalar loads
  *       when g == 1: one empty launch, no HBM traffic, no host sync — gd3d_scale_rows for both arrays at once);

@@ -138,6 +138,10 @@ SYMBOLS = {
     'gd3d_one_launch_max_n': (_i64, []),
     'gd3d_loss_fused_one_launch': (_int, [ctypes.POINTER(Params), ctypes.POINTER(Prologue), _vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp,
                                           _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_loss_fused_multi_workspace_bytes': (_sz, [_i32, _i64]),
+    'gd3d_loss_fused_multi_eligible': (_int, [ctypes.POINTER(Params)]),
+    'gd3d_loss_fused_multi': (_int, [_i32, ctypes.POINTER(Params), ctypes.POINTER(_vp), _vp, _i64, ctypes.POINTER(_f32),
+                                     ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp]),
     'gd3d_loss_fused_cpu': (_int, [ctypes.POINTER(Params), _vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32]),
     'gd3d_loss_reduce_cpu': (_int, [_vp, _i64, _vp]),
     'gd3d_scale_rows_cpu': (_int, [_vp, _vp, _int, _i64, ctypes.c_int32]),

@@ -61,4 +61,44 @@ decltype(auto) with_instance(int loss_type, int fun, bool flag, F&& f) {
   }
 }
 
+// The instances the multi-loss fused kernel (gd3d_loss.hip: fused_multi_kernel) is compiled for: the first MULTI_LOSSES loss
+// types, each with MULTI_FUN and MULTI_FLAG — what a training step runs side by side on one target.  The kernel exists for
+// every non-decreasing tuple of 2 or 3 of them (16 kernels); the launcher sorts a call's losses into that order.
+constexpr int MULTI_LOSSES = 3;   // gwd3d, kld3d, bd3d
+constexpr int MULTI_FUN = GD3D_FUN_LOG1P;
+constexpr bool MULTI_FLAG = true;
+constexpr int MULTI_MAX = 3;      // losses per launch
+
+inline bool multi_marked(int loss_type, int fun, bool flag) {
+  return loss_type >= 0 && loss_type < MULTI_LOSSES && fun == MULTI_FUN && flag == MULTI_FLAG;
+}
+
+// Calls f(std::integral_constant-like tags) for the sorted tuple (l0 <= l1 [<= l2]); count 2 passes l2 = -1.
+template <int L0, int L1, int L2>
+struct MultiTuple {
+  static constexpr int l0 = L0, l1 = L1, l2 = L2;
+  static constexpr int count = L2 < 0 ? 2 : 3;
+};
+template <int L0, int L1, class F>
+decltype(auto) with_multi_third(int l2, F&& f) {
+  if (l2 < 0) return f(MultiTuple<L0, L1, -1>{});
+  if constexpr (L1 <= 0) { if (l2 == 0) return f(MultiTuple<L0, L1, 0>{}); }
+  if constexpr (L1 <= 1) { if (l2 == 1) return f(MultiTuple<L0, L1, 1>{}); }
+  return f(MultiTuple<L0, L1, 2>{});
+}
+template <int L0, class F>
+decltype(auto) with_multi_second(int l1, int l2, F&& f) {
+  if constexpr (L0 <= 0) { if (l1 == 0) return with_multi_third<L0, 0>(l2, f); }
+  if constexpr (L0 <= 1) { if (l1 == 1) return with_multi_third<L0, 1>(l2, f); }
+  return with_multi_third<L0, 2>(l2, f);
+}
+// l0 <= l1 (<= l2 unless l2 < 0), all marked
+template <class F>
+decltype(auto) with_multi_tuple(int l0, int l1, int l2, F&& f) {
+  static_assert(MULTI_LOSSES == 3, "the three-way chains above list the marked loss types");
+  if (l0 == 0) return with_multi_second<0>(l1, l2, f);
+  if (l0 == 1) return with_multi_second<1>(l1, l2, f);
+  return with_multi_second<2>(l1, l2, f);
+}
+
 }  // namespace gd3d

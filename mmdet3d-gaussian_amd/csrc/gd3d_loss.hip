@@ -380,6 +380,147 @@ __global__ __launch_bounds__(TILE) void fused_kernel(const LossArgs a_in) {
   }
 }
 
+// ---- several losses on one target in one launch (gd3d_loss_fused_multi) -----------------------------------------------------
+// A training step evaluates K losses against ONE target.  K single launches read that target K times (from HBM, or at
+// about a third of that cost from the Infinity Cache when the launches follow each other: DMA_AUX_TARGET above); this kernel
+// brings each target tile into LDS once, next to K prediction tiles, and evaluates the K losses on it: (1 + 2 K) x 28 bytes per
+// row instead of 3 K x 28.  Unweighted, prologue-free, no target gradient; per loss the SAME pair_loss instance on the same
+// operands in the same order as fused_kernel, the same per-wave and per-tile sums: bit-identical losses and gradients.
+struct MultiArgs {
+  const float* target;
+  const float* pred[MULTI_MAX];
+  float* gp[MULTI_MAX];         // nullable
+  float* partials[MULTI_MAX];   // one partial array per loss (workspace rows of ws_nbp(n) floats)
+  long long n;
+  float scale[MULTI_MAX], alpha[MULTI_MAX], ia2[MULTI_MAX], tau[MULTI_MAX];
+  float c[MULTI_MAX][3];
+  int vec_ok;                   // target and every pred / gp pointer 16-byte aligned
+};
+
+// (K + 1) x NPIECE pieces of 1 KiB: the K pred tiles, then the target tile, adjacent in LDS (piece j lands at smem + j * 256).
+// Wave w issues pieces w, w + 4, ...; a round of four pieces lies in one tensor or straddles ONE tensor boundary (4 < NPIECE),
+// which is known at compile time: one wave-uniform branch in a straddling round, none otherwise (see issue_tile_dma).
+template <int K>
+GD_DEV void issue_multi_dma(const MultiArgs& a, long long off, float* smem, int wave, int lane) {
+  constexpr int NP = (K + 1) * NPIECE;
+#pragma unroll
+  for (int k = 0; k * NWAVE < NP; ++k) {
+    const int j = wave + k * NWAVE;   // wave-uniform
+    const int t_lo = (k * NWAVE) / NPIECE;                                            // compile time after unrolling
+    const int t_hi = (k * NWAVE + NWAVE - 1) / NPIECE < K ? (k * NWAVE + NWAVE - 1) / NPIECE : K;
+    lds_ptr_t* const dst = (lds_ptr_t*)(smem + j * 256);
+    // source of piece j when it belongs to tensor t: base_t + (j - t * NPIECE) * 256 floats
+    const float* const lo_src = (t_lo < K ? a.pred[t_lo < K ? t_lo : 0] : a.target) + off + (j - t_lo * NPIECE) * 256 + lane * 4;
+    const float* const hi_src = (t_hi < K ? a.pred[t_hi < K ? t_hi : 0] : a.target) + off + (j - t_hi * NPIECE) * 256 + lane * 4;
+    const bool last_round = (k + 1) * NWAVE > NP;
+    if (last_round && j >= NP) continue;   // uniform; only the last round can run past the last piece
+    if (t_lo == t_hi || j < t_hi * NPIECE) {
+      if (t_lo < K) __builtin_amdgcn_global_load_lds((gbl_cptr_t*)lo_src, dst, 16, 0, DMA_AUX);
+      else __builtin_amdgcn_global_load_lds((gbl_cptr_t*)lo_src, dst, 16, 0, DMA_AUX_TARGET);
+    } else {
+      if (t_hi < K) __builtin_amdgcn_global_load_lds((gbl_cptr_t*)hi_src, dst, 16, 0, DMA_AUX);
+      else __builtin_amdgcn_global_load_lds((gbl_cptr_t*)hi_src, dst, 16, 0, DMA_AUX_TARGET);
+    }
+  }
+}
+
+// loss k of the tuple on this thread's row: gradient into the row's own place in pred k's LDS tile, wave sum into swave
+template <int LOSS, int KI>
+GD_DEV void multi_eval(const MultiArgs& a, float* sp, const float (&tv_in)[7], float* swave, int tid, int lane, int wave,
+                       bool valid) {
+  float pv[7], tv[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    pv[k] = sp[tid * 7 + k];
+    tv[k] = tv_in[k];
+    // each loss sees the target row as values of its own: nothing of one loss's arithmetic is shared with another's, so every
+    // loss is contracted and rounded exactly as in its single-loss kernel
+    asm volatile("" : "+v"(tv[k]));
+  }
+  const float c[3] = {a.c[KI][0], a.c[KI][1], a.c[KI][2]};
+  const float f = a.scale[KI];
+  float g1[7], g2[7];
+  const float L = pair_loss<LOSS, MULTI_FUN, MULTI_FLAG, false>(pv, tv, c, a.alpha[KI], a.ia2[KI], a.tau[KI], f, g1, g2);
+  const float fl = valid ? f * L : 0.0f;
+#pragma unroll
+  for (int k = 0; k < 7; ++k) sp[tid * 7 + k] = g1[k];   // own row: no hazard with other threads
+  const float ws = wave_sum(fl);   // uniform (readlane 63)
+  if (lane == 0) swave[KI * NWAVE + wave] = ws;
+}
+
+template <int L0, int L1, int L2>
+__global__ __launch_bounds__(TILE) void fused_multi_kernel(const MultiArgs a) {
+  constexpr int K = L2 < 0 ? 2 : 3;
+  // dynamic LDS: K pred tiles | target tile | 32 floats of per-wave sums (K x NWAVE used)
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* const st = smem + K * TILE_F;
+  float* const swave = smem + (K + 1) * TILE_F;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const unsigned tile = blockIdx.x;
+  const long long base = (long long)tile * TILE;
+  const long long rows_left = a.n - base;
+  const bool fast = rows_left >= TILE && a.vec_ok;   // workgroup-uniform
+  const bool valid = tid < rows_left;
+  const long long fl7 = (rows_left < TILE ? rows_left : TILE) * 7;
+
+  if (fast) {
+    issue_multi_dma<K>(a, base * 7, smem, wave, lane);
+  } else {
+    for (int i = tid; i < TILE_F; i += TILE) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) smem[k * TILE_F + i] = i < fl7 ? a.pred[k][base * 7 + i] : 1.0f;
+      st[i] = i < fl7 ? a.target[base * 7 + i] : 1.0f;
+    }
+  }
+  __syncthreads();  // s_waitcnt vmcnt(0) + barrier: every wave's pieces have landed
+
+  float tv[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) tv[k] = st[tid * 7 + k];
+  multi_eval<L0, 0>(a, smem, tv, swave, tid, lane, wave, valid);
+  multi_eval<L1, 1>(a, smem + TILE_F, tv, swave, tid, lane, wave, valid);
+  if constexpr (K == 3) multi_eval<L2, 2>(a, smem + 2 * TILE_F, tv, swave, tid, lane, wave, valid);
+  __syncthreads();
+
+  static_assert(NWAVE == 4, "the tile sum below adds four wave sums");
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (tid == k) {   // thread k finishes loss k's tile sum, in fused_kernel's order
+      float bsum = 0.0f;
+      const float* const s4 = swave + k * NWAVE;
+      bsum += (s4[0] + s4[1]) + (s4[2] + s4[3]);
+      a.partials[k][tile] = bsum;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    float* const gp = a.gp[k];
+    if (gp == nullptr) continue;   // uniform
+    const float* const sp = smem + k * TILE_F;
+    if (fast) {
+      store_v4(gp + base * 7, sp, tid);
+      if (tid < TILE_V4 - TILE) store_v4(gp + base * 7, sp, tid + TILE);  // 7/4 vectors per thread
+    } else {
+      for (int i = tid; i < fl7; i += TILE) gp[base * 7 + i] = sp[i];
+    }
+  }
+}
+
+// Dynamic-LDS request of the multi-loss launch = its occupancy: floor(160 KiB / bytes) workgroups per CU.  Its own need is
+// (K + 1) tiles + 128 bytes: 28 800 bytes at K = 3 (5 per CU at most), 21 632 at K = 2 (7 per CU).  Swept at K = 3 on
+// gwd3d + kld3d + bd3d, 10 M rows, us per launch pair (fused + second stage) in back-to-back loops, three single launches with
+// their second stages beside it in the same process (profiles/r20_multi_loss_probe.txt):
+//   5 per CU 312.2-316.7 (singles 368.5-369.7)   4 per CU 321.2-324.2 (370.8-371.9)   3 per CU 368.2-369.5 (371.6-372.1)
+// and at K = 2 on gwd3d + kld3d / kld3d + bd3d (two single launches with their second stages: 243.8-245.5 on every line):
+//   7 per CU 209.6-211.8 / 206.5-209.9   6 per CU 211.5-213.8 / 214.1-216.2   5 per CU 222.1-223.1 / 234.2-236.8
+//   4 per CU 221.0-221.7 / 236.7-237.2
+// So neither launch is capped: the request is what the tiles need, and the single launches' caps (MIN_LDS) are not inherited.
+constexpr int MULTI_LDS_K3 = 28800;   // 5 workgroups per CU
+constexpr int MULTI_LDS_K2 = 21632;   // 7
+
 // Clears (or fills) small or large device buffers from a KERNEL.  Not hipMemsetAsync: inside a captured hipGraph a memset node was
 // found not to be reliably ordered against the kernels around it on this ROCm (profiles/r04_nms_queue_ab.txt) —
 // rule of this library: no memset nodes in paths a caller may capture.
@@ -409,9 +550,7 @@ int fill_words(void* p, size_t bytes, unsigned value, hipStream_t s) {   // byte
 // (39 K floats at 10 M pairs): every thread issues ALL its 16-byte loads of a 48 K-partial round before the first add
 // (one memory round trip at 10 M pairs), then one barrier: thread t of wave 0 adds 16 consecutive per-thread sums from
 // LDS and the wave finishes with 6 shuffle steps.  Deterministic (fixed order), independent of the launch geometry.
-__global__ __launch_bounds__(1024) void reduce_partials_kernel(const float* __restrict__ partials, long long nb,
-                                                               float* __restrict__ out) {
-  __shared__ double sd[1024];
+GD_DEV void reduce_partials_body(const float* __restrict__ partials, long long nb, float* __restrict__ out, double* sd) {
   constexpr int RU = 12;
   const int tid = threadIdx.x;
   const long long nv = nb >> 2;  // whole float4s (the workspace is 16-byte aligned)
@@ -439,6 +578,23 @@ __global__ __launch_bounds__(1024) void reduce_partials_kernel(const float* __re
     for (int off = 32; off >= 1; off >>= 1) s2 += __shfl_down(s2, off, 64);
     if (tid == 0) *out = (float)s2;
   }
+}
+__global__ __launch_bounds__(1024) void reduce_partials_kernel(const float* __restrict__ partials, long long nb,
+                                                               float* __restrict__ out) {
+  __shared__ double sd[1024];
+  reduce_partials_body(partials, nb, out, sd);
+}
+// the same sum for the K losses of gd3d_loss_fused_multi in ONE launch: workgroup k adds row k of the workspace
+struct ReduceMultiArgs {
+  float* out[MULTI_MAX];
+};
+__global__ __launch_bounds__(1024) void reduce_partials_multi_kernel(const float* __restrict__ partials, long long nb,
+                                                                     long long nbp, const ReduceMultiArgs o) {
+  __shared__ double sd[1024];
+  float* out = o.out[0];
+  if (blockIdx.x == 1) out = o.out[1];
+  if (blockIdx.x == 2) out = o.out[2];
+  reduce_partials_body(partials + (long long)blockIdx.x * nbp, nb, out, sd);
 }
 int reduce_partials(const float* partials, long long nb, float* out, hipStream_t s) {
   hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(1024), 0, s, partials, nb, out);
@@ -872,6 +1028,86 @@ int gd3d_loss_reduce(const void* workspace, int64_t n, float* loss_sum, void* st
   if (workspace == nullptr) return GD3D_E_BADARG;
   const long long nparts = (n + TILE - 1) / TILE;
   return reduce_partials((const float*)workspace, nparts, loss_sum, s);
+}
+
+size_t gd3d_loss_fused_multi_workspace_bytes(int32_t count, int64_t n) {
+  if (n <= 0 || count <= 0) return 64;
+  return (size_t)(4 * (int64_t)count * ws_nbp(n) + 16);
+}
+
+int gd3d_loss_fused_multi_eligible(const gd3d_params* p) {
+  return p != nullptr && multi_marked(p->loss_type, p->fun, p->flag != 0) ? 1 : 0;
+}
+
+int gd3d_loss_fused_multi(int32_t count, const gd3d_params* params, const float* const* preds, const float* target,
+                          int64_t n, const float* scales, float* const* loss_sums, float* const* grad_preds,
+                          void* workspace, void* stream) {
+  if (count < 2 || count > MULTI_MAX || params == nullptr || preds == nullptr || scales == nullptr || loss_sums == nullptr ||
+      n < 0)
+    return GD3D_E_BADARG;
+  for (int k = 0; k < count; ++k) {
+    if (!gd3d_loss_fused_multi_eligible(&params[k]) || loss_sums[k] == nullptr) return GD3D_E_BADARG;
+    if (n > 0 && preds[k] == nullptr) return GD3D_E_BADARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {
+    for (int k = 0; k < count; ++k) {
+      const int e0 = fill_words(loss_sums[k], sizeof(float), 0u, s);
+      if (e0 != 0) return e0;
+    }
+    return 0;
+  }
+  if (target == nullptr || workspace == nullptr || ((uintptr_t)workspace & 15) != 0) return GD3D_E_BADARG;
+  const int64_t nb = (n + TILE - 1) / TILE;
+  if (nb > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  // the kernels exist for non-decreasing loss types: slot j of the launch is the caller's loss order[j] (stable)
+  int order[MULTI_MAX] = {0, 1, 2};
+  for (int i = 1; i < count; ++i)
+    for (int j = i; j > 0 && params[order[j]].loss_type < params[order[j - 1]].loss_type; --j) {
+      const int t = order[j];
+      order[j] = order[j - 1];
+      order[j - 1] = t;
+    }
+  const long long nbp = ws_nbp(n);
+  MultiArgs a = {};
+  ReduceMultiArgs r = {};
+  uintptr_t bits = (uintptr_t)target;
+  int lt[MULTI_MAX] = {-1, -1, -1};
+  for (int j = 0; j < count; ++j) {
+    const int k = order[j];
+    const gd3d_params& p = params[k];
+    lt[j] = p.loss_type;
+    a.pred[j] = preds[k];
+    a.gp[j] = grad_preds != nullptr ? grad_preds[k] : nullptr;
+    a.partials[j] = (float*)workspace + j * nbp;
+    a.scale[j] = scales[k];
+    a.alpha[j] = p.alpha;
+    a.ia2[j] = gd3d_inv_alpha2(p.alpha);
+    a.tau[j] = p.tau;
+    for (int q = 0; q < 3; ++q) a.c[j][q] = p.center_offset[q];
+    r.out[j] = loss_sums[k];
+    bits |= (uintptr_t)a.pred[j] | (uintptr_t)a.gp[j];
+  }
+  a.target = target;
+  a.n = n;
+  a.vec_ok = (bits & 15) == 0;
+  // this launch walks the tiles upwards once and leaves the end of the target in the Infinity Cache at best: the next
+  // single launch on this stream starts without reuse (ascending, capped)
+  bool reuse = false;
+  next_tile_order_reversed(s, nullptr, -1, &reuse);
+  const hipError_t e = with_multi_tuple(lt[0], lt[1], lt[2], [&](auto tup) {
+    using T = decltype(tup);
+    constexpr int K = T::count;
+    size_t lds = (size_t)((K + 1) * TILE_F + 32) * sizeof(float);
+    constexpr size_t min_lds = K == 3 ? MULTI_LDS_K3 : MULTI_LDS_K2;
+    if (lds < min_lds) lds = min_lds;
+    hipLaunchKernelGGL((fused_multi_kernel<T::l0, T::l1, T::l2>), dim3((unsigned)nb), dim3(TILE), lds, s, a);
+    return hipGetLastError();
+  });
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(reduce_partials_multi_kernel, dim3((unsigned)count), dim3(1024), 0, s, (const float*)workspace,
+                     (long long)nb, nbp, r);
+  return (int)hipGetLastError();
 }
 
 int gd3d_prof_event_create(void** event) {

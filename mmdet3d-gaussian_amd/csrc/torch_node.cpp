@@ -30,7 +30,11 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <exception>
+#include <limits>
 #include <mutex>
+#include <sstream>
+#include <vector>
 
 #include "../../include/gd3d.h"
 
@@ -46,6 +50,9 @@ struct Abi {
   decltype(&::gd3d_loss_fused_timed) loss_fused_timed = nullptr;
   decltype(&::gd3d_loss_fused_select) loss_fused_select = nullptr;
   decltype(&::gd3d_loss_fused_one_launch) loss_fused_one_launch = nullptr;
+  decltype(&::gd3d_loss_fused_multi) loss_fused_multi = nullptr;
+  decltype(&::gd3d_loss_fused_multi_eligible) loss_fused_multi_eligible = nullptr;
+  decltype(&::gd3d_loss_fused_multi_workspace_bytes) loss_fused_multi_workspace_bytes = nullptr;
   decltype(&::gd3d_grad_finish) grad_finish = nullptr;
   decltype(&::gd3d_loss_fused_cpu) loss_fused_cpu = nullptr;
   decltype(&::gd3d_scale_rows_cpu) scale_rows_cpu = nullptr;
@@ -75,6 +82,9 @@ int bind(const std::string& path) {
   resolve(image, "gd3d_loss_fused_timed", abi.loss_fused_timed);
   resolve(image, "gd3d_loss_fused_select", abi.loss_fused_select);
   resolve(image, "gd3d_loss_fused_one_launch", abi.loss_fused_one_launch);
+  resolve(image, "gd3d_loss_fused_multi", abi.loss_fused_multi);
+  resolve(image, "gd3d_loss_fused_multi_eligible", abi.loss_fused_multi_eligible);
+  resolve(image, "gd3d_loss_fused_multi_workspace_bytes", abi.loss_fused_multi_workspace_bytes);
   resolve(image, "gd3d_grad_finish", abi.grad_finish);
   resolve(image, "gd3d_loss_fused_cpu", abi.loss_fused_cpu);
   resolve(image, "gd3d_scale_rows_cpu", abi.scale_rows_cpu);
@@ -128,7 +138,11 @@ struct Weights {
   }
 };
 
+void flush_pending();   // launches every deferred forward (below)
+
 struct ReducedBackward : public torch::autograd::Node {
+  std::atomic<bool> pending_{false};   // its forward waits in a pending list: gp_ and the loss value are not written yet
+  bool poisoned_ = false;              // its deferred forward was refused (an input changed before the launch)
   torch::autograd::SavedVariable pred_, target_;
   Tensor weight_, aux_, gp_, gt_, buf_;   // aux_: the tensor behind prologue_.aux; buf_: owns the any-positive flag
   gd3d_params params_;
@@ -151,7 +165,9 @@ struct ReducedBackward : public torch::autograd::Node {
   }
 
   variable_list apply(variable_list&& grads) override {
+    if (pending_.load(std::memory_order_acquire)) flush_pending();   // a deferred forward: launch it (and its list) now
     std::lock_guard<std::mutex> lock(mutex_);
+    TORCH_CHECK(!poisoned_, "GDLoss: this loss was never evaluated: one of its inputs was modified in place before its deferred launch");
     const bool twice = at::GradMode::is_enabled();   // create_graph=True: the only case with grad mode ON in here
     at::AutoGradMode no_grad(false);
     variable_list out(2);
@@ -218,6 +234,153 @@ struct ReducedBackward : public torch::autograd::Node {
   }
 };
 
+// ---- deferred forwards: losses queued on one target leave in ONE fused launch (gd3d_loss_fused_multi) -----------------------------
+// An eligible forward (gd_loss.reduced_call decides; `reduced` checks the rest) allocates its loss scalar and its gradient buffer
+// as always and is APPENDED to the pending list of its (device, stream) instead of being launched.  flush_pending() launches a list:
+// one live entry through the single launch it would have taken, two or three through gd3d_loss_fused_multi — the target is read
+// once instead of once per loss; values and gradients are bit-identical either way.  A list is flushed when a forward arrives that
+// does not fit it (another target or n, a pred already queued, three entries), when a queued node's backward runs, and from Python
+// (gd_loss.flush: any use of a LossValue).  An entry owns nothing of its call: the loss scalar is held weakly, and an entry whose
+// loss value was destroyed before the flush is dropped.  At the flush the inputs must still be at the versions they were queued at.
+using ImplPtr = c10::intrusive_ptr<c10::TensorImpl, c10::UndefinedTensorImpl>;
+using WeakImpl = c10::weak_intrusive_ptr<c10::TensorImpl, c10::UndefinedTensorImpl>;
+struct PendingEntry {
+  explicit PendingEntry(const Tensor& loss) : total(loss.getIntrusivePtr()) {}
+  WeakImpl total;   // the loss scalar (it keeps the result + workspace buffer alive); gone: dropped
+  std::weak_ptr<ReducedBackward> node;              // empty: no gradient was asked for
+  bool has_node = false;
+  Tensor pred, target;                              // the caller's own arrays
+  uint32_t pred_version = 0, target_version = 0;
+  float* gp = nullptr;                              // the node's gradient buffer
+  float* base = nullptr;                            // [0] the result, [4:] gd3d_loss_workspace_bytes(n) of workspace
+  gd3d_params params;
+  float scale = 1.0f;
+};
+struct PendingList {
+  c10::Device device{c10::kCPU};
+  void* stream = nullptr;
+  const float* target = nullptr;
+  int64_t n = 0;
+  std::vector<PendingEntry> entries;
+};
+std::mutex g_pending_mu;
+std::vector<PendingList> g_pending;
+std::atomic<int64_t> g_multi_launches{0}, g_single_launches{0}, g_dropped{0};
+
+void flush_list(PendingList& pl) {   // g_pending_mu held
+  std::vector<PendingEntry> entries = std::move(pl.entries);
+  pl.entries.clear();
+  struct Live {
+    PendingEntry* e;
+    ImplPtr total;
+    std::shared_ptr<ReducedBackward> node;
+  };
+  std::vector<Live> good, bad;
+  std::string why;
+  for (PendingEntry& e : entries) {
+    Live l{&e, e.total.lock(), e.node.lock()};
+    if (l.node) l.node->pending_.store(false, std::memory_order_release);
+    if (!l.total.defined() || (e.has_node && !l.node)) {   // the loss value was destroyed unused: nothing to compute
+      g_dropped.fetch_add(1, std::memory_order_relaxed);
+      continue;
+    }
+    const bool pred_ok = e.pred._version() == e.pred_version, target_ok = e.target._version() == e.target_version;
+    if (pred_ok && target_ok) {
+      good.push_back(std::move(l));
+      continue;
+    }
+    if (why.empty()) {
+      const Tensor& t = pred_ok ? e.target : e.pred;
+      std::ostringstream os;
+      os << "GDLoss: one of the variables needed by a deferred loss evaluation has been modified by an inplace operation: ["
+         << t.toString() << " " << t.sizes() << "] (" << (pred_ok ? "target" : "pred") << ") is at version " << t._version()
+         << "; expected version " << (pred_ok ? e.target_version : e.pred_version)
+         << " instead. Hint: call gd_loss.flush() before editing an input in place, or set GD3D_DEFER=0.";
+      why = os.str();
+    }
+    bad.push_back(std::move(l));
+  }
+  c10::OptionalDeviceGuard device_guard;
+  if (!good.empty() || !bad.empty()) device_guard.reset_device(pl.device);
+  if (good.size() == 1) {
+    PendingEntry& e = *good[0].e;
+    g_single_launches.fetch_add(1, std::memory_order_relaxed);
+    fail(abi.loss_fused_timed(&e.params, nullptr, fp(e.pred), fp(e.target), nullptr, nullptr, pl.n, e.scale, nullptr, e.base, e.gp,
+                               nullptr, e.base + 4, pl.stream, nullptr, nullptr), "gd3d_loss_fused_timed");
+  } else if (good.size() >= 2) {
+    const int32_t k = (int32_t)good.size();
+    gd3d_params params[3];
+    const float* preds[3];
+    float scales[3];
+    float* sums[3];
+    float* gps[3];
+    for (int32_t i = 0; i < k; ++i) {
+      const PendingEntry& e = *good[i].e;
+      params[i] = e.params;
+      preds[i] = fp(e.pred);
+      scales[i] = e.scale;
+      sums[i] = e.base;
+      gps[i] = e.gp;
+    }
+    g_multi_launches.fetch_add(1, std::memory_order_relaxed);
+    fail(abi.loss_fused_multi(k, params, preds, pl.target, pl.n, scales, sums, gps, good[0].e->base + 4, pl.stream),
+         "gd3d_loss_fused_multi");
+  }
+  if (!bad.empty()) {   // never computed: the value reads NaN, the node refuses its backward, and this flush raises
+    at::AutoDispatchBelowADInplaceOrView below_autograd;
+    for (Live& l : bad) {
+      if (l.node) l.node->poisoned_ = true;
+      Tensor(l.total).fill_(std::numeric_limits<float>::quiet_NaN());
+    }
+    TORCH_CHECK(false, why);
+  }
+}
+
+void flush_pending() {
+  std::lock_guard<std::mutex> lock(g_pending_mu);
+  std::vector<PendingList> lists = std::move(g_pending);
+  g_pending.clear();
+  std::exception_ptr first;
+  for (PendingList& pl : lists) {
+    try {
+      if (!pl.entries.empty()) flush_list(pl);
+    } catch (...) {
+      if (!first) first = std::current_exception();
+    }
+  }
+  if (first) std::rethrow_exception(first);
+}
+
+// Appends the call to the list of its (device, stream); flushes that list first when the call does not fit it, and afterwards
+// when it is full.
+void enqueue_pending(PendingEntry&& e, const c10::Device& device, void* stream, int64_t n) {
+  std::lock_guard<std::mutex> lock(g_pending_mu);
+  PendingList* pl = nullptr;
+  for (PendingList& l : g_pending)
+    if (l.device == device && l.stream == stream) pl = &l;
+  if (pl == nullptr) {
+    if (g_pending.size() >= 64) {   // streams long gone: launch what they left and start over
+      std::vector<PendingList> lists = std::move(g_pending);
+      g_pending.clear();
+      for (PendingList& l : lists)
+        if (!l.entries.empty()) flush_list(l);
+    }
+    g_pending.emplace_back();
+    pl = &g_pending.back();
+    pl->device = device;
+    pl->stream = stream;
+  }
+  if (!pl->entries.empty()) {
+    bool fits = pl->target == fp(e.target) && pl->n == n && pl->entries.size() < 3;
+    for (const PendingEntry& q : pl->entries) fits = fits && fp(q.pred) != fp(e.pred);
+    if (!fits) flush_list(*pl);
+  }
+  pl->target = fp(e.target);
+  pl->n = n;
+  pl->entries.push_back(std::move(e));
+  if (pl->entries.size() == 3) flush_list(*pl);
+}
+
 // One fused launch for a reduced GDLoss call.  Returns (loss sum as a 0-dim fp32 tensor, the int32 any-positive flag (1,) or
 // None).  params / prologue: addresses of gd3d_params / gd3d_prologue (copied); aux: the tensor prologue->aux points into;
 // ticket: device int32 of gd3d_loss_fused_one_launch or 0 (two-stage form); ev_start / ev_stop: hipEvent_t from
@@ -225,7 +388,7 @@ struct ReducedBackward : public torch::autograd::Node {
 std::tuple<Tensor, c10::optional<Tensor>> reduced(const Tensor& pred, const Tensor& target, const c10::optional<Tensor>& weight,
                                                   int64_t params_addr, int64_t prologue_addr, const c10::optional<Tensor>& aux,
                                                   double scale, bool select, int64_t ticket, int64_t ev_start, int64_t ev_stop,
-                                                  int64_t ws_floats, bool want_flag) {
+                                                  int64_t ws_floats, bool want_flag, bool defer) {
   TORCH_CHECK(pred.dim() == 2 && pred.size(1) == 7 && pred.scalar_type() == at::kFloat && pred.is_contiguous() &&
                   target.sizes() == pred.sizes() && target.scalar_type() == at::kFloat && target.is_contiguous() &&
                   target.device() == pred.device(),
@@ -260,6 +423,7 @@ std::tuple<Tensor, c10::optional<Tensor>> reduced(const Tensor& pred, const Tens
     pro = &prologue;
   }
   Tensor gp, gt, buf, total;
+  void* defer_stream = nullptr;
   {
     at::AutoDispatchBelowADInplaceOrView below_autograd;
     c10::OptionalDeviceGuard device_guard;
@@ -270,7 +434,14 @@ std::tuple<Tensor, c10::optional<Tensor>> reduced(const Tensor& pred, const Tens
     buf = at::empty({4 + ws_floats}, pred.options());
     float* base = buf.data_ptr<float>();
     const Weights ws(w);
-    if (!pred.is_cuda()) {
+    // deferral (see PendingEntry): the caller asked for it and this call is one the multi-loss launch can take
+    defer = defer && pred.is_cuda() && !w.defined() && pro == nullptr && !select && ticket == 0 && ev_start == 0 && ev_stop == 0 &&
+            !need_gt && !want_flag && n > 0 && abi.loss_fused_multi_eligible(&params) != 0 &&
+            (size_t)ws_floats * 4 >= abi.loss_fused_multi_workspace_bytes(3, n) &&
+            (((uintptr_t)fp(pred) | (uintptr_t)fp(target) | (uintptr_t)fp(gp) | (uintptr_t)base) & 15) == 0;
+    if (defer) {
+      defer_stream = current_stream(pred);
+    } else if (!pred.is_cuda()) {
       fail(abi.loss_fused_cpu(&params, fp(pred), fp(target), ws.w1, ws.w7, n, (float)scale, nullptr, base, fp(gp), fp(gt), base + 4,
                                at::get_num_threads()), "gd3d_loss_fused_cpu");
     } else {
@@ -310,6 +481,25 @@ std::tuple<Tensor, c10::optional<Tensor>> reduced(const Tensor& pred, const Tens
     node->scale_ = (float)scale;
     node->n_ = n;
     torch::autograd::set_history(total, node);
+  }
+  if (defer) {
+    PendingEntry e(total);
+    if (node) {
+      node->pending_.store(true, std::memory_order_release);
+      e.node = node;
+      e.has_node = true;
+      e.gp = fp(node->gp_);
+    }
+    e.pred = pred;
+    e.target = target;
+    e.pred_version = pred._version();
+    e.target_version = target._version();
+    e.base = buf.data_ptr<float>();
+    e.params = params;
+    e.scale = (float)scale;
+    const c10::Device device = pred.device();
+    pybind11::gil_scoped_release nogil;   // a flush may free tensors whose Python objects another thread's flush waits behind
+    enqueue_pending(std::move(e), device, defer_stream, n);
   }
   return {total, flag_out};
 }
@@ -626,7 +816,11 @@ PYBIND11_MODULE(_gd3d_node, m) {
   m.doc() = "C++ autograd node of GDLoss's reduced forms above the C ABI of libgd3d.so";
   m.def("reduced", &reduced, py::arg("pred"), py::arg("target"), py::arg("weight"), py::arg("params"), py::arg("prologue"),
         py::arg("aux"), py::arg("scale"), py::arg("select"), py::arg("ticket"), py::arg("ev_start"), py::arg("ev_stop"),
-        py::arg("ws_floats"), py::arg("want_flag"));
+        py::arg("ws_floats"), py::arg("want_flag"), py::arg("defer") = false);
+  m.def("flush_pending", &flush_pending, py::call_guard<py::gil_scoped_release>(),
+        "launch every deferred GDLoss forward (one fused launch per list of two or three losses on one target)");
+  m.def("pending_stats", []() { return std::make_tuple(g_multi_launches.load(), g_single_launches.load(), g_dropped.load()); },
+        "(multi-loss launches, single launches, dropped entries) made by flushes so far");
   m.def("nms_scored", &nms_scored, py::arg("boxes"), py::arg("scores"), py::arg("thresh"), py::arg("n_keep"), py::arg("normal"),
         py::arg("padded"), py::arg("post_max"));
   m.def("anchor_head", &anchor_head, py::arg("bbox_pred"), py::arg("bbox_targets"), py::arg("bbox_weights"), py::arg("anchors"),

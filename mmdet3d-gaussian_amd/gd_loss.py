@@ -165,11 +165,40 @@ _UNIT_ROOT = os.environ.get('GD3D_UNIT_ROOT', '1') != '0'
 _TENSOR_BACKWARD = torch.Tensor.backward
 
 
+# Deferred forwards (C++ node only; csrc/torch_node.cpp, PendingEntry).  A training step evaluates several losses against ONE
+# target; launched one by one each reads that target again.  An eligible forward is therefore QUEUED on its (device, stream), and
+# the queue leaves in one launch that reads the target once (gd3d_loss_fused_multi: 313 us against 369 us for three losses on
+# 10 M rows, profiles/r20_multi_loss_probe.txt) as soon as anything needs a result: any use of a LossValue (`+`, `item`,
+# `detach`, `backward`, printing ...: its __torch_function__ below), a queued node's backward, a forward that does not fit the queue
+# (another target or n, a pred already queued, three queued), or `flush()`.  A LossValue dropped unused is never computed.
+# Eligible: fp32 contiguous 16-byte aligned CUDA rows, no weight, no avg_factor, no prologue, reduction mean / sum, a loss the
+# multi-loss kernel is compiled for (gwd3d / kld3d / bd3d, fun log1p, flag on), LossValue on, no capture, no PROFILE_EVENTS,
+# n >= DEFER_MIN_N.  An input edited in place between the forward and the flush makes the flush raise.  GD3D_DEFER=0: off.
+_DEFER = os.environ.get('GD3D_DEFER', '1') != '0'
+# Smallest n that is queued.  The multi-loss launch wins from the smallest size measured, 32 768 rows (11 us against 26 us of GPU
+# time for three losses, launch-bound; profiles/r20_multi_loss_probe.txt); below that nothing was measured.  Whatever this is set
+# to (tests lower it), calls of gd3d_one_launch_max_n() rows or fewer are never queued: they keep their single-launch form.
+DEFER_MIN_N = 32768
+_deferred = False      # a forward has been queued since the last flush from this module
+
+
+def flush():
+    """Launch every queued GDLoss forward now, on the stream each was queued on (a no-op when nothing is queued)."""
+    global _deferred
+    _deferred = False
+    fn = getattr(_lib._node, 'flush_pending', None)
+    if fn is not None:
+        fn()
+
+
 class LossValue(torch.Tensor):
-    """A loss scalar of this package: a plain tensor in every respect but `.backward()` (see the note above)."""
+    """A loss scalar of this package: a plain tensor in every respect but `.backward()` (see the note above); any use of one
+    first launches the forwards that are still queued (`flush`)."""
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
+        if _deferred:
+            flush()
         if func is _TENSOR_BACKWARD and _UNIT_ROOT:
             kw = dict(kwargs) if kwargs else {}
             self = args[0]
@@ -243,7 +272,7 @@ def per_pair_call(params, pred, target, row_weight, scale, want_loss, want_gp, w
     return loss, gp, gt
 
 
-def reduced_call(params, pred, target, row_weight, scale, prologue=None, select=False, want_flag=False):
+def reduced_call(params, pred, target, row_weight, scale, prologue=None, select=False, want_flag=False, deferrable=False):
     """scale * sum_i w_i L_i as a 0-dim tensor whose autograd node (_pynode.GDLossReduced, or its C++ twin in
     csrc/torch_node.cpp) holds the final gradients the SAME launch produced.  With `select` the value and the gradient are those of the reference's early-out
     `(pred * weight).sum()` when no weight entry is > 0; `want_flag` also returns the int32 (1,) any-positive flag.
@@ -266,8 +295,15 @@ def reduced_call(params, pred, target, row_weight, scale, prologue=None, select=
     trusted = getattr(node, 'reduced_trusted', None)
     if trusted is not None:   # the Python glue: operands were validated by GDLoss.forward, the structs are never rewritten
         return trusted(pred, target, row_weight, params, prologue, aux, scale, select, ticket, ev0, ev1, _ws_floats(n), want_flag)
+    # `deferrable` (GDLoss.forward: no avg_factor, the result becomes a LossValue): queue the call instead of launching it when
+    # the rest of the eligibility rule holds too (see DEFER_MIN_N above; the node checks dtype, alignment and the loss instance)
+    defer = (deferrable and _DEFER and _UNIT_ROOT and pred.is_cuda and ev0 == 0 and ticket == 0 and row_weight is None and
+             prologue is None and not select and n >= DEFER_MIN_N and n > _one_launch_max() and not _capturing())
+    if defer:
+        global _deferred
+        _deferred = True
     return node.reduced(pred, target, row_weight, ctypes.addressof(params), 0 if prologue is None else ctypes.addressof(prologue),
-                        aux, scale, select, ticket, ev0, ev1, _ws_floats(n), want_flag)
+                        aux, scale, select, ticket, ev0, ev1, _ws_floats(n), want_flag, defer)
 
 
 class _GDPerPair(torch.autograd.Function):
@@ -401,7 +437,8 @@ class GDLoss(nn.Module):
             out = _GDPerPair.apply(p, t, w, params, float(scale), prologue)
         else:
             want_flag = select and post_div is not None
-            out, flag = reduced_call(params, p, t, w, float(scale), prologue, select, want_flag)
+            out, flag = reduced_call(params, p, t, w, float(scale), prologue, select, want_flag,
+                                     deferrable=avg_factor is None and out_dtype == torch.float32)
             if post_div is not None:
                 if select:  # the early-out value is not divided by avg_factor (it returns before the loss is called)
                     post_div = torch.where(flag.reshape(()) != 0, post_div.to(torch.float32), 1.0)
