@@ -1256,6 +1256,85 @@ int gd3d_simota_assign_cpu(const float* pred_scores, const float* decoded_bboxes
                            float match_init, int64_t* gt_inds, int64_t* labels, float* max_overlaps, int32_t* pos_cnt,
                            int64_t* pos_inds, int64_t* pos_gt_inds, void* workspace, size_t workspace_bytes);
 
+/* ------------------------------------------------------------------------------------
+ * Sparse 3D convolution (an addition inside ABI 6): spconv 1.x's SubMConv3d / SparseConv3d as mmdet3d's SparseEncoder and the
+ * reference's MlvlSparseEncoder (models/middle_encoders/mlvl_sparse_encoder.py:11-32) use them, and SparseConvTensor.dense().
+ * Neither mmdet3d nor spconv is pinned by the reference: the op is RESTATED here.  A sparse convolution equals the dense conv3d of
+ * the densified input read at the active output sites; that is the oracle of the tests.  fp32 only, dilation 1 only.
+ *
+ * coors (N, 4) int32 rows [b, z, y, x]; spatial_shape, kernel_size, stride, padding: 3 HOST values each, (z, y, x), read during the
+ * call.  K = kz*ky*kx <= 27; offset j = (a*ky + b)*kx + c with a over kz slowest: spconv 1.x's (kz, ky, kx, Cin, Cout) weight stored as
+ * (K, Cin, Cout) fp32.  A row is INACTIVE when any entry is negative, b >= B, or a coordinate lies outside spatial_shape (the tail
+ * rows of gd3d_hard_voxelize are such rows): it produces no output, is never a neighbour and gets a zero gradient.  Active rows
+ * must be unique; with duplicates nothing faults and a look-up finds the LOWEST row of the cell.  Keys are 64-bit,
+ * ((b*D + z)*H + y)*W + x, and a neighbour's coordinate is range-checked per axis BEFORE it is linearised: x = W-1 has no x+1
+ * neighbour in the next row, the last cell of sample b none in sample b+1.
+ *   subm = 1 : every kernel extent odd, stride 1, padding k/2 on every axis, else GD3D_E_BADARG.  R = N output rows,
+ *     out_coors = coors (copied as they are), nbr[o, j] = the input row at (b, z - kz/2 + a, y - ky/2 + b', x - kx/2 + c) or -1 (all -1
+ *     for an inactive row), num = {N, N}, out_batch_cnt[b] = the active rows of sample b.  nbr_t is not written (may be NULL): for
+ *     unique rows nbr_t[i, j] = nbr[i, K-1-j].
+ *   subm = 0 : out_shape = floor((n + 2p - k) / s) + 1 per axis (0 where the kernel does not fit: no output, every count zero).  The active outputs are the cells
+ *     (b, oz, oy, ox) inside out_shape for which some active input and some offset satisfy in = o*s - p + off on every axis;
+ *     out_coors (R, 4), R = max_out, holds them in ascending (b, z, y, x) order (samples stay grouped); num = {rows kept, true count},
+ *     rows kept = min(true count, max_out): the LOWEST keys are kept.  Rows at and past the kept count: coors -1, nbr -1.
+ *     nbr (R, K)[o, j] = the input row at o*s - p + off_j or -1; nbr_t (N, K)[i, j] = the kept output row o with nbr[o, j] == i, or -1
+ *     (never a dropped row).  out_batch_cnt[b] = the kept rows of sample b.
+ *   One stream-ordered run of launches, no host read: keys, rocPRIM's stable radix sort of (key, row), look-ups by lower bound; for
+ *   subm = 0 also a sort of the N*K candidate output keys, head flags, a scan, a compaction.  workspace:
+ *   gd3d_sparse_conv_index_workspace_bytes(N, K, subm) bytes, 256-byte aligned.  N == 0 writes the counts (zeros) and the tail rows.
+ *   N*K and R*K > 2^31 - 1, an extent > 2^24, K > 27, B*D*H*W >= 2^62: GD3D_E_TOOLARGE.
+ * gd3d_sparse_conv_forward : out (R, Cout)[o, :] = sum over j with nbr[o, j] >= 0 of features (N, Cin)[nbr[o, j], :] . weight[j]
+ *   (+ bias), fp32 multiply-adds.  EVERY row of out is written; a row without a valid neighbour (an inactive row, a tail row) and a row
+ *   at or past num[0] (num nullable, device) is ZERO, bias or not.  One launch, a workgroup per 64 rows x 16, 32 or 64 channels, no atomics: the
+ *   same bits from run to run.  An entry of nbr outside [0, N) counts as -1.
+ * gd3d_sparse_conv_backward_input : grad_features (N, Cin)[i, :] = sum over j with t[i, j] >= 0 of grad_out (R, Cout)[t[i, j], :] .
+ *   weight[j]^T, t[i, j] = table[i, j] (flip = 0: table = nbr_t) or table[i, K-1-j] (flip = 1: table = nbr of a submanifold index,
+ *   N == R).  The forward kernel over the transposed table and weight; every row is written.
+ * gd3d_sparse_conv_backward_weight : grad_weight (K, Cin, Cout)[j] = sum over o < num[0] with nbr[o, j] >= 0 of
+ *   features[nbr[o, j], :]^T . grad_out[o, :]; grad_bias (Cout, nullable) = the column sums of grad_out over the rows o < num[0]
+ *   that have a valid neighbour.  Two stages: partial sums per chunk of rows in the workspace
+ *   (gd3d_sparse_conv_backward_weight_workspace_bytes(R, K, Cin, Cout), 256-byte aligned, at most 64 chunks and 64 MiB), then one
+ *   launch that adds the chunks in ascending order.  No atomics: the same bits from run to run.
+ * gd3d_sparse_to_dense : dense (B, C, D, H, W) fp32 = zeros, then dense[b, :, z, y, x] = features (N, C)[row] for every active row: a
+ *   fill and one launch (gd3d_pillar_scatter's 3D sibling).  _backward: grad_features[row] = grad_dense[b, :, z, y, x], zeros for an
+ *   inactive row: one gather, every element written.
+ * Cin, Cout, C, K >= 1 (GD3D_E_BADARG); Cin, Cout, C <= 256, K <= 27, N, R <= 2^31 - 1 (GD3D_E_TOOLARGE).  R == 0 (forward), N == 0
+ * (backward_input) launch nothing.
+ * `_cpu` twins (csrc/sparse_conv_cpu.cpp): the same contracts on HOST memory on the calling thread; workspace is ignored.  Every
+ *   INTEGER output is bit-identical to the kernels'; the values are summed offset by offset, channel by channel — another order than
+ *   the kernels' tiles — and agree with them to fp32 rounding, not to the bit.
+ * ---------------------------------------------------------------------------------- */
+size_t gd3d_sparse_conv_index_workspace_bytes(int64_t N, int32_t K, int32_t subm);
+int gd3d_sparse_conv_index(const int32_t* coors, int64_t N, int32_t B, const int32_t* spatial_shape, const int32_t* kernel_size,
+                           const int32_t* stride, const int32_t* padding, int32_t subm, int64_t max_out, void* workspace,
+                           int32_t* out_coors, int32_t* nbr, int32_t* nbr_t, int64_t* num, int32_t* out_batch_cnt, void* stream);
+int gd3d_sparse_conv_forward(const float* features, const float* weight, const float* bias, const int32_t* nbr, const int64_t* num,
+                             int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, float* out, void* stream);
+int gd3d_sparse_conv_backward_input(const float* grad_out, const float* weight, const int32_t* table, int32_t flip, int64_t N,
+                                    int64_t R, int32_t K, int32_t Cin, int32_t Cout, float* grad_features, void* stream);
+size_t gd3d_sparse_conv_backward_weight_workspace_bytes(int64_t R, int32_t K, int32_t Cin, int32_t Cout);
+int gd3d_sparse_conv_backward_weight(const float* features, const float* grad_out, const int32_t* nbr, const int64_t* num, int64_t N,
+                                     int64_t R, int32_t K, int32_t Cin, int32_t Cout, void* workspace, float* grad_weight,
+                                     float* grad_bias, void* stream);
+int gd3d_sparse_to_dense(const float* features, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W,
+                         float* dense, void* stream);
+int gd3d_sparse_to_dense_backward(const float* grad_dense, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H,
+                                  int32_t W, float* grad_features, void* stream);
+int gd3d_sparse_conv_index_cpu(const int32_t* coors, int64_t N, int32_t B, const int32_t* spatial_shape, const int32_t* kernel_size,
+                               const int32_t* stride, const int32_t* padding, int32_t subm, int64_t max_out, void* workspace,
+                               int32_t* out_coors, int32_t* nbr, int32_t* nbr_t, int64_t* num, int32_t* out_batch_cnt);
+int gd3d_sparse_conv_forward_cpu(const float* features, const float* weight, const float* bias, const int32_t* nbr, const int64_t* num,
+                                 int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, float* out);
+int gd3d_sparse_conv_backward_input_cpu(const float* grad_out, const float* weight, const int32_t* table, int32_t flip, int64_t N,
+                                        int64_t R, int32_t K, int32_t Cin, int32_t Cout, float* grad_features);
+int gd3d_sparse_conv_backward_weight_cpu(const float* features, const float* grad_out, const int32_t* nbr, const int64_t* num, int64_t N,
+                                         int64_t R, int32_t K, int32_t Cin, int32_t Cout, void* workspace, float* grad_weight,
+                                         float* grad_bias);
+int gd3d_sparse_to_dense_cpu(const float* features, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H,
+                             int32_t W, float* dense);
+int gd3d_sparse_to_dense_backward_cpu(const float* grad_dense, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D,
+                                      int32_t H, int32_t W, float* grad_features);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

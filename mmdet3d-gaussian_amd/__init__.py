@@ -32,6 +32,10 @@
   * ``multi_view_voxelize`` / ``to_cylindrical`` / ``to_spherical`` / ``pillar_scatter`` / ``PointPillarsScatter`` / ``view_sample`` — the
                                  multi-view pillar encoder's view ops (pillar_od.py:24-70, pillar_mvf_encoder.py:80-107): every view's
                                  transform and cells in one launch, the dense pillar canvas, the per-point view-map sampling
+  * ``sparse_conv_index`` / ``sparse_conv`` / ``sparse_to_dense`` / ``SparseConvTensor`` / ``SubMConv3d`` / ``SparseConv3d`` /
+    ``SparseSequential`` / ``SparseBasicBlock`` / ``make_sparse_convmodule`` / ``SparseEncoder`` / ``MlvlSparseEncoder`` — the sparse 3D
+                                 convolution of the middle encoders (middle_encoders/mlvl_sparse_encoder.py:11-32; spconv 1.x's surface,
+                                 restated): neighbour tables in one stream-ordered build, one launch per layer forward, no atomics
   * ``GraphedStep``            — a launch-bound loss slice, forward and backward, captured once as a hipGraph and replayed
 Everything outside §8 that earlier rounds built (frozen, DESIGN_EXTRAS.md) lives in ``mmdet3d_gaussian_amd.extras``.
 
@@ -63,6 +67,8 @@ from .voxelize import HardSimpleVFE, Voxelization, dynamic_voxelize, hard_voxeli
 from .pillar_feat import PillarFeatureDecorator, PointVoxelStatsCalculator, pillar_decorate, point_voxel_stats
 from .view_net import PointPillarsScatter, multi_view_voxelize, pillar_scatter, to_cylindrical, to_spherical, view_sample
 from .simota import Point3DRangeGenerator, SimOTABEVAssigner, simota_assign
+from .sparse_conv import (MlvlSparseEncoder, SparseBasicBlock, SparseConv3d, SparseConvIndex, SparseConvTensor, SparseEncoder, SparseModule,
+                          SparseSequential, SubMConv3d, make_sparse_convmodule, sparse_conv, sparse_conv_index, sparse_to_dense)
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
                         anchor_head_decoded_loss_fused, center_head_gd_loss, center_head_losses)
 from . import extras
@@ -88,4 +94,6 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'keypoint_reweight', 'bev_interpolate', 'voxel_centers', 'sample_keypoints', 'hard_voxelize', 'dynamic_voxelize', 'Voxelization',
            'HardSimpleVFE', 'voxel_mean', 'pvrcnn_voxelize', 'point_voxel_stats', 'PointVoxelStatsCalculator',
            'pillar_decorate', 'PillarFeatureDecorator', 'multi_view_voxelize', 'to_cylindrical', 'to_spherical', 'pillar_scatter',
-           'PointPillarsScatter', 'view_sample', 'simota_assign', 'SimOTABEVAssigner', 'Point3DRangeGenerator', 'extras']
+           'PointPillarsScatter', 'view_sample', 'simota_assign', 'SimOTABEVAssigner', 'Point3DRangeGenerator', 'sparse_conv_index', 'sparse_conv',
+           'sparse_to_dense', 'SparseConvIndex', 'SparseConvTensor', 'SparseModule', 'SubMConv3d', 'SparseConv3d', 'SparseSequential', 'SparseBasicBlock',
+           'make_sparse_convmodule', 'SparseEncoder', 'MlvlSparseEncoder', 'extras']

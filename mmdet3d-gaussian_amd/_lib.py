@@ -317,6 +317,20 @@ SYMBOLS = {
                                   _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'gd3d_simota_assign_cpu': (_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _f32,
                                       _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    'gd3d_sparse_conv_index_workspace_bytes': (_sz, [_i64, _i32, _i32]),
+    'gd3d_sparse_conv_index': (_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_sparse_conv_forward': (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    'gd3d_sparse_conv_backward_input': (_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    'gd3d_sparse_conv_backward_weight_workspace_bytes': (_sz, [_i64, _i32, _i32, _i32]),
+    'gd3d_sparse_conv_backward_weight': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'gd3d_sparse_to_dense': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'gd3d_sparse_to_dense_backward': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'gd3d_sparse_conv_index_cpu': (_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_sparse_conv_forward_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    'gd3d_sparse_conv_backward_input_cpu': (_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp]),
+    'gd3d_sparse_conv_backward_weight_cpu': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'gd3d_sparse_to_dense_cpu': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    'gd3d_sparse_to_dense_backward_cpu': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 

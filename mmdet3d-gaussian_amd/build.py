@@ -41,6 +41,7 @@ SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'pillar_feat.hip': ['-ffp-contract=off'],  # the voxel table, the centres, the offsets and the distance replay bit for bit in pillar_feat_cpu.cpp
     'view_net.hip': ['-ffp-contract=off'],     # the view transforms, the cells, the canvas and the sampled features replay bit for bit in view_net_cpu.cpp
     'simota.hip': ['-ffp-contract=off'],       # memberships, the IoU, the costs on fx_logf, both selections and every match replay bit for bit in simota_cpu.cpp
+    'sparse_conv.hip': ['-ffp-contract=off'],  # every table of the index build replays bit for bit in sparse_conv_cpu.cpp; explicit fmaf for the values; rocPRIM sort + scan
 }
 # The frozen round-3 extras OUTSIDE §8 (DESIGN_EXTRAS.md; include/gd3d_extras.h): a library of their own since round 6,
 # libgd3d_extras.so, linked against libgd3d.so (the inference slices call its rnms_* entry points) and loaded only by
@@ -74,6 +75,7 @@ HOST_SOURCES = {
     'pillar_feat_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],  # same for pillar_feat.hip: every output bit-identical
     'view_net_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],     # same for view_net.hip: every forward output bit-identical
     'simota_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],       # same for simota.hip: every output bit-identical
+    'sparse_conv_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],  # same for sparse_conv.hip: every integer output bit-identical
 }
 HOST_COMMON = ['-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 

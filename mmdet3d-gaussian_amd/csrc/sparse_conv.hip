@@ -1,0 +1,676 @@
+// sparse_conv.hip — sparse 3D convolution (spconv 1.x's SubMConv3d / SparseConv3d, restated: include/gd3d.h, gd3d_sparse_conv_*;
+// DESIGN.md §3.18) for gfx950: the index build, the forward and input-gradient implicit GEMM, the two-stage weight gradient, and
+// SparseConvTensor.dense() with its backward.  Every call is one stream-ordered run of launches that reads nothing back.
+//   index build   key_kernel     one int64 key per input row, ((b * D + z) * H + y) * W + x, or the sentinel B*D*H*W for an inactive row
+//                 radix sort     (key, row) pairs, stable: a look-up by lower bound finds the LOWEST row of a duplicated cell.  rocPRIM's
+//                                device radix sort, as in hard_voxel.hip.
+//                 submanifold    subm_kernel: a thread per (row, offset) looks its neighbour's coordinate up
+//                 regular        cand_kernel (the output cell of every (row, offset) pair, or the sentinel), a radix sort of those
+//                                keys, head flags, a plus-scan and a compaction give the unique output keys in ascending order;
+//                                finish_kernel the counts; out_kernel decodes the kept keys and looks the inputs up; nbrt_kernel
+//                                looks every input row's outputs up in the kept keys
+//   gemm_kernel   output stationary: a workgroup owns TILE_M rows x 16, 32 or 64 channels (the smallest tile that holds Cout), walks the offsets, skips (workgroup-uniformly)
+//                 an offset no row of the tile uses, stages the gathered rows and the weight slice in LDS, accumulates with fmaf in
+//                 registers and writes every element once.  The input gradient is the same kernel over the transposed table and
+//                 weight.  No atomics: the bits replay.
+//   wgrad_kernel  per (row chunk, offset, tile of W[j] of 16, 32 or 64 channels a side): partial sums into the workspace; wfinish_kernel adds the chunks in
+//                 ascending order.  bias_kernel / the same finish for the bias gradient.
+// Compiled with -ffp-contract=off (the tables replay bit for bit in csrc/sparse_conv_cpu.cpp); the multiply-adds are explicit fmaf.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "../../include/gd3d.h"
+#include "gd3d_fill.h"
+#include "sparse_conv_common.h"
+
+namespace sparse_conv {
+
+constexpr int BLOCK = 256;
+
+static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+static unsigned blocks_of(long long threads) { return (unsigned)((threads + BLOCK - 1) / BLOCK); }
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+static int key_bits(long long sentinel) {   // the bits of the largest key
+  int bits = 1;
+  while (bits < 63 && (sentinel >> bits) != 0) ++bits;
+  return bits;
+}
+
+struct Layout {   // carve of the caller's workspace (all offsets multiples of 256 bytes)
+  size_t key_in, skey, val_in, srow, cand, scand, flag, pos, sort_tmp, total;
+  size_t sort_bytes;
+};
+
+static hipError_t layout(int64_t n, int64_t m, bool subm, Layout& L) {   // m = n * K
+  size_t a = 0, b = 0, c = 0;
+  hipError_t e = rocprim::radix_sort_pairs(nullptr, a, (const long long*)nullptr, (long long*)nullptr, (const int*)nullptr,
+                                           (int*)nullptr, (size_t)n, 0, 64, (hipStream_t)0);
+  if (e != hipSuccess) return e;
+  if (!subm) {
+    e = rocprim::radix_sort_keys(nullptr, b, (const long long*)nullptr, (long long*)nullptr, (size_t)m, 0, 64, (hipStream_t)0);
+    if (e != hipSuccess) return e;
+    e = rocprim::exclusive_scan(nullptr, c, (const int*)nullptr, (int*)nullptr, 0, (size_t)m, rocprim::plus<int>(), (hipStream_t)0);
+    if (e != hipSuccess) return e;
+  }
+  L.sort_bytes = a > b ? (a > c ? a : c) : (b > c ? b : c);
+  size_t o = 0;
+  L.key_in = o; o += up256(sizeof(long long) * (size_t)n);
+  L.skey = o; o += up256(sizeof(long long) * (size_t)n);
+  L.val_in = o; o += up256(sizeof(int) * (size_t)n);
+  L.srow = o; o += up256(sizeof(int) * (size_t)n);
+  const size_t mm = subm ? 0 : (size_t)m;
+  L.cand = o; o += up256(sizeof(long long) * mm);
+  L.scand = o; o += up256(sizeof(long long) * mm);
+  L.flag = o; o += up256(sizeof(int) * mm);
+  L.pos = o; o += up256(sizeof(int) * mm);
+  L.sort_tmp = o; o += up256(L.sort_bytes);
+  L.total = o;
+  return hipSuccess;
+}
+
+__global__ __launch_bounds__(BLOCK) void key_kernel(const int32_t* __restrict__ coors, long long n, const Geo g,
+                                                    long long* __restrict__ keys, int* __restrict__ vals) {
+  const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const int32_t* c = coors + i * 4;
+  keys[i] = row_active(c, g) ? in_key(g, c[0], c[1], c[2], c[3]) : g.in_sent;
+  vals[i] = (int)i;
+}
+
+// a thread per (row, offset): out_coors = coors, nbr[o, j] = the row at the neighbour's coordinate
+__global__ __launch_bounds__(BLOCK) void subm_kernel(const int32_t* __restrict__ coors, long long n, const Geo g,
+                                                     const long long* __restrict__ skey, const int* __restrict__ srow,
+                                                     int32_t* __restrict__ out_coors, int32_t* __restrict__ nbr) {
+  const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= n * g.K) return;
+  const long long o = t / g.K;
+  const int j = (int)(t - o * g.K);
+  const int32_t* c = coors + o * 4;
+  if (j == 0) {
+    for (int a = 0; a < 4; ++a) out_coors[o * 4 + a] = c[a];
+  }
+  int32_t v = -1;
+  if (row_active(c, g)) {
+    int off[3], in[3];
+    const int oc[3] = {c[1], c[2], c[3]};
+    split_offset(g, j, off);
+    if (input_of(g, oc, off, in)) v = find_row(skey, srow, n, in_key(g, c[0], in[0], in[1], in[2]));
+  }
+  nbr[t] = v;
+}
+
+__global__ __launch_bounds__(BLOCK) void cand_kernel(const int32_t* __restrict__ coors, long long n, const Geo g,
+                                                     long long* __restrict__ cand) {
+  const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= n * g.K) return;
+  const long long i = t / g.K;
+  const int j = (int)(t - i * g.K);
+  const int32_t* c = coors + i * 4;
+  long long key = g.out_sent;
+  if (row_active(c, g)) {
+    int off[3], o[3];
+    const int in[3] = {c[1], c[2], c[3]};
+    split_offset(g, j, off);
+    if (output_of(g, in, off, o)) key = out_key(g, c[0], o[0], o[1], o[2]);
+  }
+  cand[t] = key;
+}
+
+__global__ __launch_bounds__(BLOCK) void head_kernel(const long long* __restrict__ scand, long long m, long long sentinel,
+                                                     int* __restrict__ flag) {
+  const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= m) return;
+  const long long key = scand[t];
+  flag[t] = (key != sentinel && (t == 0 || key != scand[t - 1])) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(BLOCK) void compact_kernel(const long long* __restrict__ scand, const int* __restrict__ flag,
+                                                        const int* __restrict__ pos, long long m, long long* __restrict__ ukey) {
+  const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= m) return;
+  if (flag[t]) ukey[pos[t]] = scand[t];                         // pos[t] <= t: inside the m entries of ukey
+}
+
+// One workgroup.  keys: the sorted input keys (subm) or the unique output keys (regular); `cells`: keys of one sample.
+__global__ __launch_bounds__(BLOCK) void finish_kernel(const long long* __restrict__ keys, long long n_keys, const int* __restrict__ flag,
+                                                       const int* __restrict__ pos, long long m, long long max_out, long long sentinel,
+                                                       int B, int subm, long long* __restrict__ num, int32_t* __restrict__ out_batch_cnt) {
+  long long total, kept;
+  if (subm) {
+    total = kept = n_keys;                                      // every row is an output row
+  } else {
+    total = m > 0 ? (long long)pos[m - 1] + flag[m - 1] : 0;
+    kept = total < max_out ? total : max_out;
+    n_keys = kept;
+  }
+  if (threadIdx.x == 0) { num[0] = kept; num[1] = total; }
+  const long long cells = B > 0 ? sentinel / B : 0;
+  for (int b = threadIdx.x; b < B; b += BLOCK)
+    out_batch_cnt[b] = (int32_t)(lower_bound(keys, n_keys, (long long)(b + 1) * cells) - lower_bound(keys, n_keys, (long long)b * cells));
+}
+
+// a thread per (output row, offset) of the R = max_out rows
+__global__ __launch_bounds__(BLOCK) void out_kernel(const long long* __restrict__ ukey, const long long* __restrict__ num, long long rows,
+                                                    long long n, const Geo g, const long long* __restrict__ skey,
+                                                    const int* __restrict__ srow, int32_t* __restrict__ out_coors,
+                                                    int32_t* __restrict__ nbr) {
+  const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= rows * g.K) return;
+  const long long r = t / g.K;
+  const int j = (int)(t - r * g.K);
+  int32_t c[4] = {-1, -1, -1, -1};
+  int32_t v = -1;
+  if (r < num[0]) {
+    decode_out(g, ukey[r], c);
+    int off[3], in[3];
+    const int oc[3] = {c[1], c[2], c[3]};
+    split_offset(g, j, off);
+    if (input_of(g, oc, off, in)) v = find_row(skey, srow, n, in_key(g, c[0], in[0], in[1], in[2]));
+  }
+  if (j == 0) {
+    for (int a = 0; a < 4; ++a) out_coors[r * 4 + a] = c[a];
+  }
+  nbr[t] = v;
+}
+
+// a thread per (input row, offset): the kept output row that reads this row through this offset
+__global__ __launch_bounds__(BLOCK) void nbrt_kernel(const int32_t* __restrict__ coors, long long n, const Geo g,
+                                                     const long long* __restrict__ skey, const int* __restrict__ srow,
+                                                     const long long* __restrict__ ukey, const long long* __restrict__ num,
+                                                     int32_t* __restrict__ nbr_t) {
+  const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= n * g.K) return;
+  const long long i = t / g.K;
+  const int j = (int)(t - i * g.K);
+  const int32_t* c = coors + i * 4;
+  int32_t v = -1;
+  // of the rows of a duplicated cell only the one the look-up finds is anybody's neighbour
+  if (row_active(c, g) && find_row(skey, srow, n, in_key(g, c[0], c[1], c[2], c[3])) == (int32_t)i) {
+    int off[3], o[3];
+    const int in[3] = {c[1], c[2], c[3]};
+    split_offset(g, j, off);
+    if (output_of(g, in, off, o)) {
+      const long long kept = num[0], key = out_key(g, c[0], o[0], o[1], o[2]);
+      const long long at = lower_bound(ukey, kept, key);
+      if (at < kept && ukey[at] == key) v = (int32_t)at;
+    }
+  }
+  nbr_t[t] = v;
+}
+
+// ---- the implicit GEMM ---------------------------------------------------------------------------------------------------------------
+
+struct GemmArgs {
+  const float* src;        // (n_src, Cr): the rows gathered
+  const float* W;          // (K, Cin, Cout)
+  const float* bias;       // (Co) or null
+  const int32_t* table;    // (rows, K)
+  const long long* num;    // nullable: rows at and past num[0] are zeros
+  long long n_src, rows;
+  int K, Cr, Co, flip;     // flip: the table's column of offset j is K - 1 - j (the submanifold transpose)
+  float* out;              // (rows, Co)
+};
+
+// TRANS: the weight slice is read transposed (the input gradient: Cr = Cout, Co = Cin).  VEC: Co % 4 == 0 and `out` 16-byte aligned.
+// TN: the output channels of one workgroup, 16, 32 or 64 — the smallest that holds Co, so that a 16-channel layer keeps every thread
+// busy: TN / 4 threads lie along the channels (4 each), the other BLOCK / (TN / 4) along the TILE_M rows (TN / 16 rows each).
+template <bool TRANS, bool VEC, int TN>
+__global__ __launch_bounds__(BLOCK) void gemm_kernel(const GemmArgs a) {
+  constexpr int CT = TN / 4, RPT = TILE_M * CT / BLOCK;
+  __shared__ int nb[TILE_M];
+  __shared__ int used[TILE_M];
+  __shared__ float Xs[TILE_M][TILE_K + 1];
+  __shared__ __attribute__((aligned(16))) float Ws[TILE_K][TN];
+  const int t = threadIdx.x, tx = t % CT, ty = t / CT;
+  const long long row0 = (long long)blockIdx.x * TILE_M;
+  const int col0 = blockIdx.y * TN;
+  long long limit = a.rows;
+  if (a.num != nullptr) { const long long k = a.num[0]; limit = k < limit ? (k < 0 ? 0 : k) : limit; }
+  float acc[RPT][4];
+  for (int i = 0; i < RPT; ++i)
+    for (int q = 0; q < 4; ++q) acc[i][q] = 0.0f;
+  int mine = 0;                                                  // thread t < TILE_M: whether row t has any neighbour
+  for (int j = 0; j < a.K; ++j) {
+    int v = -1;
+    if (t < TILE_M && row0 + t < limit) {
+      v = a.table[(row0 + t) * a.K + (a.flip ? a.K - 1 - j : j)];
+      if (v < 0 || v >= a.n_src) v = -1;
+    }
+    if (t < TILE_M) { nb[t] = v; mine |= v >= 0; }
+    if (!__syncthreads_or(v >= 0)) continue;                     // nobody reads nb[] of a skipped offset
+    const float* Wj = a.W + (long long)j * a.Cr * a.Co;
+    for (int kc = 0; kc < a.Cr; kc += TILE_K) {
+      for (int idx = t; idx < TILE_M * TILE_K; idx += BLOCK) {
+        const int r = idx / TILE_K, kk = idx % TILE_K;
+        const int row = nb[r];
+        Xs[r][kk] = (row >= 0 && kc + kk < a.Cr) ? a.src[(long long)row * a.Cr + kc + kk] : 0.0f;
+      }
+      for (int idx = t; idx < TILE_K * TN; idx += BLOCK) {
+        const int kk = idx / TN, c = idx % TN;
+        float w = 0.0f;
+        if (kc + kk < a.Cr && col0 + c < a.Co)
+          w = TRANS ? Wj[(long long)(col0 + c) * a.Cr + kc + kk] : Wj[(long long)(kc + kk) * a.Co + col0 + c];
+        Ws[kk][c] = w;
+      }
+      __syncthreads();
+      const int kn = a.Cr - kc < TILE_K ? a.Cr - kc : TILE_K;
+      for (int kk = 0; kk < kn; ++kk) {
+        const float4 w = *reinterpret_cast<const float4*>(&Ws[kk][tx * 4]);
+#pragma unroll
+        for (int i = 0; i < RPT; ++i) {
+          const float x = Xs[ty * RPT + i][kk];
+          acc[i][0] = __builtin_fmaf(x, w.x, acc[i][0]);
+          acc[i][1] = __builtin_fmaf(x, w.y, acc[i][1]);
+          acc[i][2] = __builtin_fmaf(x, w.z, acc[i][2]);
+          acc[i][3] = __builtin_fmaf(x, w.w, acc[i][3]);
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (t < TILE_M) used[t] = mine;
+  __syncthreads();
+  const int c = col0 + tx * 4;
+#pragma unroll
+  for (int i = 0; i < RPT; ++i) {
+    const long long row = row0 + ty * RPT + i;
+    if (row >= a.rows) continue;
+    const bool live = used[ty * RPT + i] != 0;                   // a row without neighbours (inactive, or past the count) is zero, bias or not
+    float o[4];
+    for (int q = 0; q < 4; ++q) o[q] = live ? acc[i][q] + ((a.bias != nullptr && c + q < a.Co) ? a.bias[c + q] : 0.0f) : 0.0f;
+    float* dst = a.out + row * a.Co + c;
+    if (VEC) {
+      if (c < a.Co) *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+      for (int q = 0; q < 4; ++q)
+        if (c + q < a.Co) dst[q] = o[q];
+    }
+  }
+}
+
+template <int TN>
+static int launch_gemm_tile(const GemmArgs& a, bool trans, hipStream_t s) {
+  const dim3 grid((unsigned)((a.rows + TILE_M - 1) / TILE_M), (unsigned)((a.Co + TN - 1) / TN));
+  const bool vec = a.Co % 4 == 0 && aligned16(a.out);
+  if (trans) {
+    if (vec) hipLaunchKernelGGL((gemm_kernel<true, true, TN>), grid, dim3(BLOCK), 0, s, a);
+    else hipLaunchKernelGGL((gemm_kernel<true, false, TN>), grid, dim3(BLOCK), 0, s, a);
+  } else {
+    if (vec) hipLaunchKernelGGL((gemm_kernel<false, true, TN>), grid, dim3(BLOCK), 0, s, a);
+    else hipLaunchKernelGGL((gemm_kernel<false, false, TN>), grid, dim3(BLOCK), 0, s, a);
+  }
+  return (int)hipGetLastError();
+}
+
+static int tile_of(int channels) { return channels <= 16 ? 16 : (channels <= 32 ? 32 : 64); }   // the smallest tile that holds them, at most 64
+
+static int launch_gemm(const GemmArgs& a, bool trans, hipStream_t s) {
+  switch (tile_of(a.Co)) {
+    case 16: return launch_gemm_tile<16>(a, trans, s);
+    case 32: return launch_gemm_tile<32>(a, trans, s);
+    default: return launch_gemm_tile<TILE_N>(a, trans, s);
+  }
+}
+
+// ---- the weight gradient ---------------------------------------------------------------------------------------------------------------
+
+struct WgradArgs {
+  const float *X, *gY;
+  const int32_t* nbr;
+  const long long* num;
+  long long n_src, rows, chunk, parts;
+  int K, Cin, Cout, tiles_co;
+  float *part_w, *part_b;   // (parts, K, Cin, Cout) and (parts, Cout)
+  float *gW, *gb;           // gb nullable
+};
+
+__device__ __forceinline__ long long row_limit(const long long* num, long long rows) {
+  if (num == nullptr) return rows;
+  const long long k = num[0];
+  return k < rows ? (k < 0 ? 0 : k) : rows;
+}
+
+// grid (parts, K, tiles of TI x TO of W[j]): the partial sum of chunk p.  TI, TO in {16, 32, 64}: the smallest tiles that hold Cin and
+// Cout; a thread owns TI / 16 x TO / 16 elements.
+template <int TI, int TO>
+__global__ __launch_bounds__(BLOCK) void wgrad_kernel(const WgradArgs a) {
+  constexpr int MI = TI / 16, MO = TO / 16;
+  __shared__ int nb[WG_ROWS];
+  __shared__ float Xg[WG_ROWS][TI];
+  __shared__ float Gy[WG_ROWS][TO];
+  const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+  const int j = blockIdx.y;
+  const int ci0 = (blockIdx.z / a.tiles_co) * TI, co0 = (blockIdx.z % a.tiles_co) * TO;
+  const long long limit = row_limit(a.num, a.rows);
+  const long long begin = (long long)blockIdx.x * a.chunk;
+  long long end = begin + a.chunk;
+  end = end < limit ? end : limit;
+  float acc[MI][MO];
+  for (int i = 0; i < MI; ++i)
+    for (int q = 0; q < MO; ++q) acc[i][q] = 0.0f;
+  for (long long r0 = begin; r0 < end; r0 += WG_ROWS) {          // begin, end, r0: the same for the whole workgroup
+    int v = -1;
+    if (t < WG_ROWS && r0 + t < end) {
+      v = a.nbr[(r0 + t) * a.K + j];
+      if (v < 0 || v >= a.n_src) v = -1;
+    }
+    if (t < WG_ROWS) nb[t] = v;
+    if (!__syncthreads_or(v >= 0)) continue;
+    for (int idx = t; idx < WG_ROWS * TI; idx += BLOCK) {
+      const int r = idx / TI, c = idx % TI;
+      const int row = nb[r];
+      Xg[r][c] = (row >= 0 && ci0 + c < a.Cin) ? a.X[(long long)row * a.Cin + ci0 + c] : 0.0f;
+    }
+    for (int idx = t; idx < WG_ROWS * TO; idx += BLOCK) {
+      const int r = idx / TO, c = idx % TO;
+      Gy[r][c] = (nb[r] >= 0 && co0 + c < a.Cout) ? a.gY[(r0 + r) * a.Cout + co0 + c] : 0.0f;
+    }
+    __syncthreads();
+    for (int r = 0; r < WG_ROWS; ++r) {
+      float x[MI], g[MO];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) x[i] = Xg[r][ty * MI + i];
+#pragma unroll
+      for (int q = 0; q < MO; ++q) g[q] = Gy[r][tx * MO + q];
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int q = 0; q < MO; ++q) acc[i][q] = __builtin_fmaf(x[i], g[q], acc[i][q]);
+    }
+    __syncthreads();
+  }
+  float* dst = a.part_w + ((long long)blockIdx.x * a.K + j) * a.Cin * a.Cout;
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int ci = ci0 + ty * MI + i;
+    if (ci >= a.Cin) continue;
+#pragma unroll
+    for (int q = 0; q < MO; ++q) {
+      const int co = co0 + tx * MO + q;
+      if (co < a.Cout) dst[(long long)ci * a.Cout + co] = acc[i][q];
+    }
+  }
+}
+
+template <int TI>
+static void launch_wgrad_in(WgradArgs& a, int to, hipStream_t s) {
+  a.tiles_co = (a.Cout + to - 1) / to;
+  const dim3 grid((unsigned)a.parts, (unsigned)a.K, (unsigned)(((a.Cin + TI - 1) / TI) * a.tiles_co));
+  switch (to) {
+    case 16: hipLaunchKernelGGL((wgrad_kernel<TI, 16>), grid, dim3(BLOCK), 0, s, a); break;
+    case 32: hipLaunchKernelGGL((wgrad_kernel<TI, 32>), grid, dim3(BLOCK), 0, s, a); break;
+    default: hipLaunchKernelGGL((wgrad_kernel<TI, 64>), grid, dim3(BLOCK), 0, s, a); break;
+  }
+}
+
+static void launch_wgrad(WgradArgs& a, hipStream_t s) {
+  const int to = tile_of(a.Cout);
+  switch (tile_of(a.Cin)) {
+    case 16: launch_wgrad_in<16>(a, to, s); break;
+    case 32: launch_wgrad_in<32>(a, to, s); break;
+    default: launch_wgrad_in<64>(a, to, s); break;
+  }
+}
+
+// grid (parts): column sums of gY over the chunk's rows that have a neighbour.  The workgroup's threads form 256 / CP groups of CP >= Cout
+// columns (CP a power of two); group g adds the rows g, g + groups, ... of every 256-row step, then the groups are added in ascending order.
+__global__ __launch_bounds__(BLOCK) void bias_kernel(const WgradArgs a, const int CP) {
+  __shared__ int live[BLOCK];
+  __shared__ float red[BLOCK];
+  const int t = threadIdx.x, col = t % CP, grp = t / CP, groups = BLOCK / CP;
+  const long long limit = row_limit(a.num, a.rows);
+  const long long begin = (long long)blockIdx.x * a.chunk;
+  long long end = begin + a.chunk;
+  end = end < limit ? end : limit;
+  float acc = 0.0f;
+  for (long long r0 = begin; r0 < end; r0 += BLOCK) {
+    int any = 0;
+    if (r0 + t < end) {
+      for (int j = 0; j < a.K; ++j) {
+        const int v = a.nbr[(r0 + t) * a.K + j];
+        any |= v >= 0 && v < a.n_src;
+      }
+    }
+    live[t] = any;
+    __syncthreads();
+    const int rn = end - r0 < BLOCK ? (int)(end - r0) : BLOCK;
+    if (col < a.Cout)
+      for (int r = grp; r < rn; r += groups)
+        if (live[r]) acc += a.gY[(r0 + r) * a.Cout + col];
+    __syncthreads();
+  }
+  red[t] = acc;
+  __syncthreads();
+  if (grp == 0 && col < a.Cout) {
+    float s = 0.0f;
+    for (int g = 0; g < groups; ++g) s += red[g * CP + col];
+    a.part_b[(long long)blockIdx.x * a.Cout + col] = s;
+  }
+}
+
+// the chunks' partial sums added in ascending chunk order
+__global__ __launch_bounds__(BLOCK) void wfinish_kernel(const WgradArgs a) {
+  const long long kcc = (long long)a.K * a.Cin * a.Cout;
+  const long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (idx < kcc) {
+    float s = 0.0f;
+    for (long long p = 0; p < a.parts; ++p) s += a.part_w[p * kcc + idx];
+    a.gW[idx] = s;
+  } else if (a.gb != nullptr && idx - kcc < a.Cout) {
+    const long long c = idx - kcc;
+    float s = 0.0f;
+    for (long long p = 0; p < a.parts; ++p) s += a.part_b[p * a.Cout + c];
+    a.gb[c] = s;
+  }
+}
+
+// ---- dense() ---------------------------------------------------------------------------------------------------------------------------
+
+// a thread per (row, channel); BACKWARD: the gather
+template <bool BACKWARD>
+__global__ __launch_bounds__(BLOCK) void dense_kernel(const float* __restrict__ src, const int32_t* __restrict__ coors, long long n, int C,
+                                                      const Geo g, float* __restrict__ dst) {
+  const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= n * C) return;
+  const long long i = t / C;
+  const int ch = (int)(t - i * C);
+  const int32_t* c = coors + i * 4;
+  const bool in = row_active(c, g);
+  const long long plane = (long long)g.n[0] * g.n[1] * g.n[2];
+  const long long at = in ? ((long long)c[0] * C + ch) * plane + ((long long)c[1] * g.n[1] + c[2]) * g.n[2] + c[3] : 0;
+  if (BACKWARD) dst[t] = in ? src[at] : 0.0f;
+  else if (in) dst[at] = src[t];
+}
+
+static int dense_geo(int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W, Geo* g) {
+  const int32_t shape[3] = {D, H, W}, one[3] = {1, 1, 1}, zero[3] = {0, 0, 0};
+  if (C < 1) return GD3D_E_BADARG;
+  if (C > MAX_C) return GD3D_E_TOOLARGE;
+  const int rc = make_geo(N, B, shape, one, one, zero, 0, g);
+  if (rc != 0) return rc;
+  if (g->in_sent > (1LL << 62) / C || N * C > (1LL << 40)) return GD3D_E_TOOLARGE;
+  return 0;
+}
+
+}  // namespace sparse_conv
+
+using namespace sparse_conv;
+
+extern "C" {
+
+size_t gd3d_sparse_conv_index_workspace_bytes(int64_t N, int32_t K, int32_t subm) {
+  if (N <= 0 || K < 1 || K > MAX_K || N * K > 0x7fffffffLL) return 256;
+  Layout L;
+  if (layout(N, N * K, subm != 0, L) != hipSuccess) return 0;
+  return L.total;
+}
+
+int gd3d_sparse_conv_index(const int32_t* coors, int64_t N, int32_t B, const int32_t* spatial_shape, const int32_t* kernel_size,
+                           const int32_t* stride, const int32_t* padding, int32_t subm, int64_t max_out, void* workspace,
+                           int32_t* out_coors, int32_t* nbr, int32_t* nbr_t, int64_t* num, int32_t* out_batch_cnt, void* stream) {
+  Geo g;
+  const int rc = make_geo(N, B, spatial_shape, kernel_size, stride, padding, subm, &g);
+  if (rc != 0) return rc;
+  if (num == nullptr || (B > 0 && out_batch_cnt == nullptr) || max_out < 0) return GD3D_E_BADARG;
+  const int64_t R = subm ? N : max_out;
+  if (R > 0x7fffffffLL || R * g.K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  hipStream_t s = (hipStream_t)stream;
+  int e = 0;
+  if (R > 0) {
+    if (out_coors == nullptr || nbr == nullptr) return GD3D_E_BADARG;
+  }
+  if (N == 0) {                                                  // no input row: the counts are zeros, every output row a tail row
+    e = gd3d::fill_words(num, 2 * sizeof(int64_t), 0u, s);
+    if (e == 0 && B > 0) e = gd3d::fill_words(out_batch_cnt, sizeof(int32_t) * (size_t)B, 0u, s);
+    if (e == 0 && R > 0) e = gd3d::fill_words(out_coors, sizeof(int32_t) * 4 * (size_t)R, 0xffffffffu, s);
+    if (e == 0 && R > 0) e = gd3d::fill_words(nbr, sizeof(int32_t) * (size_t)R * g.K, 0xffffffffu, s);
+    return e;
+  }
+  if (coors == nullptr || workspace == nullptr || ((uintptr_t)workspace & 255) != 0) return GD3D_E_BADARG;
+  if (!subm && nbr_t == nullptr) return GD3D_E_BADARG;
+  const long long M = (long long)N * g.K;
+  Layout L;
+  hipError_t he = layout(N, M, subm != 0, L);
+  if (he != hipSuccess) return (int)he;
+  char* w = (char*)workspace;
+  long long* key_in = (long long*)(w + L.key_in);
+  long long* skey = (long long*)(w + L.skey);
+  int* val_in = (int*)(w + L.val_in);
+  int* srow = (int*)(w + L.srow);
+  hipLaunchKernelGGL(key_kernel, dim3(blocks_of(N)), dim3(BLOCK), 0, s, coors, (long long)N, g, key_in, val_in);
+  size_t sb = L.sort_bytes;
+  he = rocprim::radix_sort_pairs((void*)(w + L.sort_tmp), sb, (const long long*)key_in, skey, (const int*)val_in, srow, (size_t)N, 0,
+                                 (unsigned)key_bits(g.in_sent), s);
+  if (he != hipSuccess) return (int)he;
+  if (subm) {
+    hipLaunchKernelGGL(subm_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, coors, (long long)N, g, (const long long*)skey,
+                       (const int*)srow, out_coors, nbr);
+    // the sorted keys below the sentinel are the active rows: a sample's count is a difference of two lower bounds
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(BLOCK), 0, s, (const long long*)skey, (long long)N, (const int*)nullptr,
+                       (const int*)nullptr, 0LL, 0LL, g.in_sent, (int)B, 1, (long long*)num, out_batch_cnt);
+    return (int)hipGetLastError();
+  }
+  long long* cand = (long long*)(w + L.cand);
+  long long* scand = (long long*)(w + L.scand);
+  int* flag = (int*)(w + L.flag);
+  int* pos = (int*)(w + L.pos);
+  hipLaunchKernelGGL(cand_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, coors, (long long)N, g, cand);
+  sb = L.sort_bytes;
+  he = rocprim::radix_sort_keys((void*)(w + L.sort_tmp), sb, (const long long*)cand, scand, (size_t)M, 0, (unsigned)key_bits(g.out_sent), s);
+  if (he != hipSuccess) return (int)he;
+  hipLaunchKernelGGL(head_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, (const long long*)scand, M, g.out_sent, flag);
+  sb = L.sort_bytes;
+  he = rocprim::exclusive_scan((void*)(w + L.sort_tmp), sb, (const int*)flag, pos, 0, (size_t)M, rocprim::plus<int>(), s);
+  if (he != hipSuccess) return (int)he;
+  long long* ukey = cand;                                        // the candidates are sorted out of this buffer: it is free again
+  hipLaunchKernelGGL(compact_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, (const long long*)scand, (const int*)flag, (const int*)pos, M, ukey);
+  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(BLOCK), 0, s, (const long long*)ukey, 0LL, (const int*)flag, (const int*)pos, M,
+                     (long long)max_out, g.out_sent, (int)B, 0, (long long*)num, out_batch_cnt);
+  if (R > 0)
+    hipLaunchKernelGGL(out_kernel, dim3(blocks_of(R * g.K)), dim3(BLOCK), 0, s, (const long long*)ukey, (const long long*)num, (long long)R,
+                       (long long)N, g, (const long long*)skey, (const int*)srow, out_coors, nbr);
+  hipLaunchKernelGGL(nbrt_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, coors, (long long)N, g, (const long long*)skey, (const int*)srow,
+                     (const long long*)ukey, (const long long*)num, nbr_t);
+  return (int)hipGetLastError();
+}
+
+int gd3d_sparse_conv_forward(const float* features, const float* weight, const float* bias, const int32_t* nbr, const int64_t* num,
+                             int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, float* out, void* stream) {
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (N < 0 || R < 0) return GD3D_E_BADARG;
+  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  if (R == 0) return 0;
+  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
+  GemmArgs a;
+  a.src = features; a.W = weight; a.bias = bias; a.table = nbr; a.num = (const long long*)num; a.n_src = N; a.rows = R;
+  a.K = K; a.Cr = Cin; a.Co = Cout; a.flip = 0; a.out = out;
+  return launch_gemm(a, false, (hipStream_t)stream);
+}
+
+int gd3d_sparse_conv_backward_input(const float* grad_out, const float* weight, const int32_t* table, int32_t flip, int64_t N,
+                                    int64_t R, int32_t K, int32_t Cin, int32_t Cout, float* grad_features, void* stream) {
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (N < 0 || R < 0 || (flip && N != R)) return GD3D_E_BADARG;
+  if (N > 0x7fffffffLL || R > 0x7fffffffLL || N * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  if (N == 0) return 0;
+  if (weight == nullptr || table == nullptr || grad_features == nullptr || (R > 0 && grad_out == nullptr)) return GD3D_E_BADARG;
+  GemmArgs a;
+  a.src = grad_out; a.W = weight; a.bias = nullptr; a.table = table; a.num = nullptr; a.n_src = R; a.rows = N;
+  a.K = K; a.Cr = Cout; a.Co = Cin; a.flip = flip ? 1 : 0; a.out = grad_features;
+  return launch_gemm(a, true, (hipStream_t)stream);
+}
+
+size_t gd3d_sparse_conv_backward_weight_workspace_bytes(int64_t R, int32_t K, int32_t Cin, int32_t Cout) {
+  if (R <= 0 || check_channels(K, Cin, Cout) != 0) return 256;
+  int64_t parts, chunk;
+  weight_parts(R, (int64_t)K * Cin * Cout, &parts, &chunk);
+  return up256(sizeof(float) * (size_t)parts * (size_t)K * Cin * Cout) + up256(sizeof(float) * (size_t)parts * Cout);
+}
+
+int gd3d_sparse_conv_backward_weight(const float* features, const float* grad_out, const int32_t* nbr, const int64_t* num, int64_t N,
+                                     int64_t R, int32_t K, int32_t Cin, int32_t Cout, void* workspace, float* grad_weight,
+                                     float* grad_bias, void* stream) {
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (N < 0 || R < 0 || grad_weight == nullptr) return GD3D_E_BADARG;
+  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t kcc = (int64_t)K * Cin * Cout;
+  if (R == 0 || N == 0) {                                        // no pair: the gradients are zeros
+    int e = gd3d::fill_words(grad_weight, sizeof(float) * (size_t)kcc, 0u, s);
+    if (e == 0 && grad_bias != nullptr) e = gd3d::fill_words(grad_bias, sizeof(float) * (size_t)Cout, 0u, s);
+    return e;
+  }
+  if (features == nullptr || grad_out == nullptr || nbr == nullptr || workspace == nullptr || ((uintptr_t)workspace & 255) != 0)
+    return GD3D_E_BADARG;
+  WgradArgs a;
+  a.X = features; a.gY = grad_out; a.nbr = nbr; a.num = (const long long*)num; a.n_src = N; a.rows = R;
+  weight_parts(R, kcc, (int64_t*)&a.parts, (int64_t*)&a.chunk);
+  a.K = K; a.Cin = Cin; a.Cout = Cout; a.tiles_co = 1;
+  a.part_w = (float*)workspace;
+  a.part_b = (float*)((char*)workspace + up256(sizeof(float) * (size_t)a.parts * (size_t)kcc));
+  a.gW = grad_weight; a.gb = grad_bias;
+  launch_wgrad(a, s);
+  if (grad_bias != nullptr) {
+    int cp = 1;
+    while (cp < Cout) cp <<= 1;                                  // <= 256 = BLOCK
+    hipLaunchKernelGGL(bias_kernel, dim3((unsigned)a.parts), dim3(BLOCK), 0, s, a, cp);
+  }
+  hipLaunchKernelGGL(wfinish_kernel, dim3(blocks_of(kcc + Cout)), dim3(BLOCK), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+int gd3d_sparse_to_dense(const float* features, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W,
+                         float* dense, void* stream) {
+  Geo g;
+  const int rc = dense_geo(N, C, B, D, H, W, &g);
+  if (rc != 0) return rc;
+  if (B == 0) return 0;
+  if (dense == nullptr) return GD3D_E_BADARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int e = gd3d::fill_words(dense, sizeof(float) * (size_t)g.in_sent * (size_t)C, 0u, s);
+  if (e != 0 || N == 0) return e;
+  if (features == nullptr || coors == nullptr) return GD3D_E_BADARG;
+  hipLaunchKernelGGL(dense_kernel<false>, dim3(blocks_of(N * C)), dim3(BLOCK), 0, s, features, coors, (long long)N, (int)C, g, dense);
+  return (int)hipGetLastError();
+}
+
+int gd3d_sparse_to_dense_backward(const float* grad_dense, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H,
+                                  int32_t W, float* grad_features, void* stream) {
+  Geo g;
+  const int rc = dense_geo(N, C, B, D, H, W, &g);
+  if (rc != 0) return rc;
+  if (N == 0) return 0;
+  if (coors == nullptr || grad_features == nullptr || (B > 0 && grad_dense == nullptr)) return GD3D_E_BADARG;
+  hipLaunchKernelGGL(dense_kernel<true>, dim3(blocks_of(N * C)), dim3(BLOCK), 0, (hipStream_t)stream, grad_dense, coors, (long long)N,
+                     (int)C, g, grad_features);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

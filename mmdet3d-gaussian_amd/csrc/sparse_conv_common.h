@@ -1,0 +1,136 @@
+// sparse_conv_common.h — the integer rules of the sparse 3D convolution (include/gd3d.h, gd3d_sparse_conv_*),
+// shared by csrc/sparse_conv.hip and csrc/sparse_conv_cpu.cpp: which rows are active, the 64-bit keys, the offsets, the per-axis range
+// checks made BEFORE anything is linearised, and the look-up in a sorted key list.  Integers only: both targets give the same tables.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/gd3d.h"
+
+#if defined(__HIPCC__)
+#define SC_HD __host__ __device__ __forceinline__
+#else
+#define SC_HD inline
+#endif
+
+namespace sparse_conv {
+
+constexpr int MAX_K = 27;     // offsets of one kernel
+constexpr int MAX_C = 256;    // channels, either side
+constexpr int TILE_M = 64;    // output rows of one workgroup of the forward / input-gradient kernel (tests name their row counts from it)
+constexpr int TILE_N = 64;    // output channels of one workgroup
+constexpr int TILE_K = 32;    // reduction chunk staged in LDS
+constexpr int WG_ROWS = 32;   // rows of one staged step of the weight gradient
+constexpr int MAX_PARTS = 64; // row chunks (partial sums per offset) of the weight gradient
+
+struct Geo {
+  int32_t B, n[3], k[3], s[3], p[3], o[3], K, subm;
+  long long in_sent, out_sent;   // B * D * H * W and B * oD * oH * oW: above every valid key
+};
+
+// GD3D_E_* or 0.  shape, kernel, stride, padding: 3 host values each, (z, y, x).
+inline int make_geo(int64_t N, int32_t B, const int32_t* shape, const int32_t* kernel, const int32_t* stride, const int32_t* padding,
+                    int32_t subm, Geo* g) {
+  if (N < 0 || B < 0 || shape == nullptr || kernel == nullptr || stride == nullptr || padding == nullptr) return GD3D_E_BADARG;
+  long long K = 1, cells = B > 0 ? B : 1, ocells = B > 0 ? B : 1;
+  for (int a = 0; a < 3; ++a) {
+    g->n[a] = shape[a]; g->k[a] = kernel[a]; g->s[a] = stride[a]; g->p[a] = padding[a];
+    if (shape[a] < 1 || kernel[a] < 1 || stride[a] < 1 || padding[a] < 0) return GD3D_E_BADARG;
+    if (shape[a] > (1 << 24) || kernel[a] > MAX_K || padding[a] > (1 << 24) || stride[a] > (1 << 24)) return GD3D_E_TOOLARGE;
+    if (subm && (kernel[a] % 2 == 0 || stride[a] != 1 || padding[a] != kernel[a] / 2)) return GD3D_E_BADARG;
+    const long long span = (long long)shape[a] + 2LL * padding[a] - kernel[a];
+    g->o[a] = span < 0 ? 0 : (int32_t)(span / stride[a] + 1);              // the kernel does not fit: no output cell, every count zero
+    K *= kernel[a];
+    if (K > MAX_K) return GD3D_E_TOOLARGE;
+    if (cells > (1LL << 62) / shape[a] || (g->o[a] > 0 && ocells > (1LL << 62) / g->o[a])) return GD3D_E_TOOLARGE;
+    cells *= shape[a];
+    ocells *= g->o[a];
+  }
+  if (N > 0x7fffffffLL || N * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  g->B = B; g->K = (int32_t)K; g->subm = subm ? 1 : 0;
+  g->in_sent = B > 0 ? cells : 0;
+  g->out_sent = B > 0 ? ocells : 0;
+  return 0;
+}
+
+SC_HD bool row_active(const int32_t* c, const Geo& g) {
+  return c[0] >= 0 && c[0] < g.B && c[1] >= 0 && c[1] < g.n[0] && c[2] >= 0 && c[2] < g.n[1] && c[3] >= 0 && c[3] < g.n[2];
+}
+
+SC_HD long long in_key(const Geo& g, int b, int z, int y, int x) {
+  return (((long long)b * g.n[0] + z) * g.n[1] + y) * g.n[2] + x;
+}
+
+SC_HD long long out_key(const Geo& g, int b, int z, int y, int x) {
+  return (((long long)b * g.o[0] + z) * g.o[1] + y) * g.o[2] + x;
+}
+
+SC_HD void split_offset(const Geo& g, int j, int* off) {   // j = (a * ky + b) * kx + c: kz slowest
+  off[2] = j % g.k[2];
+  const int ab = j / g.k[2];
+  off[1] = ab % g.k[1];
+  off[0] = ab / g.k[1];
+}
+
+// the input cell that output cell `o` reads through offset `off`; false when it leaves the grid on any axis
+SC_HD bool input_of(const Geo& g, const int* o, const int* off, int* in) {
+  bool ok = true;
+  for (int a = 0; a < 3; ++a) {
+    const long long v = (long long)o[a] * g.s[a] - g.p[a] + off[a];
+    ok = ok && v >= 0 && v < g.n[a];
+    in[a] = (int)v;
+  }
+  return ok;
+}
+
+// the output cell that reads input cell `in` through offset `off`; false when there is none (not on the stride, outside out_shape)
+SC_HD bool output_of(const Geo& g, const int* in, const int* off, int* o) {
+  bool ok = true;
+  for (int a = 0; a < 3; ++a) {
+    const long long v = (long long)in[a] + g.p[a] - off[a];
+    ok = ok && v >= 0 && v % g.s[a] == 0 && v / g.s[a] < g.o[a];
+    o[a] = (int)(v / g.s[a]);
+  }
+  return ok;
+}
+
+// first position of `keys` (ascending, n entries) that is not below `key`
+SC_HD long long lower_bound(const long long* keys, long long n, long long key) {
+  long long lo = 0, hi = n;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (keys[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// the (lowest) input row at a key, or -1
+SC_HD int32_t find_row(const long long* skey, const int32_t* srow, long long n, long long key) {
+  const long long at = lower_bound(skey, n, key);
+  return at < n && skey[at] == key ? srow[at] : -1;
+}
+
+SC_HD void decode_out(const Geo& g, long long key, int32_t* c) {   // -> [b, z, y, x]
+  c[3] = (int32_t)(key % g.o[2]); key /= g.o[2];
+  c[2] = (int32_t)(key % g.o[1]); key /= g.o[1];
+  c[1] = (int32_t)(key % g.o[0]);
+  c[0] = (int32_t)(key / g.o[0]);
+}
+
+// how the weight gradient cuts R rows: `parts` chunks of `chunk` rows (a multiple of WG_ROWS), the partials held to 64 MiB
+inline void weight_parts(int64_t R, int64_t kcc, int64_t* parts, int64_t* chunk) {
+  int64_t cap = ((int64_t)64 << 20) / (kcc * 4);
+  cap = cap < 1 ? 1 : (cap > MAX_PARTS ? MAX_PARTS : cap);
+  int64_t c = (R + cap - 1) / cap;
+  c = (c + WG_ROWS - 1) / WG_ROWS * WG_ROWS;
+  if (c < WG_ROWS) c = WG_ROWS;
+  *chunk = c;
+  *parts = R > 0 ? (R + c - 1) / c : 0;
+}
+
+inline int check_channels(int32_t K, int32_t Cin, int32_t Cout) {
+  if (K < 1 || Cin < 1 || Cout < 1) return GD3D_E_BADARG;
+  if (K > MAX_K || Cin > MAX_C || Cout > MAX_C) return GD3D_E_TOOLARGE;
+  return 0;
+}
+
+}  // namespace sparse_conv

@@ -1,0 +1,512 @@
+"""Sparse 3D convolution: spconv 1.x's `SubMConv3d` / `SparseConv3d` / `SparseConvTensor` / `SparseSequential` as mmdet3d re-exports them
+(`mmdet3d.ops.spconv`), mmdet3d's `SparseBasicBlock`, `make_sparse_convmodule` and `SparseEncoder`, and the reference's
+`MlvlSparseEncoder` (models/middle_encoders/mlvl_sparse_encoder.py:11-32): PV-RCNN's `voxel_middle_encoder` and CenterPoint's
+`pts_middle_encoder`.  mmdet3d and spconv are CUDA-only and absent from the reference tree: the op is RESTATED (include/gd3d.h,
+DESIGN.md §3.18) — a sparse convolution equals the dense `conv3d` of the densified input read at the active output sites.
+
+Three calls carry it (csrc/sparse_conv.hip): `sparse_conv_index` builds the neighbour tables of one layer geometry in one stream-ordered
+run of launches (64-bit keys, a stable radix sort, look-ups by lower bound; the outputs of a strided layer in ascending (b, z, y, x)
+order, as spconv 1.x's GPU path gives them), `sparse_conv` evaluates a layer over a table (one launch forward; one for the input
+gradient; three for the weight and bias gradients; no atomics, the bits replay), `sparse_to_dense` is `SparseConvTensor.dense()`.  CUDA
+tensors go to the kernels on the current stream, CPU tensors to the library's `_cpu` twins.  fp32: another dtype is evaluated in fp32 and
+cast back.  Dilation must be 1.
+"""
+import ctypes
+import math
+from collections import OrderedDict
+from typing import NamedTuple, Optional
+
+import torch
+from torch import nn
+
+from . import _host, _lib
+
+MAX_CHANNELS = 256
+MAX_OFFSETS = 27
+
+
+class SparseConvIndex(NamedTuple):
+    """The tables of one layer geometry over one set of input rows (include/gd3d.h, gd3d_sparse_conv_index)."""
+    out_coors: torch.Tensor              # (R, 4) int32 [b, z, y, x]; -1 rows past num[0]
+    out_shape: tuple                     # (oD, oH, oW)
+    nbr: torch.Tensor                    # (R, K) int32: the input row output row o reads through offset j, or -1
+    nbr_t: Optional[torch.Tensor]        # (N, K) int32: the output row that reads input row i through offset j, or -1; None for subm
+    num: torch.Tensor                    # (2,) int64 on the device: rows kept, true count
+    out_batch_cnt: torch.Tensor          # (B,) int32: kept rows per sample
+    subm: bool = False
+    num_in: int = 0                      # N, the input rows the tables were built over
+
+
+def _triple(v, name):
+    if isinstance(v, (list, tuple)):
+        v = tuple(int(x) for x in v)
+        if len(v) != 3:
+            raise RuntimeError(f'{name} must be a number or hold 3 values (z, y, x), got {len(v)}')
+        return v
+    return (int(v),) * 3
+
+
+def _geometry(spatial_shape, kernel_size, stride, padding, subm, who):
+    """(shape, kernel, stride, padding, out_shape) as int triples, validated as the C entry point validates them"""
+    n, k, s, p = _triple(spatial_shape, 'spatial_shape'), _triple(kernel_size, 'kernel_size'), _triple(stride, 'stride'), _triple(padding, 'padding')
+    if min(n) < 1 or min(k) < 1 or min(s) < 1 or min(p) < 0:
+        raise RuntimeError(f'{who}: spatial_shape {n}, kernel_size {k} and stride {s} must be positive, padding {p} not negative')
+    if k[0] * k[1] * k[2] > MAX_OFFSETS:
+        raise RuntimeError(f'{who}: kernel_size {k} has more than {MAX_OFFSETS} offsets')
+    if subm and any(ka % 2 == 0 or sa != 1 or pa != ka // 2 for ka, sa, pa in zip(k, s, p)):
+        raise RuntimeError(f'{who}: a submanifold convolution needs odd kernel extents, stride 1 and padding k // 2, got kernel_size {k}, '
+                           f'stride {s}, padding {p}')
+    o = tuple(max(0, (na + 2 * pa - ka) // sa + 1) for na, ka, sa, pa in zip(n, k, s, p))     # 0: the kernel does not fit, no output
+    return n, k, s, p, o
+
+
+_index_workspace_bytes = _host.memo(lambda n, k, subm: _lib.load().gd3d_sparse_conv_index_workspace_bytes(n, k, subm))
+_weight_workspace_bytes = _host.memo(lambda r, k, cin, cout: _lib.load().gd3d_sparse_conv_backward_weight_workspace_bytes(r, k, cin, cout))
+
+
+def _workspace(nbytes, dev):
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev) if dev.type == 'cuda' else None
+
+
+def _coors_i32(coors, who):
+    if not isinstance(coors, torch.Tensor) or coors.dim() != 2 or coors.size(1) != 4:
+        raise RuntimeError(f'shape mismatch: {who}: coors must be an (N, 4) tensor [b, z, y, x], got {tuple(getattr(coors, "shape", ()))}')
+    if coors.dtype.is_floating_point or coors.dtype == torch.bool:
+        raise RuntimeError(f'{who}: coors must be an integer tensor, got {coors.dtype}')
+    c = coors if coors.dtype == torch.int32 else coors.to(torch.int32)
+    return c if c.is_contiguous() else c.contiguous()
+
+
+def sparse_conv_index(coors, spatial_shape, batch_size, kernel_size, stride=1, padding=0, subm=False, max_out=None, dilation=1):
+    """The neighbour tables of one layer -> `SparseConvIndex(out_coors, out_shape, nbr, nbr_t, num, out_batch_cnt)`.
+
+    coors (N, 4) integer rows [b, z, y, x]; a row with a negative entry, b >= batch_size or a coordinate outside `spatial_shape` is
+    inactive (the tail rows of `hard_voxelize(static=True)`): no output, nobody's neighbour.  Active rows must be unique.
+    subm=True  : odd kernel, stride 1, padding k // 2 (anything else raises); the outputs are the inputs, R = N, no read-back.
+    subm=False : out_shape = (n + 2p - k) // s + 1 (0 on an axis the kernel does not fit: no output); the active outputs in ascending (b, z, y, x) order.  max_out=None reads the count
+                 back ONCE and returns exact-size views; an int gives the static, capturable form: R = max_out rows, the lowest keys
+                 kept, the rows past num[0] holding -1, and nothing read back.
+    Every output is an integer and replays bit for bit on the device, in the `_cpu` twin and in the numpy restatement of the tests."""
+    if _triple(dilation, 'dilation') != (1, 1, 1):
+        raise RuntimeError(f'sparse_conv_index: dilation must be 1, got {dilation}')
+    subm = bool(subm)
+    n, k, s, p, o = _geometry(spatial_shape, kernel_size, stride, padding, subm, 'sparse_conv_index')
+    c = _coors_i32(coors, 'sparse_conv_index')
+    B, N, K, dev = int(batch_size), c.size(0), k[0] * k[1] * k[2], c.device
+    if B < 0:
+        raise RuntimeError(f'sparse_conv_index: batch_size must not be negative, got {B}')
+    if subm:
+        R = N
+    elif max_out is None:
+        # what N rows can reach: every row feeds at most prod(ceil(k / s)) output cells
+        R = min(N * math.prod(-(-ka // sa) for ka, sa in zip(k, s)), B * o[0] * o[1] * o[2])
+    else:
+        R = int(max_out)
+        if R < 0:
+            raise RuntimeError(f'sparse_conv_index: max_out must not be negative, got {R}')
+    out_coors = torch.empty((R, 4), dtype=torch.int32, device=dev)
+    nbr = torch.empty((R, K), dtype=torch.int32, device=dev)
+    nbr_t = None if subm else torch.empty((N, K), dtype=torch.int32, device=dev)
+    num = torch.empty((2,), dtype=torch.int64, device=dev)
+    cnt = torch.empty((B,), dtype=torch.int32, device=dev)
+    work = _workspace(_index_workspace_bytes(N, K, int(subm)), dev)
+    i3 = ctypes.c_int32 * 3
+    ptr = _host.ptr_or_null
+    _host.call('gd3d_sparse_conv_index', dev,
+               (ptr(c), N, B, i3(*n), i3(*k), i3(*s), i3(*p), int(subm), R, ptr(work), ptr(out_coors), ptr(nbr), ptr(nbr_t), num.data_ptr(),
+                ptr(cnt)))
+    if not subm and max_out is None:
+        kept = int(num[0])                                                           # the one read-back
+        out_coors, nbr = out_coors[:kept], nbr[:kept]
+    return SparseConvIndex(out_coors, o, nbr, nbr_t, num, cnt, subm, N)
+
+
+def _weight3(weight, who):
+    if not isinstance(weight, torch.Tensor) or weight.dim() not in (3, 5) or not weight.dtype.is_floating_point:
+        raise RuntimeError(f'shape mismatch: {who}: weight must be a floating-point (K, Cin, Cout) or (kz, ky, kx, Cin, Cout) tensor, got '
+                           f'{tuple(getattr(weight, "shape", ()))}')
+    return weight.reshape(-1, weight.size(-2), weight.size(-1))
+
+
+class _SparseConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, weight, bias, nbr, nbr_t, num, subm):
+        x, w = _host.f32c(features), _host.f32c(weight)
+        b = None if bias is None else _host.f32c(bias)
+        N, (K, Cin, Cout), R, dev = x.size(0), w.shape, nbr.size(0), x.device
+        out = torch.empty((R, Cout), dtype=torch.float32, device=dev)
+        ptr = _host.ptr_or_null
+        _host.call('gd3d_sparse_conv_forward', dev, (ptr(x), ptr(w), ptr(b), ptr(nbr), ptr(num), N, R, K, Cin, Cout, ptr(out)))
+        ctx.save_for_backward(x, w, nbr, nbr_t, num)
+        ctx.state = (subm, bias is not None, features.dtype, weight.dtype, None if bias is None else bias.dtype, weight.shape)
+        return out if features.dtype == torch.float32 else out.to(features.dtype)
+
+    @staticmethod
+    @_host.guard_double_backward
+    def backward(ctx, grad_out):
+        x, w, nbr, nbr_t, num = ctx.saved_tensors
+        subm, has_bias, x_dtype, w_dtype, b_dtype, w_shape = ctx.state
+        gy = _host.f32c(grad_out)
+        N, (K, Cin, Cout), R, dev = x.size(0), w.shape, nbr.size(0), x.device
+        ptr = _host.ptr_or_null
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty((N, Cin), dtype=torch.float32, device=dev)
+            _host.call('gd3d_sparse_conv_backward_input', dev,
+                       (ptr(gy), ptr(w), ptr(nbr if subm else nbr_t), int(subm), N, R, K, Cin, Cout, ptr(gx)))
+            gx = gx.to(x_dtype)
+        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
+            gw = torch.empty((K, Cin, Cout), dtype=torch.float32, device=dev)
+            gb = torch.empty((Cout,), dtype=torch.float32, device=dev) if has_bias else None
+            work = _workspace(_weight_workspace_bytes(R, K, Cin, Cout), dev)
+            _host.call('gd3d_sparse_conv_backward_weight', dev,
+                       (ptr(x), ptr(gy), ptr(nbr), ptr(num), N, R, K, Cin, Cout, ptr(work), ptr(gw), ptr(gb)))
+            gw = gw.to(w_dtype).reshape(w_shape)
+            gb = gb.to(b_dtype) if has_bias else None
+        return gx, gw, gb, None, None, None, None
+
+
+def sparse_conv(features, weight, bias, index):
+    """One sparse convolution layer over the tables of `sparse_conv_index` -> (R, Cout), differentiable w.r.t. features, weight, bias.
+
+    out[o] = sum over the offsets j with index.nbr[o, j] >= 0 of features[nbr[o, j]] @ weight[j] (+ bias); weight is spconv 1.x's
+    (kz, ky, kx, Cin, Cout) or the flat (K, Cin, Cout).  A row without a valid neighbour — an inactive row of a submanifold layer, a tail row
+    of the static form — is zero, bias or not, and takes no part in any gradient.  Forward: one launch; input gradient: one (the same
+    kernel over the transposed table and weight); weight and bias gradients: per-chunk partial sums and one finishing launch.  No atomics
+    anywhere: the same bits from run to run."""
+    if not isinstance(index, SparseConvIndex):
+        raise RuntimeError('sparse_conv: index must be the record sparse_conv_index returns')
+    w = _weight3(weight, 'sparse_conv')
+    K, Cin, Cout = w.shape
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.size(1) != Cin or not features.dtype.is_floating_point:
+        raise RuntimeError(f'shape mismatch: sparse_conv: features must be a floating-point (N, {Cin}) tensor, got {tuple(getattr(features, "shape", ()))}')
+    if features.size(0) != index.num_in or index.nbr.size(1) != K:
+        raise RuntimeError(f'shape mismatch: sparse_conv: the index was built over {index.num_in} rows and {index.nbr.size(1)} offsets, got '
+                           f'{features.size(0)} rows and a weight of {K} offsets')
+    if max(Cin, Cout) > MAX_CHANNELS or min(Cin, Cout) < 1:
+        raise RuntimeError(f'sparse_conv: 1 .. {MAX_CHANNELS} channels are supported, got {Cin} -> {Cout}')
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.shape != (Cout,)):
+        raise RuntimeError(f'shape mismatch: sparse_conv: bias must be ({Cout},), got {tuple(getattr(bias, "shape", ()))}')
+    for name, t in (('weight', weight), ('bias', bias), ('index', index.nbr)):
+        if t is not None and t.device != features.device:
+            raise RuntimeError(f'sparse_conv: {name} is on {t.device}, features on {features.device}')
+    return _SparseConv.apply(features, w, bias, index.nbr, index.nbr_t, index.num, index.subm)
+
+
+class _SparseToDense(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, coors, shape, B):
+        x = _host.f32c(features)
+        N, C, dev = x.size(0), x.size(1), x.device
+        dense = torch.empty((B, C) + shape, dtype=torch.float32, device=dev)
+        ptr = _host.ptr_or_null
+        _host.call('gd3d_sparse_to_dense', dev, (ptr(x), ptr(coors), N, C, B, *shape, ptr(dense)))
+        ctx.save_for_backward(coors)
+        ctx.state = (shape, B, N, C, features.dtype)
+        return dense if features.dtype == torch.float32 else dense.to(features.dtype)
+
+    @staticmethod
+    @_host.guard_double_backward
+    def backward(ctx, grad_dense):
+        (coors,) = ctx.saved_tensors
+        shape, B, N, C, dtype = ctx.state
+        g = _host.f32c(grad_dense)
+        gx = torch.empty((N, C), dtype=torch.float32, device=g.device)
+        ptr = _host.ptr_or_null
+        _host.call('gd3d_sparse_to_dense_backward', g.device, (ptr(g), ptr(coors), N, C, B, *shape, ptr(gx)))
+        return gx.to(dtype), None, None, None
+
+
+def sparse_to_dense(features, coors, spatial_shape, batch_size):
+    """`SparseConvTensor.dense()` -> (B, C, D, H, W): zeros, then dense[b, :, z, y, x] = features[row] for every active row of coors
+    (N, 4) [b, z, y, x]; a fill and one launch.  Differentiable w.r.t. features: the backward is one gather, zeros for an inactive row."""
+    shape = _triple(spatial_shape, 'spatial_shape')
+    c = _coors_i32(coors, 'sparse_to_dense')
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.size(0) != c.size(0) or not features.dtype.is_floating_point:
+        raise RuntimeError(f'shape mismatch: sparse_to_dense: features must be a floating-point ({c.size(0)}, C) tensor, got '
+                           f'{tuple(getattr(features, "shape", ()))}')
+    B = int(batch_size)
+    if min(shape) == 0 and B >= 0:                                                     # the shape of a layer without output cells
+        return features.new_zeros((B, features.size(1)) + shape)
+    if B < 0 or min(shape) < 1 or not 1 <= features.size(1) <= MAX_CHANNELS:
+        raise RuntimeError(f'sparse_to_dense: needs batch_size >= 0, a positive spatial_shape and 1 .. {MAX_CHANNELS} channels, got {B}, {shape}, '
+                           f'{features.size(1)}')
+    if c.device != features.device:
+        raise RuntimeError(f'sparse_to_dense: coors is on {c.device}, features on {features.device}')
+    return _SparseToDense.apply(features, c, shape, B)
+
+
+# ---- spconv 1.x's surface ------------------------------------------------------------------------------------------------------------
+
+class SparseConvTensor:
+    """spconv 1.x's tensor: features (N, C), indices (N, 4) int32 [b, z, y, x], spatial_shape (D, H, W), batch_size, and `indice_dict`
+    — the indices built so far, by `indice_key`, shared along a tensor's lineage."""
+
+    def __init__(self, features, indices, spatial_shape, batch_size, grid=None):
+        self.features = features
+        self.indices = indices
+        self.spatial_shape = list(spatial_shape)
+        self.batch_size = batch_size
+        self.indice_dict = {}
+        self.grid = grid
+
+    @property
+    def spatial_size(self):
+        return math.prod(self.spatial_shape)
+
+    def find_indice_pair(self, key):
+        return None if key is None else self.indice_dict.get(key)
+
+    def dense(self, channels_first=True):
+        out = sparse_to_dense(self.features, self.indices, self.spatial_shape, self.batch_size)
+        return out if channels_first else out.permute(0, 2, 3, 4, 1).contiguous()
+
+    @property
+    def sparity(self):
+        return self.indices.shape[0] / max(1, self.spatial_size * self.batch_size)
+
+
+class SparseModule(nn.Module):
+    """Marks the modules that take and return a `SparseConvTensor` (everything else `SparseSequential` applies to `.features`)."""
+
+
+class SparseConvolution(SparseModule):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, subm=False, indice_key=None,
+                 max_out=None):
+        super().__init__()
+        if _triple(dilation, 'dilation') != (1, 1, 1):
+            raise RuntimeError(f'{type(self).__name__}: dilation must be 1, got {dilation}')
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        self.kernel_size = _triple(kernel_size, 'kernel_size')
+        self.subm = bool(subm)
+        # a submanifold layer pads by k // 2 whatever it is handed, as spconv does
+        self.stride = (1, 1, 1) if self.subm else _triple(stride, 'stride')
+        self.padding = tuple(k // 2 for k in self.kernel_size) if self.subm else _triple(padding, 'padding')
+        self.dilation = (1, 1, 1)
+        self.indice_key = indice_key
+        self.max_out = max_out
+        if not 1 <= self.in_channels <= MAX_CHANNELS or not 1 <= self.out_channels <= MAX_CHANNELS:
+            raise RuntimeError(f'{type(self).__name__}: 1 .. {MAX_CHANNELS} channels are supported, got {in_channels} -> {out_channels}')
+        if math.prod(self.kernel_size) > MAX_OFFSETS or min(self.kernel_size) < 1:
+            raise RuntimeError(f'{type(self).__name__}: kernel_size {self.kernel_size} must hold 1 .. {MAX_OFFSETS} offsets')
+        if self.subm and any(k % 2 == 0 for k in self.kernel_size):
+            raise RuntimeError(f'{type(self).__name__}: a submanifold convolution needs odd kernel extents, got {self.kernel_size}')
+        self.weight = nn.Parameter(torch.empty(*self.kernel_size, self.in_channels, self.out_channels))
+        self.bias = nn.Parameter(torch.empty(self.out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(math.prod(self.kernel_size) * self.in_channels)   # kaiming_uniform_(a=sqrt(5)) over fan_in = K * Cin
+        nn.init.uniform_(self.weight, -bound, bound)
+        if self.bias is not None:
+            nn.init.uniform_(self.bias, -bound, bound)
+
+    def build_index(self, x):
+        return sparse_conv_index(x.indices, x.spatial_shape, x.batch_size, self.kernel_size, self.stride, self.padding, self.subm, self.max_out)
+
+    def forward(self, x):
+        if not isinstance(x, SparseConvTensor):
+            raise RuntimeError(f'{type(self).__name__} takes a SparseConvTensor, got {type(x).__name__}')
+        index = x.find_indice_pair(self.indice_key)
+        if index is not None and (index.num_in != x.features.size(0) or index.subm != self.subm or index.nbr.size(1) != math.prod(self.kernel_size)):
+            raise RuntimeError(f'{type(self).__name__}: the index stored under indice_key {self.indice_key!r} was built for another layer '
+                               'geometry or another set of rows')
+        if index is None:
+            index = self.build_index(x)
+            if self.indice_key is not None:
+                x.indice_dict[self.indice_key] = index
+        out = SparseConvTensor(sparse_conv(x.features, self.weight, self.bias, index), x.indices if self.subm else index.out_coors,
+                               index.out_shape, x.batch_size, x.grid)
+        out.indice_dict = x.indice_dict
+        return out
+
+    def extra_repr(self):
+        return (f'{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, '
+                f'bias={self.bias is not None}, indice_key={self.indice_key!r}')
+
+
+class SubMConv3d(SparseConvolution):
+    """spconv 1.x's submanifold convolution: the outputs are the inputs.  `stride` and `padding` are accepted and not used (k // 2)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, indice_key=None):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, bias, True, indice_key)
+
+
+class SparseConv3d(SparseConvolution):
+    """spconv 1.x's regular sparse convolution.  max_out (an addition): an int gives the static form of `sparse_conv_index`."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, indice_key=None, max_out=None):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, bias, False, indice_key, max_out)
+
+
+class SparseSequential(SparseModule):
+    """spconv 1.x's container: sparse modules take the tensor, every other `nn.Module` (BatchNorm1d, ReLU) is applied to `.features`."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__()
+        if len(args) == 1 and isinstance(args[0], OrderedDict):
+            for key, module in args[0].items():
+                self.add_module(key, module)
+        else:
+            for idx, module in enumerate(args):
+                self.add_module(str(idx), module)
+        for name, module in kwargs.items():
+            if name in self._modules:
+                raise ValueError('name exists.')
+            self.add_module(name, module)
+
+    def __getitem__(self, idx):
+        if not -len(self) <= idx < len(self):
+            raise IndexError(f'index {idx} is out of range')
+        return list(self._modules.values())[idx]
+
+    def __len__(self):
+        return len(self._modules)
+
+    def add(self, module, name=None):
+        name = str(len(self._modules)) if name is None else name
+        if name in self._modules:
+            raise KeyError('name exists')
+        self.add_module(name, module)
+
+    def forward(self, input):
+        for module in self._modules.values():
+            if isinstance(module, SparseModule):
+                input = module(input)
+            elif isinstance(input, SparseConvTensor):
+                if input.indices.shape[0] != 0:
+                    input.features = module(input.features)
+            else:
+                input = module(input)
+        return input
+
+
+def _norm1d(norm_cfg, channels):
+    cfg = dict(norm_cfg or dict(type='BN1d'))
+    kind = cfg.pop('type', 'BN1d')
+    if kind not in ('BN1d', 'BN'):
+        raise RuntimeError(f'norm_cfg type {kind!r}: only BN1d is built here')
+    cfg.pop('requires_grad', None)
+    return nn.BatchNorm1d(channels, **cfg)
+
+
+class SparseBasicBlock(SparseModule):
+    """mmdet3d's sparse residual block: conv -> norm -> relu -> conv -> norm -> add identity -> relu, both SubMConv3d k3 without bias.
+    indice_key (an addition): one index for both layers; the result does not depend on it."""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None, conv_cfg=None, norm_cfg=None, indice_key=None):
+        super().__init__()
+        if conv_cfg is not None and conv_cfg.get('type', 'SubMConv3d') != 'SubMConv3d':
+            raise RuntimeError(f'SparseBasicBlock is built from SubMConv3d, got conv_cfg {conv_cfg}')
+        self.conv1 = SubMConv3d(inplanes, planes, 3, stride, padding=1, bias=False, indice_key=indice_key)
+        self.norm1 = _norm1d(norm_cfg, planes)
+        self.conv2 = SubMConv3d(planes, planes, 3, padding=1, bias=False, indice_key=indice_key)
+        self.norm2 = _norm1d(norm_cfg, planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = downsample
+
+    def forward(self, x):
+        identity = x.features
+        out = self.conv1(x)
+        out.features = self.relu(self.norm1(out.features))
+        out = self.conv2(out)
+        out.features = self.norm2(out.features)
+        if self.downsample is not None:
+            identity = self.downsample(x)
+        out.features = self.relu(out.features + identity)
+        return out
+
+
+def make_sparse_convmodule(in_channels, out_channels, kernel_size, indice_key, stride=1, padding=0, conv_type='SubMConv3d', norm_cfg=None,
+                           order=('conv', 'norm', 'act')):
+    """mmdet3d's sparse conv module: the layers of `order` — conv (no bias), BatchNorm1d(eps, momentum from norm_cfg), ReLU — in a
+    `SparseSequential`."""
+    if not isinstance(order, tuple) or len(order) > 3 or not set(order) <= {'conv', 'norm', 'act'}:
+        raise RuntimeError(f"make_sparse_convmodule: order must be a tuple over 'conv', 'norm', 'act', got {order!r}")
+    layers = []
+    for layer in order:
+        if layer == 'conv':
+            if conv_type == 'SubMConv3d':
+                layers.append(SubMConv3d(in_channels, out_channels, kernel_size, stride, padding, bias=False, indice_key=indice_key))
+            elif conv_type == 'SparseConv3d':
+                layers.append(SparseConv3d(in_channels, out_channels, kernel_size, stride, padding, bias=False, indice_key=indice_key))
+            else:
+                raise RuntimeError(f'make_sparse_convmodule: conv_type {conv_type!r} is not built here (SubMConv3d, SparseConv3d)')
+        elif layer == 'norm':
+            layers.append(_norm1d(norm_cfg, out_channels))
+        else:
+            layers.append(nn.ReLU(inplace=True))
+    return SparseSequential(*layers)
+
+
+class SparseEncoder(nn.Module):
+    """mmdet3d 0.x's `SparseEncoder`, restated from its published sparse_encoder.py (absent from the reference tree: not pinned):
+    CenterPoint's `pts_middle_encoder` (configs/_base_/models/centerpoint_01voxel_second_secfpn_nus.py:10-19).  forward returns
+    `spatial_features`: conv_out's dense() viewed as (B, C * D, H, W)."""
+
+    def __init__(self, in_channels, sparse_shape, order=('conv', 'norm', 'act'), norm_cfg=dict(type='BN1d', eps=1e-3, momentum=0.01),
+                 base_channels=16, output_channels=128, encoder_channels=((16,), (32, 32, 32), (64, 64, 64), (64, 64, 64)),
+                 encoder_paddings=((1,), (1, 1, 1), (1, 1, 1), ((0, 1, 1), 1, 1)), block_type='conv_module'):
+        super().__init__()
+        if block_type not in ('conv_module', 'basicblock'):
+            raise RuntimeError(f"block_type must be 'conv_module' or 'basicblock', got {block_type!r}")
+        if not isinstance(order, tuple) or len(order) != 3 or set(order) != {'conv', 'norm', 'act'}:
+            raise RuntimeError(f"order must be a permutation of ('conv', 'norm', 'act'), got {order!r}")
+        self.sparse_shape = list(sparse_shape)
+        self.in_channels, self.order, self.base_channels, self.output_channels = in_channels, order, base_channels, output_channels
+        self.encoder_channels, self.encoder_paddings = encoder_channels, encoder_paddings
+        self.stage_num = len(encoder_channels)
+        self.fp16_enabled = False
+        self.conv_input = make_sparse_convmodule(in_channels, base_channels, 3, norm_cfg=norm_cfg, padding=1, indice_key='subm1',
+                                                 conv_type='SubMConv3d', order=order if order[0] == 'conv' else ('conv',))
+        encoder_out_channels = self.make_encoder_layers(make_sparse_convmodule, norm_cfg, base_channels, block_type=block_type)
+        self.conv_out = make_sparse_convmodule(encoder_out_channels, output_channels, kernel_size=(3, 1, 1), stride=(2, 1, 1), norm_cfg=norm_cfg,
+                                               padding=0, indice_key='spconv_down2', conv_type='SparseConv3d')
+
+    def make_encoder_layers(self, make_block, norm_cfg, in_channels, block_type='conv_module', conv_cfg=dict(type='SubMConv3d')):
+        self.encoder_layers = SparseSequential()
+        out_channels = in_channels
+        for i, blocks in enumerate(self.encoder_channels):
+            blocks_list = []
+            for j, out_channels in enumerate(tuple(blocks)):
+                padding = tuple(self.encoder_paddings[i])[j]
+                if i != 0 and j == 0 and block_type == 'conv_module':     # every stage but the first starts with the strided layer
+                    blocks_list.append(make_block(in_channels, out_channels, 3, norm_cfg=norm_cfg, stride=2, padding=padding,
+                                                  indice_key=f'spconv{i + 1}', conv_type='SparseConv3d'))
+                elif block_type == 'basicblock':
+                    if j == len(blocks) - 1 and i != len(self.encoder_channels) - 1:
+                        blocks_list.append(make_block(in_channels, out_channels, 3, norm_cfg=norm_cfg, stride=2, padding=padding,
+                                                      indice_key=f'spconv{i + 1}', conv_type='SparseConv3d'))
+                    else:
+                        blocks_list.append(SparseBasicBlock(out_channels, out_channels, norm_cfg=norm_cfg, conv_cfg=conv_cfg,
+                                                            indice_key=f'subm{i + 1}'))
+                else:
+                    blocks_list.append(make_block(in_channels, out_channels, 3, norm_cfg=norm_cfg, padding=padding, indice_key=f'subm{i + 1}',
+                                                  conv_type='SubMConv3d'))
+                in_channels = out_channels
+            self.encoder_layers.add_module(f'encoder_layer{i + 1}', SparseSequential(*blocks_list))
+        return out_channels
+
+    def encode(self, voxel_features, coors, batch_size):
+        """-> (the stages' SparseConvTensors, conv_out's dense() viewed as (B, C * D, H, W))"""
+        x = self.conv_input(SparseConvTensor(voxel_features, coors.int(), self.sparse_shape, batch_size))
+        encode_features = []
+        for encoder_layer in self.encoder_layers:
+            x = encoder_layer(x)
+            encode_features.append(x)
+        spatial_features = self.conv_out(encode_features[-1]).dense()
+        N, C, D, H, W = spatial_features.shape
+        return encode_features, spatial_features.view(N, C * D, H, W)
+
+    def forward(self, voxel_features, coors, batch_size):
+        return self.encode(voxel_features, coors, batch_size)[1]
+
+
+class MlvlSparseEncoder(SparseEncoder):
+    """The reference's `MlvlSparseEncoder` (models/middle_encoders/mlvl_sparse_encoder.py:11-32), PV-RCNN's `voxel_middle_encoder`:
+    forward returns dict(encode_features = every stage's SparseConvTensor, spatial_features)."""
+
+    def forward(self, voxel_features, coors, batch_size):
+        encode_features, spatial_features = self.encode(voxel_features, coors, batch_size)
+        return dict(encode_features=encode_features, spatial_features=spatial_features)
