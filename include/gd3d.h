@@ -1335,6 +1335,56 @@ int gd3d_sparse_to_dense_cpu(const float* features, const int32_t* coors, int64_
 int gd3d_sparse_to_dense_backward_cpu(const float* grad_dense, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D,
                                       int32_t H, int32_t W, float* grad_features);
 
+/* ------------------------------------------------------------------------------------
+ * Sparse 3D convolution on fp16 / bf16 operands (an addition inside ABI 6; csrc/sparse_conv_16.hip): the entries
+ * above for half-precision training and inference, over the SAME tables of gd3d_sparse_conv_index.  dtype: GD3D_DTYPE_F16 (IEEE
+ * binary16) or GD3D_DTYPE_BF16; anything else is GD3D_E_BADARG.  Every 16-bit pointer must be 2-byte aligned (GD3D_E_BADARG).
+ * gd3d_sparse_conv_forward_16 : features (N, Cin), weight (K, Cin, Cout) and out (R, Cout) in `dtype`; bias (Cout) fp32, nullable.
+ *   out = rn16(sum + bias): the products of the 16-bit operands are accumulated in fp32 (v_mfma_f32_16x16x32_{f16,bf16} on the
+ *   device), the fp32 bias is added, and the result is rounded to nearest even ONCE.  The contract of gd3d_sparse_conv_forward:
+ *   EVERY row of out is written; a row without a valid neighbour and a row at or past num[0] (num nullable, device) is ZERO, bias
+ *   or not; an entry of nbr outside [0, N) counts as -1.  NaN and inf pass through; a sum beyond the type's range is inf, never
+ *   saturated.  One launch, a workgroup per 128 rows x 16, 32 or 64 channels, no atomics: the same bits from run to run.  Every
+ *   channel count 1..256 is accepted; Cin % 8 == 0 with a 16-byte aligned `features` takes 16-byte gathers, Cout % 8 == 0 with a
+ *   16-byte aligned `out` 16-byte stores, anything else the element-wise form of the same arithmetic.
+ * gd3d_sparse_conv_backward_input_16 : grad_out (R, Cout), weight and grad_features (N, Cin) in `dtype`; the forward kernel over the
+ *   transposed table and weight (table, flip as in gd3d_sparse_conv_backward_input); every row is written.
+ * gd3d_sparse_conv_backward_weight_16 : features and grad_out in `dtype`; grad_weight (K, Cin, Cout) and grad_bias (Cout, nullable)
+ *   are FP32 — master weights receive unrounded gradients.  The operands are widened (their products are exact in fp32) and summed
+ *   by gd3d_sparse_conv_backward_weight's two stages in its order; workspace:
+ *   gd3d_sparse_conv_backward_weight_workspace_bytes(R, K, Cin, Cout) bytes, 256-byte aligned.
+ * gd3d_sparse_to_dense_16 / _backward_16 : gd3d_sparse_to_dense and its backward for 2-byte elements of either type (a fill and a
+ *   copy: no dtype argument); dense (B, C, D, H, W) and grad_features (N, C) in the features' type.
+ * Limits, error codes and the empty cases (R == 0, N == 0) are those of the fp32 entries.
+ * `_cpu` twins (csrc/sparse_conv_16_cpu.cpp): the operands widened to fp32, the fp32 twin's loops, one rounding to nearest even;
+ *   another summation order than the device's: the values agree to the tests' bound, not to the bit.
+ * ---------------------------------------------------------------------------------- */
+#define GD3D_DTYPE_F16 1
+#define GD3D_DTYPE_BF16 2
+int gd3d_sparse_conv_forward_16(const void* features, const void* weight, const float* bias, const int32_t* nbr, const int64_t* num,
+                                int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* out, void* stream);
+int gd3d_sparse_conv_backward_input_16(const void* grad_out, const void* weight, const int32_t* table, int32_t flip, int64_t N,
+                                       int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* grad_features,
+                                       void* stream);
+int gd3d_sparse_conv_backward_weight_16(const void* features, const void* grad_out, const int32_t* nbr, const int64_t* num, int64_t N,
+                                        int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* workspace,
+                                        float* grad_weight, float* grad_bias, void* stream);
+int gd3d_sparse_to_dense_16(const void* features, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W,
+                            void* dense, void* stream);
+int gd3d_sparse_to_dense_backward_16(const void* grad_dense, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H,
+                                     int32_t W, void* grad_features, void* stream);
+int gd3d_sparse_conv_forward_16_cpu(const void* features, const void* weight, const float* bias, const int32_t* nbr, const int64_t* num,
+                                    int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* out);
+int gd3d_sparse_conv_backward_input_16_cpu(const void* grad_out, const void* weight, const int32_t* table, int32_t flip, int64_t N,
+                                           int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* grad_features);
+int gd3d_sparse_conv_backward_weight_16_cpu(const void* features, const void* grad_out, const int32_t* nbr, const int64_t* num,
+                                            int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* workspace,
+                                            float* grad_weight, float* grad_bias);
+int gd3d_sparse_to_dense_16_cpu(const void* features, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H,
+                                int32_t W, void* dense);
+int gd3d_sparse_to_dense_backward_16_cpu(const void* grad_dense, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D,
+                                         int32_t H, int32_t W, void* grad_features);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

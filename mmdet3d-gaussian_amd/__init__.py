@@ -35,7 +35,9 @@
   * ``sparse_conv_index`` / ``sparse_conv`` / ``sparse_to_dense`` / ``SparseConvTensor`` / ``SubMConv3d`` / ``SparseConv3d`` /
     ``SparseSequential`` / ``SparseBasicBlock`` / ``make_sparse_convmodule`` / ``SparseEncoder`` / ``MlvlSparseEncoder`` — the sparse 3D
                                  convolution of the middle encoders (middle_encoders/mlvl_sparse_encoder.py:11-32; spconv 1.x's surface,
-                                 restated): neighbour tables in one stream-ordered build, one launch per layer forward, no atomics
+                                 restated): neighbour tables in one stream-ordered build, one launch per layer forward, no atomics;
+                                 ``compute_dtype=torch.float16 / torch.bfloat16 / 'auto'`` (off by default) runs a layer on 16-bit
+                                 operands on the matrix cores with fp32 accumulation and fp32 parameter gradients
   * ``GraphedStep``            — a launch-bound loss slice, forward and backward, captured once as a hipGraph and replayed
 Everything outside §8 that earlier rounds built (frozen, DESIGN_EXTRAS.md) lives in ``mmdet3d_gaussian_amd.extras``.
 

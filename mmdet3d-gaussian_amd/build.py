@@ -42,6 +42,7 @@ SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'view_net.hip': ['-ffp-contract=off'],     # the view transforms, the cells, the canvas and the sampled features replay bit for bit in view_net_cpu.cpp
     'simota.hip': ['-ffp-contract=off'],       # memberships, the IoU, the costs on fx_logf, both selections and every match replay bit for bit in simota_cpu.cpp
     'sparse_conv.hip': ['-ffp-contract=off'],  # every table of the index build replays bit for bit in sparse_conv_cpu.cpp; explicit fmaf for the values; rocPRIM sort + scan
+    'sparse_conv_16.hip': ['-ffp-contract=off'],  # the fp16 / bf16 forms on v_mfma_f32_16x16x32: the weight gradient's explicit fmaf keeps sparse_conv.hip's order
 }
 # The frozen round-3 extras OUTSIDE §8 (DESIGN_EXTRAS.md; include/gd3d_extras.h): a library of their own since round 6,
 # libgd3d_extras.so, linked against libgd3d.so (the inference slices call its rnms_* entry points) and loaded only by
@@ -76,6 +77,7 @@ HOST_SOURCES = {
     'view_net_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],     # same for view_net.hip: every forward output bit-identical
     'simota_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],       # same for simota.hip: every output bit-identical
     'sparse_conv_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],  # same for sparse_conv.hip: every integer output bit-identical
+    'sparse_conv_16_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],  # widen, sparse_conv_cpu.cpp's loops, one rounding; _Float16 through F16C
 }
 HOST_COMMON = ['-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 

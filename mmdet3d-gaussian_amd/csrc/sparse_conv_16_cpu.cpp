@@ -1,0 +1,179 @@
+// sparse_conv_16_cpu.cpp — the `_cpu` twins of csrc/sparse_conv_16.hip (include/gd3d.h, gd3d_sparse_conv_*_16): the
+// 16-bit operands widened to fp32 (exact), the fp32 twins of csrc/sparse_conv_cpu.cpp on them, and ONE rounding to nearest even of
+// every 16-bit output.  Another summation order than the device's matrix cores: the values agree to the tests' bound, not to the bit.
+// fp16 goes through _Float16 (F16C at x86-64-v3); bf16 is the upper half of an fp32, rounded by explicit bit operations.
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "sparse_conv_common.h"
+
+using namespace sparse_conv;
+
+namespace {
+
+inline float widen_bf16(uint16_t h) {
+  const uint32_t u = (uint32_t)h << 16;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+
+inline uint16_t narrow_bf16(float f) {   // round to nearest even; inf stays inf, a NaN stays a (quiet) NaN
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+inline float widen_f16(uint16_t h) {
+  _Float16 v;
+  std::memcpy(&v, &h, 2);
+  return (float)v;
+}
+
+inline uint16_t narrow_f16(float f) {
+  const _Float16 v = (_Float16)f;
+  uint16_t h;
+  std::memcpy(&h, &v, 2);
+  return h;
+}
+
+bool dtype_ok(int32_t dtype) { return dtype == GD3D_DTYPE_F16 || dtype == GD3D_DTYPE_BF16; }
+bool odd(const void* p) { return ((uintptr_t)p & 1u) != 0; }
+
+std::vector<float> widen(const void* p, int64_t n, int32_t dtype) {
+  std::vector<float> out((size_t)(p == nullptr || n < 0 ? 0 : n));
+  const uint16_t* s = (const uint16_t*)p;
+  if (dtype == GD3D_DTYPE_F16)
+    for (size_t i = 0; i < out.size(); ++i) out[i] = widen_f16(s[i]);
+  else
+    for (size_t i = 0; i < out.size(); ++i) out[i] = widen_bf16(s[i]);
+  return out;
+}
+
+void narrow(const std::vector<float>& v, int32_t dtype, void* p) {
+  uint16_t* d = (uint16_t*)p;
+  if (dtype == GD3D_DTYPE_F16)
+    for (size_t i = 0; i < v.size(); ++i) d[i] = narrow_f16(v[i]);
+  else
+    for (size_t i = 0; i < v.size(); ++i) d[i] = narrow_bf16(v[i]);
+}
+
+int dense_geo(int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W, Geo* g) {
+  const int32_t shape[3] = {D, H, W}, one[3] = {1, 1, 1}, zero[3] = {0, 0, 0};
+  if (C < 1) return GD3D_E_BADARG;
+  if (C > MAX_C) return GD3D_E_TOOLARGE;
+  const int rc = make_geo(N, B, shape, one, one, zero, 0, g);
+  if (rc != 0) return rc;
+  if (g->in_sent > (1LL << 62) / C || N * C > (1LL << 40)) return GD3D_E_TOOLARGE;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gd3d_sparse_conv_forward_16_cpu(const void* features, const void* weight, const float* bias, const int32_t* nbr, const int64_t* num,
+                                    int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* out) {
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (!dtype_ok(dtype) || N < 0 || R < 0) return GD3D_E_BADARG;
+  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  if (R == 0) return 0;
+  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
+  if (odd(features) || odd(weight) || odd(out)) return GD3D_E_BADARG;
+  try {
+    const std::vector<float> x = widen(features, N * Cin, dtype), w = widen(weight, (int64_t)K * Cin * Cout, dtype);
+    std::vector<float> o((size_t)(R * Cout));
+    const int e = gd3d_sparse_conv_forward_cpu(N > 0 ? x.data() : nullptr, w.data(), bias, nbr, num, N, R, K, Cin, Cout, o.data());
+    if (e != 0) return e;
+    narrow(o, dtype, out);
+    return 0;
+  } catch (const std::bad_alloc&) {
+    return GD3D_E_HOST;
+  }
+}
+
+int gd3d_sparse_conv_backward_input_16_cpu(const void* grad_out, const void* weight, const int32_t* table, int32_t flip, int64_t N,
+                                           int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* grad_features) {
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (!dtype_ok(dtype) || N < 0 || R < 0 || (flip && N != R)) return GD3D_E_BADARG;
+  if (N > 0x7fffffffLL || R > 0x7fffffffLL || N * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  if (N == 0) return 0;
+  if (weight == nullptr || table == nullptr || grad_features == nullptr || (R > 0 && grad_out == nullptr)) return GD3D_E_BADARG;
+  if (odd(grad_out) || odd(weight) || odd(grad_features)) return GD3D_E_BADARG;
+  try {
+    const std::vector<float> gy = widen(grad_out, R * Cout, dtype), w = widen(weight, (int64_t)K * Cin * Cout, dtype);
+    std::vector<float> gx((size_t)(N * Cin));
+    const int e = gd3d_sparse_conv_backward_input_cpu(R > 0 ? gy.data() : nullptr, w.data(), table, flip, N, R, K, Cin, Cout, gx.data());
+    if (e != 0) return e;
+    narrow(gx, dtype, grad_features);
+    return 0;
+  } catch (const std::bad_alloc&) {
+    return GD3D_E_HOST;
+  }
+}
+
+int gd3d_sparse_conv_backward_weight_16_cpu(const void* features, const void* grad_out, const int32_t* nbr, const int64_t* num,
+                                            int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* workspace,
+                                            float* grad_weight, float* grad_bias) {
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (!dtype_ok(dtype) || N < 0 || R < 0 || grad_weight == nullptr) return GD3D_E_BADARG;
+  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  if (odd(features) || odd(grad_out)) return GD3D_E_BADARG;
+  try {
+    const bool empty = R == 0 || N == 0;
+    const std::vector<float> x = widen(features, empty ? 0 : N * Cin, dtype), gy = widen(grad_out, empty ? 0 : R * Cout, dtype);
+    return gd3d_sparse_conv_backward_weight_cpu(empty || features == nullptr ? nullptr : x.data(), empty || grad_out == nullptr ? nullptr : gy.data(),
+                                                nbr, num, N, R, K, Cin, Cout, workspace, grad_weight, grad_bias);
+  } catch (const std::bad_alloc&) {
+    return GD3D_E_HOST;
+  }
+}
+
+int gd3d_sparse_to_dense_16_cpu(const void* features, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H,
+                                int32_t W, void* dense) {
+  Geo g;
+  const int rc = dense_geo(N, C, B, D, H, W, &g);
+  if (rc != 0) return rc;
+  if (B == 0) return 0;
+  if (dense == nullptr || odd(dense)) return GD3D_E_BADARG;
+  const long long plane = (long long)D * H * W;
+  uint16_t* d = (uint16_t*)dense;
+  std::memset(d, 0, sizeof(uint16_t) * (size_t)g.in_sent * (size_t)C);
+  if (N == 0) return 0;
+  if (features == nullptr || coors == nullptr || odd(features)) return GD3D_E_BADARG;
+  const uint16_t* f = (const uint16_t*)features;
+  for (int64_t i = 0; i < N; ++i) {
+    const int32_t* c = coors + i * 4;
+    if (!row_active(c, g)) continue;
+    const long long cell = ((long long)c[1] * H + c[2]) * W + c[3];
+    for (int ch = 0; ch < C; ++ch) d[((long long)c[0] * C + ch) * plane + cell] = f[i * C + ch];
+  }
+  return 0;
+}
+
+int gd3d_sparse_to_dense_backward_16_cpu(const void* grad_dense, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D,
+                                         int32_t H, int32_t W, void* grad_features) {
+  Geo g;
+  const int rc = dense_geo(N, C, B, D, H, W, &g);
+  if (rc != 0) return rc;
+  if (N == 0) return 0;
+  if (coors == nullptr || grad_features == nullptr || (B > 0 && grad_dense == nullptr)) return GD3D_E_BADARG;
+  if (odd(grad_dense) || odd(grad_features)) return GD3D_E_BADARG;
+  const long long plane = (long long)D * H * W;
+  const uint16_t* s = (const uint16_t*)grad_dense;
+  uint16_t* gx = (uint16_t*)grad_features;
+  for (int64_t i = 0; i < N; ++i) {
+    const int32_t* c = coors + i * 4;
+    const bool in = row_active(c, g);
+    const long long cell = in ? ((long long)c[1] * H + c[2]) * W + c[3] : 0;
+    for (int ch = 0; ch < C; ++ch) gx[i * C + ch] = in ? s[((long long)c[0] * C + ch) * plane + cell] : (uint16_t)0;
+  }
+  return 0;
+}
+
+}  // extern "C"

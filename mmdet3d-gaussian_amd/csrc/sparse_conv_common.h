@@ -19,6 +19,7 @@ constexpr int MAX_C = 256;    // channels, either side
 constexpr int TILE_M = 64;    // output rows of one workgroup of the forward / input-gradient kernel (tests name their row counts from it)
 constexpr int TILE_N = 64;    // output channels of one workgroup
 constexpr int TILE_K = 32;    // reduction chunk staged in LDS
+constexpr int TILE_M16 = 128; // output rows of one workgroup of the 16-bit forward / input-gradient kernel (csrc/sparse_conv_16.hip): 4 waves x 2 tiles of 16
 constexpr int WG_ROWS = 32;   // rows of one staged step of the weight gradient
 constexpr int MAX_PARTS = 64; // row chunks (partial sums per offset) of the weight gradient
 

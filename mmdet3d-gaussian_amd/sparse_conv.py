@@ -8,8 +8,10 @@ Three calls carry it (csrc/sparse_conv.hip): `sparse_conv_index` builds the neig
 run of launches (64-bit keys, a stable radix sort, look-ups by lower bound; the outputs of a strided layer in ascending (b, z, y, x)
 order, as spconv 1.x's GPU path gives them), `sparse_conv` evaluates a layer over a table (one launch forward; one for the input
 gradient; three for the weight and bias gradients; no atomics, the bits replay), `sparse_to_dense` is `SparseConvTensor.dense()`.  CUDA
-tensors go to the kernels on the current stream, CPU tensors to the library's `_cpu` twins.  fp32: another dtype is evaluated in fp32 and
-cast back.  Dilation must be 1.
+tensors go to the kernels on the current stream, CPU tensors to the library's `_cpu` twins.  By default fp32: another dtype is evaluated
+in fp32 and cast back.  `compute_dtype=torch.float16 / torch.bfloat16 / 'auto'` (a keyword of `sparse_conv`, of every layer and of every
+builder here) selects the mixed-precision form (csrc/sparse_conv_16.hip): 16-bit operands on the matrix cores, fp32
+accumulation, a 16-bit output, fp32 weight and bias gradients.  Dilation must be 1.
 """
 import ctypes
 import math
@@ -166,14 +168,95 @@ class _SparseConv(torch.autograd.Function):
         return gx, gw, gb, None, None, None, None
 
 
-def sparse_conv(features, weight, bias, index):
+_DTYPE_CODES = {torch.float16: 1, torch.bfloat16: 2}          # GD3D_DTYPE_F16, GD3D_DTYPE_BF16 (include/gd3d.h)
+
+
+def _autocast_dtype(device_type):
+    """the autocast dtype of `device_type` where autocast is enabled for it, else None"""
+    if device_type not in ('cuda', 'cpu'):
+        return None
+    return torch.get_autocast_dtype(device_type) if torch.is_autocast_enabled(device_type) else None
+
+
+def _check_compute_dtype(compute_dtype, who):
+    if compute_dtype is not None and not (isinstance(compute_dtype, str) and compute_dtype == 'auto') and compute_dtype not in _DTYPE_CODES:
+        raise RuntimeError(f"{who}: compute_dtype must be None, torch.float16, torch.bfloat16 or 'auto', got {compute_dtype!r}")
+    return compute_dtype
+
+
+def _resolve_compute_dtype(compute_dtype, features):
+    """None (the fp32 path), torch.float16 or torch.bfloat16.  'auto': the features' dtype if it is one of the two, else the autocast
+    dtype where autocast is enabled for the features' device, else None"""
+    if _check_compute_dtype(compute_dtype, 'sparse_conv') is None or compute_dtype in _DTYPE_CODES:
+        return compute_dtype
+    if features.dtype in _DTYPE_CODES:
+        return features.dtype
+    dtype = _autocast_dtype(features.device.type)
+    return dtype if dtype in _DTYPE_CODES else None
+
+
+def _as16(t, dtype):
+    """t as a contiguous tensor of `dtype`; t itself when it already is"""
+    if t.dtype != dtype:
+        t = t.to(dtype)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+class _SparseConv16(torch.autograd.Function):
+    """`_SparseConv` on 16-bit operands: features, weight and grad_out in `dtype`, the bias and the parameter gradients fp32"""
+
+    @staticmethod
+    def forward(ctx, features, weight, bias, nbr, nbr_t, num, subm, dtype):
+        x, w = _as16(features, dtype), _as16(weight, dtype)
+        b = None if bias is None else _host.f32c(bias)
+        N, (K, Cin, Cout), R, dev = x.size(0), w.shape, nbr.size(0), x.device
+        out = torch.empty((R, Cout), dtype=dtype, device=dev)
+        ptr = _host.ptr_or_null
+        _host.call('gd3d_sparse_conv_forward_16', dev,
+                   (ptr(x), ptr(w), ptr(b), ptr(nbr), ptr(num), N, R, K, Cin, Cout, _DTYPE_CODES[dtype], ptr(out)))
+        ctx.save_for_backward(x, w, nbr, nbr_t, num)                                   # the 16-bit copies
+        ctx.state = (subm, bias is not None, features.dtype, weight.dtype, None if bias is None else bias.dtype, weight.shape, dtype)
+        return out
+
+    @staticmethod
+    @_host.guard_double_backward
+    def backward(ctx, grad_out):
+        x, w, nbr, nbr_t, num = ctx.saved_tensors
+        subm, has_bias, x_dtype, w_dtype, b_dtype, w_shape, dtype = ctx.state
+        gy = _as16(grad_out, dtype)
+        N, (K, Cin, Cout), R, dev = x.size(0), w.shape, nbr.size(0), x.device
+        code, ptr = _DTYPE_CODES[dtype], _host.ptr_or_null
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty((N, Cin), dtype=dtype, device=dev)
+            _host.call('gd3d_sparse_conv_backward_input_16', dev,
+                       (ptr(gy), ptr(w), ptr(nbr if subm else nbr_t), int(subm), N, R, K, Cin, Cout, code, ptr(gx)))
+            gx = gx.to(x_dtype)
+        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
+            gw = torch.empty((K, Cin, Cout), dtype=torch.float32, device=dev)          # fp32 out of the kernel: master weights get unrounded gradients
+            gb = torch.empty((Cout,), dtype=torch.float32, device=dev) if has_bias else None
+            work = _workspace(_weight_workspace_bytes(R, K, Cin, Cout), dev)
+            _host.call('gd3d_sparse_conv_backward_weight_16', dev,
+                       (ptr(x), ptr(gy), ptr(nbr), ptr(num), N, R, K, Cin, Cout, code, ptr(work), ptr(gw), ptr(gb)))
+            gw = gw.to(w_dtype).reshape(w_shape)
+            gb = gb.to(b_dtype) if has_bias else None
+        return gx, gw, gb, None, None, None, None, None
+
+
+def sparse_conv(features, weight, bias, index, compute_dtype=None):
     """One sparse convolution layer over the tables of `sparse_conv_index` -> (R, Cout), differentiable w.r.t. features, weight, bias.
 
     out[o] = sum over the offsets j with index.nbr[o, j] >= 0 of features[nbr[o, j]] @ weight[j] (+ bias); weight is spconv 1.x's
     (kz, ky, kx, Cin, Cout) or the flat (K, Cin, Cout).  A row without a valid neighbour — an inactive row of a submanifold layer, a tail row
     of the static form — is zero, bias or not, and takes no part in any gradient.  Forward: one launch; input gradient: one (the same
     kernel over the transposed table and weight); weight and bias gradients: per-chunk partial sums and one finishing launch.  No atomics
-    anywhere: the same bits from run to run."""
+    anywhere: the same bits from run to run.
+
+    compute_dtype=None: fp32 (another dtype is evaluated in fp32 and cast back).  torch.float16 / torch.bfloat16: the mixed-precision form —
+    features and weight are cast to it (nothing is done where they already are), the bias stays fp32, the products are accumulated in fp32 on
+    the matrix cores and rounded once; the output comes back in compute_dtype, grad_features in the features' dtype, and the weight and
+    bias gradients are computed in fp32 and cast to the parameters' dtypes.  'auto': the features' dtype if it is one of the two, else the
+    autocast dtype where autocast is enabled for the features' device, else None."""
     if not isinstance(index, SparseConvIndex):
         raise RuntimeError('sparse_conv: index must be the record sparse_conv_index returns')
     w = _weight3(weight, 'sparse_conv')
@@ -190,36 +273,43 @@ def sparse_conv(features, weight, bias, index):
     for name, t in (('weight', weight), ('bias', bias), ('index', index.nbr)):
         if t is not None and t.device != features.device:
             raise RuntimeError(f'sparse_conv: {name} is on {t.device}, features on {features.device}')
+    dtype = _resolve_compute_dtype(compute_dtype, features)
+    if dtype is not None:
+        return _SparseConv16.apply(features, w, bias, index.nbr, index.nbr_t, index.num, index.subm, dtype)
     return _SparseConv.apply(features, w, bias, index.nbr, index.nbr_t, index.num, index.subm)
 
 
 class _SparseToDense(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, coors, shape, B):
-        x = _host.f32c(features)
+        half = features.dtype in _DTYPE_CODES                                          # 2-byte elements are copied as they are
+        x = features.contiguous() if half else _host.f32c(features)
         N, C, dev = x.size(0), x.size(1), x.device
-        dense = torch.empty((B, C) + shape, dtype=torch.float32, device=dev)
+        dense = torch.empty((B, C) + shape, dtype=x.dtype, device=dev)
         ptr = _host.ptr_or_null
-        _host.call('gd3d_sparse_to_dense', dev, (ptr(x), ptr(coors), N, C, B, *shape, ptr(dense)))
+        _host.call('gd3d_sparse_to_dense_16' if half else 'gd3d_sparse_to_dense', dev, (ptr(x), ptr(coors), N, C, B, *shape, ptr(dense)))
         ctx.save_for_backward(coors)
         ctx.state = (shape, B, N, C, features.dtype)
-        return dense if features.dtype == torch.float32 else dense.to(features.dtype)
+        return dense if features.dtype == dense.dtype else dense.to(features.dtype)
 
     @staticmethod
     @_host.guard_double_backward
     def backward(ctx, grad_dense):
         (coors,) = ctx.saved_tensors
         shape, B, N, C, dtype = ctx.state
-        g = _host.f32c(grad_dense)
-        gx = torch.empty((N, C), dtype=torch.float32, device=g.device)
+        half = dtype in _DTYPE_CODES and grad_dense.dtype == dtype
+        g = grad_dense.contiguous() if half else _host.f32c(grad_dense)
+        gx = torch.empty((N, C), dtype=g.dtype, device=g.device)
         ptr = _host.ptr_or_null
-        _host.call('gd3d_sparse_to_dense_backward', g.device, (ptr(g), ptr(coors), N, C, B, *shape, ptr(gx)))
+        _host.call('gd3d_sparse_to_dense_backward_16' if half else 'gd3d_sparse_to_dense_backward', g.device,
+                   (ptr(g), ptr(coors), N, C, B, *shape, ptr(gx)))
         return gx.to(dtype), None, None, None
 
 
 def sparse_to_dense(features, coors, spatial_shape, batch_size):
     """`SparseConvTensor.dense()` -> (B, C, D, H, W): zeros, then dense[b, :, z, y, x] = features[row] for every active row of coors
-    (N, 4) [b, z, y, x]; a fill and one launch.  Differentiable w.r.t. features: the backward is one gather, zeros for an inactive row."""
+    (N, 4) [b, z, y, x]; a fill and one launch.  Differentiable w.r.t. features: the backward is one gather, zeros for an inactive row.
+    fp16 / bf16 features are copied as 2-byte elements (no fp32 temporary); every other dtype goes through fp32."""
     shape = _triple(spatial_shape, 'spatial_shape')
     c = _coors_i32(coors, 'sparse_to_dense')
     if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.size(0) != c.size(0) or not features.dtype.is_floating_point:
@@ -272,8 +362,9 @@ class SparseModule(nn.Module):
 
 class SparseConvolution(SparseModule):
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, subm=False, indice_key=None,
-                 max_out=None):
+                 max_out=None, *, compute_dtype=None):
         super().__init__()
+        self.compute_dtype = _check_compute_dtype(compute_dtype, type(self).__name__)     # None, torch.float16, torch.bfloat16 or 'auto': `sparse_conv`
         if _triple(dilation, 'dilation') != (1, 1, 1):
             raise RuntimeError(f'{type(self).__name__}: dilation must be 1, got {dilation}')
         self.in_channels, self.out_channels = int(in_channels), int(out_channels)
@@ -315,28 +406,31 @@ class SparseConvolution(SparseModule):
             index = self.build_index(x)
             if self.indice_key is not None:
                 x.indice_dict[self.indice_key] = index
-        out = SparseConvTensor(sparse_conv(x.features, self.weight, self.bias, index), x.indices if self.subm else index.out_coors,
-                               index.out_shape, x.batch_size, x.grid)
+        out = SparseConvTensor(sparse_conv(x.features, self.weight, self.bias, index, self.compute_dtype),
+                               x.indices if self.subm else index.out_coors, index.out_shape, x.batch_size, x.grid)
         out.indice_dict = x.indice_dict
         return out
 
     def extra_repr(self):
         return (f'{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, '
-                f'bias={self.bias is not None}, indice_key={self.indice_key!r}')
+                f'bias={self.bias is not None}, indice_key={self.indice_key!r}'
+                + ('' if self.compute_dtype is None else f', compute_dtype={self.compute_dtype!r}'))
 
 
 class SubMConv3d(SparseConvolution):
     """spconv 1.x's submanifold convolution: the outputs are the inputs.  `stride` and `padding` are accepted and not used (k // 2)."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, indice_key=None):
-        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, bias, True, indice_key)
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, indice_key=None, *, compute_dtype=None):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, bias, True, indice_key, compute_dtype=compute_dtype)
 
 
 class SparseConv3d(SparseConvolution):
     """spconv 1.x's regular sparse convolution.  max_out (an addition): an int gives the static form of `sparse_conv_index`."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, indice_key=None, max_out=None):
-        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, bias, False, indice_key, max_out)
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, indice_key=None, max_out=None, *,
+                 compute_dtype=None):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, bias, False, indice_key, max_out,
+                         compute_dtype=compute_dtype)
 
 
 class SparseSequential(SparseModule):
@@ -395,13 +489,13 @@ class SparseBasicBlock(SparseModule):
     indice_key (an addition): one index for both layers; the result does not depend on it."""
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, conv_cfg=None, norm_cfg=None, indice_key=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, conv_cfg=None, norm_cfg=None, indice_key=None, compute_dtype=None):
         super().__init__()
         if conv_cfg is not None and conv_cfg.get('type', 'SubMConv3d') != 'SubMConv3d':
             raise RuntimeError(f'SparseBasicBlock is built from SubMConv3d, got conv_cfg {conv_cfg}')
-        self.conv1 = SubMConv3d(inplanes, planes, 3, stride, padding=1, bias=False, indice_key=indice_key)
+        self.conv1 = SubMConv3d(inplanes, planes, 3, stride, padding=1, bias=False, indice_key=indice_key, compute_dtype=compute_dtype)
         self.norm1 = _norm1d(norm_cfg, planes)
-        self.conv2 = SubMConv3d(planes, planes, 3, padding=1, bias=False, indice_key=indice_key)
+        self.conv2 = SubMConv3d(planes, planes, 3, padding=1, bias=False, indice_key=indice_key, compute_dtype=compute_dtype)
         self.norm2 = _norm1d(norm_cfg, planes)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
@@ -419,18 +513,20 @@ class SparseBasicBlock(SparseModule):
 
 
 def make_sparse_convmodule(in_channels, out_channels, kernel_size, indice_key, stride=1, padding=0, conv_type='SubMConv3d', norm_cfg=None,
-                           order=('conv', 'norm', 'act')):
+                           order=('conv', 'norm', 'act'), compute_dtype=None):
     """mmdet3d's sparse conv module: the layers of `order` — conv (no bias), BatchNorm1d(eps, momentum from norm_cfg), ReLU — in a
-    `SparseSequential`."""
+    `SparseSequential`.  compute_dtype (an addition) is handed to the conv."""
     if not isinstance(order, tuple) or len(order) > 3 or not set(order) <= {'conv', 'norm', 'act'}:
         raise RuntimeError(f"make_sparse_convmodule: order must be a tuple over 'conv', 'norm', 'act', got {order!r}")
     layers = []
     for layer in order:
         if layer == 'conv':
             if conv_type == 'SubMConv3d':
-                layers.append(SubMConv3d(in_channels, out_channels, kernel_size, stride, padding, bias=False, indice_key=indice_key))
+                layers.append(SubMConv3d(in_channels, out_channels, kernel_size, stride, padding, bias=False, indice_key=indice_key,
+                                         compute_dtype=compute_dtype))
             elif conv_type == 'SparseConv3d':
-                layers.append(SparseConv3d(in_channels, out_channels, kernel_size, stride, padding, bias=False, indice_key=indice_key))
+                layers.append(SparseConv3d(in_channels, out_channels, kernel_size, stride, padding, bias=False, indice_key=indice_key,
+                                           compute_dtype=compute_dtype))
             else:
                 raise RuntimeError(f'make_sparse_convmodule: conv_type {conv_type!r} is not built here (SubMConv3d, SparseConv3d)')
         elif layer == 'norm':
@@ -447,7 +543,7 @@ class SparseEncoder(nn.Module):
 
     def __init__(self, in_channels, sparse_shape, order=('conv', 'norm', 'act'), norm_cfg=dict(type='BN1d', eps=1e-3, momentum=0.01),
                  base_channels=16, output_channels=128, encoder_channels=((16,), (32, 32, 32), (64, 64, 64), (64, 64, 64)),
-                 encoder_paddings=((1,), (1, 1, 1), (1, 1, 1), ((0, 1, 1), 1, 1)), block_type='conv_module'):
+                 encoder_paddings=((1,), (1, 1, 1), (1, 1, 1), ((0, 1, 1), 1, 1)), block_type='conv_module', compute_dtype=None):
         super().__init__()
         if block_type not in ('conv_module', 'basicblock'):
             raise RuntimeError(f"block_type must be 'conv_module' or 'basicblock', got {block_type!r}")
@@ -457,12 +553,14 @@ class SparseEncoder(nn.Module):
         self.in_channels, self.order, self.base_channels, self.output_channels = in_channels, order, base_channels, output_channels
         self.encoder_channels, self.encoder_paddings = encoder_channels, encoder_paddings
         self.stage_num = len(encoder_channels)
-        self.fp16_enabled = False
+        self.fp16_enabled = False                 # mmdet3d's attribute, inert here: compute_dtype='auto' is what follows autocast and the fp16 hook
+        self.compute_dtype = _check_compute_dtype(compute_dtype, type(self).__name__)    # handed to every conv built below
         self.conv_input = make_sparse_convmodule(in_channels, base_channels, 3, norm_cfg=norm_cfg, padding=1, indice_key='subm1',
-                                                 conv_type='SubMConv3d', order=order if order[0] == 'conv' else ('conv',))
+                                                 conv_type='SubMConv3d', order=order if order[0] == 'conv' else ('conv',),
+                                                 compute_dtype=compute_dtype)
         encoder_out_channels = self.make_encoder_layers(make_sparse_convmodule, norm_cfg, base_channels, block_type=block_type)
         self.conv_out = make_sparse_convmodule(encoder_out_channels, output_channels, kernel_size=(3, 1, 1), stride=(2, 1, 1), norm_cfg=norm_cfg,
-                                               padding=0, indice_key='spconv_down2', conv_type='SparseConv3d')
+                                               padding=0, indice_key='spconv_down2', conv_type='SparseConv3d', compute_dtype=compute_dtype)
 
     def make_encoder_layers(self, make_block, norm_cfg, in_channels, block_type='conv_module', conv_cfg=dict(type='SubMConv3d')):
         self.encoder_layers = SparseSequential()
@@ -473,17 +571,17 @@ class SparseEncoder(nn.Module):
                 padding = tuple(self.encoder_paddings[i])[j]
                 if i != 0 and j == 0 and block_type == 'conv_module':     # every stage but the first starts with the strided layer
                     blocks_list.append(make_block(in_channels, out_channels, 3, norm_cfg=norm_cfg, stride=2, padding=padding,
-                                                  indice_key=f'spconv{i + 1}', conv_type='SparseConv3d'))
+                                                  indice_key=f'spconv{i + 1}', conv_type='SparseConv3d', compute_dtype=self.compute_dtype))
                 elif block_type == 'basicblock':
                     if j == len(blocks) - 1 and i != len(self.encoder_channels) - 1:
                         blocks_list.append(make_block(in_channels, out_channels, 3, norm_cfg=norm_cfg, stride=2, padding=padding,
-                                                      indice_key=f'spconv{i + 1}', conv_type='SparseConv3d'))
+                                                      indice_key=f'spconv{i + 1}', conv_type='SparseConv3d', compute_dtype=self.compute_dtype))
                     else:
                         blocks_list.append(SparseBasicBlock(out_channels, out_channels, norm_cfg=norm_cfg, conv_cfg=conv_cfg,
-                                                            indice_key=f'subm{i + 1}'))
+                                                            indice_key=f'subm{i + 1}', compute_dtype=self.compute_dtype))
                 else:
                     blocks_list.append(make_block(in_channels, out_channels, 3, norm_cfg=norm_cfg, padding=padding, indice_key=f'subm{i + 1}',
-                                                  conv_type='SubMConv3d'))
+                                                  conv_type='SubMConv3d', compute_dtype=self.compute_dtype))
                 in_channels = out_channels
             self.encoder_layers.add_module(f'encoder_layer{i + 1}', SparseSequential(*blocks_list))
         return out_channels
