@@ -3,7 +3,8 @@
 * the cases    every value case of tests/sparse_conv_ref.py (their channel pairs put every path of csrc/sparse_conv_16.hip under test:
                4, 5 and 3 input channels the element-wise gather and a ragged end of the reduction axis, 16 channels two offsets per
                step of 32 and a half-filled last step, 24 / 40 an offset that straddles a step, K = 3 of `down` one and a half steps,
-               `isolated` steps that are skipped), and `ROW_CASES`: row counts around the 16 rows of a wave and the 128 rows of a
+               `isolated` steps that are skipped; the further geometries and channel edges add K Cin < 32, partial second to fourth column
+               tiles and chunks that are never staged), and `ROW_CASES`: row counts around the 16 rows of a wave and the 128 rows of a
                workgroup of the 16-bit kernel, at 16 -> 16, built with `ref._case` / `ref.random_coors`.
 * the oracle   `ref.oracle` / `ref.sparse_oracle` (the fp64 dense conv3d) on the operands AFTER rounding X, W and gY to the 16-bit
                type (`.to(dtype).double()`); the bias stays fp32.  A: the same on absolute values.  L: `ref.term_counts`.
@@ -41,9 +42,11 @@ def _make_row_cases():
 
 ROW_CASES = _make_row_cases()
 VALUE_CASES = sorted(n for n, c in ref.CASES.items() if c['values']) + sorted('16:' + n for n in ROW_CASES)
-# the seven cases of the fp32 guard test, the 4 -> 16 submanifold case (the element-wise gather) and the submanifold case of the other grid
+# the seven first cases of the fp32 guard test, the 4 -> 16 submanifold case (the element-wise gather), the submanifold case of the other
+# grid, and the dead-tile cases: a workgroup whose 128 rows are all inactive or past num[0], weight chunks that are never staged
+DEAD_TILE_CASES = ('subm_inactive_block', 's2p1_inactive_block', 's2p1_max_out_far_above', 'subm_isolated_c64_64', 's2p1_isolated_c64_64')
 GUARD_CASES = ('subm_inactive_rows_scattered_and_tail', 's2p1_max_out_below', 's2p1_max_out_above', 'down_7x11x13_c16_32', 's2p011_7x11x13_c3_7',
-               'subm_rows_1', 's2p1_rows_tile_plus_1', 'subm_9x12x10_c4_16', 'subm_7x11x13_c64_64')
+               'subm_rows_1', 's2p1_rows_tile_plus_1', 'subm_9x12x10_c4_16', 'subm_7x11x13_c64_64') + DEAD_TILE_CASES
 
 
 def case_of(name):

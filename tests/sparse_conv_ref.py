@@ -230,7 +230,59 @@ def _make_cases():
     return cases
 
 
+# geometries beyond the shipped encoders' (NOT in GEOMS: `_make_cases` loops over that): (kernel, stride, padding, subm), Cin, Cout
+MORE_GEOMS = {
+    'subm_k1': (((1, 1, 1), (1, 1, 1), (0, 0, 0), True), 1, 8),
+    'subm_k311': (((3, 1, 1), (1, 1, 1), (1, 0, 0), True), 24, 12),
+    'subm_k133': (((1, 3, 3), (1, 1, 1), (0, 1, 1), True), 136, 72),
+    'subm_k515': (((5, 1, 5), (1, 1, 1), (2, 0, 2), True), 9, 9),
+    'k1': (((1, 1, 1), (1, 1, 1), (0, 0, 0), False), 8, 1),
+    'k2s2': (((2, 2, 2), (2, 2, 2), (0, 0, 0), False), 65, 33),
+    'k2s1p1': (((2, 2, 2), (1, 1, 1), (1, 1, 1), False), 17, 17),
+    'k3s1p0': (((3, 3, 3), (1, 1, 1), (0, 0, 0), False), 2, 3),
+    'k3s1p1': (((3, 3, 3), (1, 1, 1), (1, 1, 1), False), 16, 20),
+    'k3s3p2': (((3, 3, 3), (3, 3, 3), (2, 2, 2), False), 1, 1),
+    'k3s4p0': (((3, 3, 3), (4, 4, 4), (0, 0, 0), False), 12, 40),
+    'k133s122': (((1, 3, 3), (1, 2, 2), (0, 1, 1), False), 33, 65),
+    'k233s212': (((2, 3, 3), (2, 1, 2), (1, 0, 1), False), 72, 136),
+    'k551s221': (((5, 5, 1), (2, 2, 1), (2, 2, 0), False), 130, 66),
+    'k27x1x1': (((27, 1, 1), (1, 1, 1), (13, 0, 0), False), 16, 16),
+}
+MORE_GEOM_CASES = {}      # geometry name -> case name
+DEAD_ROWS = (64, 256)     # the rows of the `inactive_block` cases that are [-1, -1, -1, -1]
+
+
+def _make_more_cases(old):
+    """the cases added after `_make_cases`, drawn from a generator of their own: no earlier case changes.  A side above 64 channels uses
+    the gather - matmul oracle (`values='sparse'`)."""
+    rng = np.random.default_rng(23)
+    cases = {}
+    how = lambda cin, cout: 'sparse' if max(cin, cout) > 64 else 'dense'
+    for n, (geom, (g, cin, cout)) in enumerate(MORE_GEOMS.items()):
+        shape = ((9, 12, 10), (7, 11, 13))[n % 2]
+        name = f'{geom}_{shape[0]}x{shape[1]}x{shape[2]}_c{cin}_{cout}'
+        cases[name] = _case(random_coors(rng, 150, shape, 3, empty=(1,)), shape, 3, g, cin, cout, seed=60 + n, values=how(cin, cout))
+        MORE_GEOM_CASES[geom] = name
+    shape = (9, 12, 10)
+    # the channel edges on the shipped geometries: the maximum on both sides, mixed 16-byte / element-wise paths, one channel
+    cases['subm_c256_256_rows_400'] = _case(random_coors(rng, 400, shape, 2), shape, 2, 'subm', 256, 256, seed=80, values='sparse')
+    for n, (geom, cin, cout) in enumerate((('s2p1', 256, 256), ('subm', 16, 20), ('s2p1', 40, 8), ('down', 1, 1))):
+        cases[f'{geom}_c{cin}_{cout}'] = _case(random_coors(rng, 150, (7, 11, 13), 3, empty=(1,)), (7, 11, 13), 3, geom, cin, cout, seed=81 + n,
+                                               values=how(cin, cout))
+    # dead tiles: whole row tiles of both kernels inactive, with live rows on both sides
+    good = random_coors(rng, 108, shape, 2)
+    block = np.concatenate([good[:DEAD_ROWS[0]], np.full((DEAD_ROWS[1] - DEAD_ROWS[0], 4), -1, np.int32), good[DEAD_ROWS[0]:]])
+    for geom in ('subm', 's2p1'):
+        cases[f'{geom}_inactive_block'] = _case(block, shape, 2, geom, 16, 32, seed=86)
+    at = old['s2p1_max_out_at']
+    cases['s2p1_max_out_far_above'] = _case(at['coors'], shape, 2, 's2p1', 16, 16, max_out=at['max_out'] + 200, seed=87)
+    for geom in ('subm', 's2p1'):                                         # 64 -> 64: the 16-bit kernel stages the weight in chunks and skips most
+        cases[f'{geom}_isolated_c64_64'] = _case(old['subm_isolated']['coors'], shape, 3, geom, 64, 64, seed=88)
+    return cases
+
+
 CASES = _make_cases()
+CASES.update(_make_more_cases(CASES))
 SWEEP_SHAPE = (8, 48, 48)
 
 
@@ -239,6 +291,16 @@ def sweep_case(geom):
     """about 20 000 rows over 3 samples at 16 -> 32: many workgroups, several partial sums per offset in the weight gradient"""
     rng = np.random.default_rng(21)
     return _case(random_coors(rng, 20000, SWEEP_SHAPE, 3), SWEEP_SHAPE, 3, geom, 16, 32, seed=10)
+
+
+MANY_B, MANY_EMPTY = 300, (0, 7, 256, 299)
+
+
+@functools.lru_cache(maxsize=None)
+def many_samples_case(geom):
+    """900 rows over B = 300 samples of a (2, 3, 4) grid, four samples empty: more samples than one workgroup of the counting kernel has threads"""
+    rng = np.random.default_rng(24)
+    return _case(random_coors(rng, 900, (2, 3, 4), MANY_B, empty=MANY_EMPTY), (2, 3, 4), MANY_B, geom, 4, 4, seed=11, values=None)
 
 
 def case_of(name):

@@ -2,7 +2,8 @@
 integer outputs — out_coors, out_shape, nbr, nbr_t, num, out_batch_cnt — EXACTLY equal the numpy restatement; the values — forward, input
 gradient, weight gradient, bias gradient — lie within (L + 2) 2^-24 A of the fp64 dense-conv3d oracle, L counted from the restated tables
 and A the same convolution of absolute values (a derived bound, sparse_conv_ref.py); the modules equal the functional form, share an
-index per `indice_key`, and `MlvlSparseEncoder` at PV-RCNN's constructor values follows a per-layer fp64 oracle.
+index per `indice_key`, and `MlvlSparseEncoder` at PV-RCNN's constructor values follows a per-layer fp64 oracle.  The index build over
+300 samples, at max_out 0 and 1 and at batch size 0; a non-finite input reaches only the outputs that read it.
 tests/test_gpu_sparse_conv.py runs the same helpers on the device."""
 import ctypes
 
@@ -68,7 +69,112 @@ def check_values(name, dev, got=None):
         assert ok, f'{name}: {k} misses (L + 2) 2^-24 A on {dev}: worst ratio {worst[k]:.3e}'
     live = (ref.expected_index(name)['nbr'] >= 0).any(1)
     assert not got['out'][~live].any(), f'{name}: a row without neighbours is not zero'
+    case = ref.case_of(name)
+    dead = ~ref.active_rows(case['coors'], case['shape'], case['B'])
+    assert not got['gx'][dead].any(), f'{name}: the input gradient of an inactive row is not zero'
     return worst
+
+
+def check_many_samples(geom, dev):
+    """B = 300: the counting kernel's loop over the samples takes a second trip; every integer output equals the restatement"""
+    case = ref.many_samples_case(geom)
+    want = ref.index_ref(case['coors'], case['shape'], case['B'], case['kernel'], case['stride'], case['padding'], case['subm'])
+    got = run_index(case, dev)
+    assert tuple(got.out_shape) == tuple(want['out_shape'])
+    for k in INT_OUTPUTS:
+        if want[k] is not None:
+            assert np.array_equal(getattr(got, k).cpu().numpy(), want[k]), f'{geom}: {k} differs from the restatement on {dev}'
+    cnt = got.out_batch_cnt.cpu().numpy()
+    assert cnt.shape == (ref.MANY_B,) and cnt.sum() == int(got.num[0]) > 0 and not cnt[list(ref.MANY_EMPTY)].any()
+    assert (cnt[[b for b in range(ref.MANY_B) if b not in ref.MANY_EMPTY and b > 255]] > 0).any(), 'samples of the second trip hold rows'
+
+
+def check_max_out_0_and_1(dev):
+    """the static form at max_out 0 and 1: the tables equal the restatement, num[1] is still the true count, a layer over them returns
+    (0, C) / (1, C) in fp32 and in bf16 with finite parameter gradients (zeros at max_out 0)"""
+    name = 's2p1_max_out_at'
+    case, true = ref.CASES[name], ref.CASES[name]['max_out']
+    X, W, bias, gY = (torch.from_numpy(a).to(dev) for a in ref.operands(name))
+    for m in (0, 1):
+        want = ref.index_ref(case['coors'], case['shape'], case['B'], case['kernel'], case['stride'], case['padding'], case['subm'], m)
+        got = run_index(case, dev, max_out=m)
+        for k in INT_OUTPUTS:
+            assert np.array_equal(getattr(got, k).cpu().numpy(), want[k]), f'max_out {m}: {k} differs from the restatement on {dev}'
+        assert want['num'].tolist() == [m, true] and got.nbr_t.max().item() <= m - 1 and got.out_batch_cnt.sum().item() == m
+        for dtype in (None, torch.bfloat16):
+            x, w, b = X.clone().requires_grad_(True), W.clone().requires_grad_(True), bias.clone().requires_grad_(True)
+            out = amd.sparse_conv(x, w, b, got, compute_dtype=dtype)
+            assert out.shape == (m, W.shape[2]) and out.dtype == (dtype or torch.float32)
+            gx, gw, gb = torch.autograd.grad(out, [x, w, b], gY[:m].to(out.dtype))
+            assert gx.shape == x.shape and gw.shape == w.shape and gb.shape == b.shape
+            assert all(torch.isfinite(g).all() for g in (gx, gw, gb))
+            if m == 0:
+                assert not gx.any() and not gw.any() and not gb.any()
+            elif dtype is None:                                          # the one row against the gather - matmul oracle, the derived bound
+                o64 = ref.sparse_oracle(want, *(a.cpu().numpy() for a in (X, W, bias, gY[:1])))
+                A = ref.sparse_oracle(want, *(a.abs().cpu().numpy() for a in (X, W, bias, gY[:1])))
+                L = ref.term_counts(want, len(X), W.shape[1], W.shape[2], True)
+                for k, g in (('out', out.detach()), ('gx', gx), ('gw', gw), ('gb', gb)):
+                    assert ref.within_bound(g.cpu().numpy(), o64[k], A[k], L[k])[0], f'max_out 1: {k} misses the bound on {dev}'
+                assert gw.any() and gb.any()
+
+
+def check_batch_zero(dev):
+    """B = 0 with N > 0: every row is inactive, the counts are zero, out_batch_cnt is empty, a layer over the tables gives zeros"""
+    base = ref.CASES['s2p1_max_out_at']
+    coors = torch.from_numpy(base['coors']).to(dev)
+    N = len(coors)
+    for geom, max_out in (('subm', None), ('s2p1', None), ('s2p1', 5)):
+        k, s, p, subm = ref.GEOMS[geom]
+        want = ref.index_ref(base['coors'], base['shape'], 0, k, s, p, subm, max_out)
+        got = amd.sparse_conv_index(coors, base['shape'], 0, k, s, p, subm, max_out)
+        R = N if subm else (max_out or 0)
+        assert tuple(got.out_shape) == tuple(want['out_shape']) and got.nbr.shape == (R, 27) and got.out_batch_cnt.shape == (0,)
+        for key in INT_OUTPUTS:
+            if want[key] is not None:
+                assert np.array_equal(getattr(got, key).cpu().numpy(), want[key]), f'{geom}: {key} differs from the restatement on {dev}'
+        assert got.num.tolist() == [R if subm else 0, R if subm else 0] and (got.nbr == -1).all() and (subm or (got.nbr_t == -1).all())
+        assert (got.out_coors == (coors if subm else -1)).all()
+        x, w, b = (torch.ones(N, 4, device=dev).requires_grad_(True), torch.ones(27, 4, 8, device=dev).requires_grad_(True),
+                   torch.ones(8, device=dev).requires_grad_(True))
+        out = amd.sparse_conv(x, w, b, got)
+        grads = torch.autograd.grad(out, [x, w, b], torch.ones_like(out))
+        assert out.shape == (R, 8) and not out.any() and not any(g.any() for g in grads)
+
+
+def check_nonfinite_containment(name, dev, dtype=None):
+    """+inf and NaN in two channels of one input row i, -inf in one channel c of one live grad_out row o, against the same entry point on
+    the clean operands: what does not read the poisoned value keeps its bits, what reads it is non-finite (include/gd3d.h: NaN and inf
+    pass through).  dtype None: the fp32 path, else the 16-bit path of that type."""
+    case, nbr = ref.CASES[name], ref.expected_index(name)['nbr']
+    X, W, bias, gY = (torch.from_numpy(a).clone() for a in ref.operands(name))
+    live = (nbr >= 0).any(1)
+    i, o, c = int(nbr[nbr >= 0][0]), int(np.nonzero(live)[0][-1]), 3
+    Xp, gYp = X.clone(), gY.clone()
+    Xp[i, 0], Xp[i, 1], gYp[o, c] = float('inf'), float('nan'), float('-inf')
+    index = run_index(case, dev)
+
+    def run(x, g):
+        x, g = (x if dtype is None else x.to(dtype)).to(dev).requires_grad_(True), (g if dtype is None else g.to(dtype)).to(dev)
+        w, b = W.to(dev).requires_grad_(True), bias.to(dev).requires_grad_(True)
+        out = amd.sparse_conv(x, w, b, index, compute_dtype=dtype)
+        grads = torch.autograd.grad(out, [x, w, b], g)
+        return [t.detach().float().cpu().numpy() for t in (out,) + grads]      # exact: the 16-bit values widen without rounding
+    clean, dirty = run(X, gY), run(Xp, gYp)
+    assert all(np.isfinite(a).all() for a in clean)
+    same = lambda a, b: a.tobytes() == b.tobytes()
+    reads_i = (nbr == i).any(1)                                          # outputs that read row i
+    read_by_o = np.zeros(len(X), bool)
+    read_by_o[nbr[o][nbr[o] >= 0]] = True                                # inputs that row o reads
+    dirty_j = (nbr == i).any(0) | (nbr[o] >= 0)                          # offsets whose weight gradient sees X[i] or gY[o]
+    assert reads_i.any() and not reads_i.all() and read_by_o.any() and not read_by_o.all() and dirty_j.any() and not dirty_j.all()
+    who = f'{name} {dtype or "fp32"} on {dev}'
+    for k, (a, b), hit in (('out', (clean[0], dirty[0]), reads_i), ('gx', (clean[1], dirty[1]), read_by_o), ('gw', (clean[2], dirty[2]), dirty_j)):
+        assert same(a[~hit], b[~hit]), f'{who}: {k}: an entry that does not read the non-finite value changed'
+        flat = b[hit].reshape(int(hit.sum()), -1)
+        assert (~np.isfinite(flat)).any(1).all(), f'{who}: {k}: an entry that reads the non-finite value is finite'
+    col = np.arange(len(bias)) == c
+    assert same(clean[3][~col], dirty[3][~col]) and not np.isfinite(dirty[3][c]), f'{who}: gb'
 
 
 def check_modules_equal_functional(dev):
@@ -322,6 +428,58 @@ def test_the_cases_hold_what_they_claim():
     assert (dup[40:50, 13] == np.arange(10, 20)).all(), 'a look-up of a duplicated cell finds the lowest row'
     sub = e('subm_9x12x10_c4_16')
     assert np.array_equal(sub['nbr'][sub['nbr'][:, 5].clip(0), 26 - 5][sub['nbr'][:, 5] >= 0], np.nonzero(sub['nbr'][:, 5] >= 0)[0])   # nbr_t[i, j] = nbr[i, K-1-j]
+    # the further geometries
+    assert len(ref.MORE_GEOMS) == 15 and not set(ref.MORE_GEOMS) & set(ref.GEOMS)
+    assert sorted(int(np.prod(g[0])) for g, _, _ in ref.MORE_GEOMS.values()) == [1, 1, 3, 8, 8, 9, 9, 18, 25, 25, 27, 27, 27, 27, 27]
+    for geom, (g, cin, cout) in ref.MORE_GEOMS.items():
+        name = ref.MORE_GEOM_CASES[geom]
+        c, idx = ref.CASES[name], e(name)
+        assert (c['kernel'], c['stride'], c['padding'], c['subm'], c['cin'], c['cout']) == g + (cin, cout)
+        assert len(np.unique(c['coors'], axis=0)) == 150 and c['B'] == 3 and 1 not in c['coors'][:, 0] and c['shape'] in ((9, 12, 10), (7, 11, 13))
+        K = idx['nbr'].shape[1]
+        if c['subm']:                                                    # the transpose a submanifold input gradient reads: nbr_t[i, j] = nbr[i, K-1-j]
+            o, j = np.nonzero(idx['nbr'] >= 0)
+            assert np.array_equal(idx['nbr'][idx['nbr'][o, j], K - 1 - j], o), name
+        else:                                                            # the restated active set is conv3d(mask, ones) > 0, exactly
+            mask = torch.zeros((c['B'], 1) + c['shape'], dtype=torch.float64)
+            cc = torch.from_numpy(c['coors']).long()
+            mask[cc[:, 0], 0, cc[:, 1], cc[:, 2], cc[:, 3]] = 1
+            hit = torch.nn.functional.conv3d(mask, torch.ones((1, 1) + c['kernel'], dtype=torch.float64), stride=c['stride'], padding=c['padding'])[:, 0] > 0
+            assert np.array_equal(hit.nonzero().numpy(), idx['out_coors']) and idx['out_batch_cnt'][1] == 0, name
+    far = e(ref.MORE_GEOM_CASES['k3s4p0'])                                # a stride above the kernel: inputs that no output reads
+    assert ((far['nbr_t'] == -1).all(1)).any() and (far['nbr'] >= 0).any()
+    wide = e(ref.MORE_GEOM_CASES['k3s1p1'])                               # R >> N: more rows gathered from than written in the input gradient
+    assert len(wide['nbr']) > 5 * 150
+    grown = ref.CASES[ref.MORE_GEOM_CASES['k2s1p1']]
+    assert all(o > n for o, n in zip(e(ref.MORE_GEOM_CASES['k2s1p1'])['out_shape'], grown['shape']))
+    tiny = ref.CASES[ref.MORE_GEOM_CASES['subm_k1']]                      # K Cr < 32: the whole reduction axis is one padded step of the 16-bit kernel
+    assert 1 * tiny['cin'] < 32 and 27 * ref.CASES[ref.MORE_GEOM_CASES['k3s3p2']]['cin'] < 32
+    # the channel edges
+    lib = _lib.load()
+    top = ref.CASES['subm_c256_256_rows_400']
+    assert (len(top['coors']), top['cin'], top['cout']) == (400, 256, 256) and (64 << 20) // (27 * 256 * 256 * 4) == 9
+    per_part = 27 * 256 * 256 * 4 + 256 * 4                               # 7 chunks of 64 rows (the 64 MiB cap), not 13 of 32
+    assert lib.gd3d_sparse_conv_backward_weight_workspace_bytes(400, 27, 256, 256) == 7 * per_part
+    assert 9 < 13 < 64 and -(-400 // 64) == 7 and -(-400 // 32) == 13
+    assert (ref.CASES['s2p1_c256_256']['cin'], ref.CASES['down_c1_1']['cout']) == (256, 1)
+    assert [(ref.CASES[n]['cin'] % 8, ref.CASES[n]['cout'] % 8) for n in ('subm_c16_20', 's2p1_c40_8')] == [(0, 4), (0, 0)]
+    # the dead tiles
+    lo, hi = ref.DEAD_ROWS
+    for geom in ('subm', 's2p1'):
+        c = ref.CASES[f'{geom}_inactive_block']
+        act = ref.active_rows(c['coors'], c['shape'], c['B'])
+        assert len(act) == 300 and (c['coors'][lo:hi] == -1).all() and not act[lo:hi].any() and act[:lo].all() and act[hi:].all()
+        assert lo % ref.TILE_M == 0 and hi % 128 == 0 and hi - lo >= 128 + ref.TILE_M          # whole tiles of both kernels, a whole 16-bit workgroup
+        assert not np.isin(e(f'{geom}_inactive_block')['nbr'], np.arange(lo, hi)).any()
+    far = e('s2p1_max_out_far_above')
+    assert len(far['nbr']) == far['num'][1] + 200 and far['num'][0] == far['num'][1] and (far['nbr'][far['num'][0]:] == -1).all()
+    assert len(far['nbr']) // 128 > -(-int(far['num'][0]) // 128)         # a 16-bit workgroup (and fp32 tiles) wholly past num[0]
+    for geom in ('subm', 's2p1'):
+        c, nbr = ref.CASES[f'{geom}_isolated_c64_64'], e(f'{geom}_isolated_c64_64')['nbr']
+        assert c['bias'] and (c['cin'], c['cout']) == (64, 64) and 64 * (27 * 64 + 8) * 2 > 32 << 10           # the 16-bit weight is staged in chunks
+        assert ((nbr >= 0).sum(1) == 1).all()                             # one offset a row: every other chunk is skipped
+    lone = e('subm_isolated_c64_64')['nbr']
+    assert (lone[:, 13] == np.arange(len(lone))).all() and (np.delete(lone, 13, 1) == -1).all()               # only the centre offset
 
 
 def test_dynamic_form_returns_exact_size_views():
@@ -329,6 +487,24 @@ def test_dynamic_form_returns_exact_size_views():
     got = run_index(case, 'cpu', max_out=None)
     for k in INT_OUTPUTS:
         assert np.array_equal(getattr(got, k).numpy(), want[k]), k
+
+
+@pytest.mark.parametrize('geom', ['subm', 's2p1'])
+def test_index_over_300_samples(geom):
+    check_many_samples(geom, 'cpu')
+
+
+def test_static_form_at_max_out_0_and_1():
+    check_max_out_0_and_1('cpu')
+
+
+def test_batch_size_zero_leaves_every_row_inactive():
+    check_batch_zero('cpu')
+
+
+@pytest.mark.parametrize('name', ['subm_9x12x10_c4_16', 's2p1_9x12x10_c5_16'])
+def test_a_non_finite_value_reaches_only_what_reads_it(name):
+    check_nonfinite_containment(name, 'cpu')
 
 
 def test_other_dtypes_are_evaluated_in_fp32_and_cast_back():

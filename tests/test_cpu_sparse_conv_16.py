@@ -3,7 +3,7 @@ case of tests/sparse_conv_ref.py and the row cases of tests/sparse_conv_16_cases
 oracle on the rounded operands — the 16-bit outputs within E + u16 (|want| + E) + s, E = 2 (L + 2) 2^-24 A, the fp32 weight and bias
 gradients within (L + 2) 2^-24 A (sparse_conv_16_cases.py); `compute_dtype=None` is the call without the keyword, bit for bit; what
 'auto' picks; fp32 master weights get fp32 gradients without a 16-bit rounding; dense() of 16-bit features; the keyword reaches every
-conv of the encoders; bad arguments.  tests/test_gpu_sparse_conv_16.py runs the same helpers on the device."""
+conv of the encoders; non-finite inputs and sums beyond the type's range; bad arguments.  tests/test_gpu_sparse_conv_16.py runs the same helpers on the device."""
 import numpy as np
 import pytest
 import torch
@@ -12,7 +12,7 @@ import mmdet3d_gaussian_amd as amd
 import sparse_conv_16_cases as c16
 import sparse_conv_ref as ref
 from mmdet3d_gaussian_amd import _host, _lib
-from test_cpu_sparse_conv import run_index
+from test_cpu_sparse_conv import check_nonfinite_containment, run_index
 
 KINDS = ('fp16', 'bf16')
 
@@ -50,7 +50,25 @@ def check_values_16(name, dev, kind, got=None):
         assert ok, f'{name} {kind}: {k} misses its bound on {dev}: worst ratio {worst[k]:.3e}'
     live = (c16.expected_index(name)['nbr'] >= 0).any(1)
     assert not got['out'][~live].any(), f'{name}: a row without neighbours is not zero'
+    case = c16.case_of(name)
+    dead = ~ref.active_rows(case['coors'], case['shape'], case['B'])
+    assert not got['gx'][dead].any(), f'{name}: the input gradient of an inactive row is not zero'
     return worst
+
+
+def check_range_16(dev, kind):
+    """a sum beyond the type's range is inf, never the largest finite value: every feature 60000 (fp16) or 3e38 (bf16), every weight +1,
+    then -1, on the 4 x 4 x 4 block (8 .. 27 neighbours of 4 channels a row)"""
+    name, dtype = 'subm_dense_block_4x4x4', c16.DTYPES[kind]
+    case = ref.CASES[name]
+    index = run_index(case, dev)
+    assert (ref.expected_index(name)['nbr'] >= 0).any(1).all()
+    x = torch.full((len(case['coors']), case['cin']), dict(fp16=60000.0, bf16=3e38)[kind], device=dev).to(dtype)
+    assert torch.isfinite(x).all()
+    for sign in (1.0, -1.0):
+        w = torch.full((27, case['cin'], case['cout']), sign, device=dev)
+        out = amd.sparse_conv(x, w, None, index, compute_dtype=dtype)
+        assert out.dtype == dtype and torch.equal(out.float(), torch.full_like(out, sign * float('inf'), dtype=torch.float32)), (kind, sign)
 
 
 def check_dense_16(dev):
@@ -110,11 +128,22 @@ def test_values_twin_within_the_bounds_of_the_fp64_oracle(name, kind):
     check_values_16(name, 'cpu', kind)
 
 
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('name', ['subm_9x12x10_c4_16', 's2p1_9x12x10_c5_16'])
+def test_a_non_finite_value_reaches_only_what_reads_it(name, kind):
+    check_nonfinite_containment(name, 'cpu', c16.DTYPES[kind])
+
+
+@pytest.mark.parametrize('kind', KINDS)
+def test_a_sum_beyond_the_range_is_inf_not_the_largest_finite_value(kind):
+    check_range_16('cpu', kind)
+
+
 def test_the_row_cases_hold_what_they_claim():
     for n in (0, 1, 15, 16, 17, 127, 128, 129, 257):
         assert sum(len(c['coors']) == n for c in c16.ROW_CASES.values()) == 2, n
     assert all(c['cin'] == 16 and c['cout'] == 16 for c in c16.ROW_CASES.values())
-    assert set(c16.GUARD_CASES) <= set(ref.CASES) and len(c16.GUARD_CASES) == 9
+    assert set(c16.GUARD_CASES) <= set(ref.CASES) and len(set(c16.GUARD_CASES)) == 14 and set(c16.DEAD_TILE_CASES) <= set(c16.GUARD_CASES)
     assert ref.CASES['subm_9x12x10_c4_16']['cin'] == 4 and ref.CASES['s2p011_7x11x13_c3_7']['cout'] == 7
 
 

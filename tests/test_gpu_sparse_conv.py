@@ -2,7 +2,8 @@
 tests/test_cpu_sparse_conv.py.  The integer outputs exactly equal the numpy restatement and the `_cpu` twin; the values lie within the
 derived bound (L + 2) 2^-24 A of the fp64 dense-conv3d oracle and are bit-identical from run to run; bands around every output and
 around both workspaces stay untouched; the 20 000-row sweeps; the modules, the shared index, dense(), the encoder; the static form
-recorded and replayed in one graph on fresh inputs; the device guard."""
+recorded and replayed in one graph on fresh inputs; the device guard; the index build over 300 samples, at max_out 0 and 1 and at batch
+size 0; non-finite inputs; `out` and `gx` 4 bytes past an aligned address."""
 import ctypes
 
 import numpy as np
@@ -12,8 +13,9 @@ import torch
 import mmdet3d_gaussian_amd as amd
 import sparse_conv_ref as ref
 from mmdet3d_gaussian_amd import _lib
-from test_cpu_sparse_conv import (ENC_SHAPES, INT_OUTPUTS, SWEEPS, VALUE_CASES, check_bad_arguments, check_dense, check_encoder, check_index,
-                                  check_modules_equal_functional, check_shared_indice_key, check_values, run_index, run_values)
+from test_cpu_sparse_conv import (ENC_SHAPES, INT_OUTPUTS, SWEEPS, VALUE_CASES, check_bad_arguments, check_batch_zero, check_dense, check_encoder,
+                                  check_index, check_many_samples, check_max_out_0_and_1, check_modules_equal_functional,
+                                  check_nonfinite_containment, check_shared_indice_key, check_values, run_index, run_values)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -58,11 +60,15 @@ def test_dynamic_form_returns_exact_size_views():
         assert np.array_equal(getattr(got, k).cpu().numpy(), want[k]), k
 
 
-@pytest.mark.parametrize('name', ['subm_inactive_rows_scattered_and_tail', 's2p1_max_out_below', 's2p1_max_out_above', 'down_7x11x13_c16_32',
-                                  's2p011_7x11x13_c3_7', 'subm_rows_1', 's2p1_rows_tile_plus_1'])
-def test_nothing_is_written_beyond_the_outputs_and_the_workspaces(name):
+GUARD_CASES = ['subm_inactive_rows_scattered_and_tail', 's2p1_max_out_below', 's2p1_max_out_above', 'down_7x11x13_c16_32', 's2p011_7x11x13_c3_7',
+               'subm_rows_1', 's2p1_rows_tile_plus_1',
+               # whole 64-row tiles inactive or past num[0]; 64 -> 64 with one offset a row
+               'subm_inactive_block', 's2p1_inactive_block', 's2p1_max_out_far_above', 'subm_isolated_c64_64', 's2p1_isolated_c64_64']
+
+
+def run_c_entries_between_bands(name, shift):
     """the C entry points on sentinel-filled buffers with a guard band either side of every output and of both workspaces: every row of
-    every output is written, the bands stay untouched"""
+    every output is written, the bands stay untouched.  `out` and `gx` start `shift` floats past a 16-byte aligned address."""
     case, want = ref.case_of(name), ref.expected_index(name)
     X, W, bias, gY = (None if a is None else torch.from_numpy(a).to(DEV) for a in ref.operands(name))
     coors = torch.from_numpy(case['coors']).to(DEV)
@@ -74,7 +80,9 @@ def test_nothing_is_written_beyond_the_outputs_and_the_workspaces(name):
     bufs['num'] = torch.full((2 + 2 * G,), 77, dtype=torch.int64, device=DEV)
     floats = dict(out=R * Cout, gx=N * Cin, gw=K * Cin * Cout, gb=Cout)
     bufs.update({k: torch.full((n + 2 * G,), S, device=DEV) for k, n in floats.items()})
-    at = lambda k: bufs[k][G:].data_ptr()
+    off = {k: G + (shift if k in ('out', 'gx') else 0) for k in bufs}
+    at = lambda k: bufs[k][off[k]:].data_ptr()
+    assert all(at(k) % 16 == (4 * shift if k in ('out', 'gx') else 0) for k in floats)
 
     def banded(nbytes):
         assert nbytes % 256 == 0
@@ -94,9 +102,10 @@ def test_nothing_is_written_beyond_the_outputs_and_the_workspaces(name):
     _lib.check(lib.gd3d_sparse_conv_backward_weight(X.data_ptr(), gY.data_ptr(), at('nbr'), at('num'), N, R, K, Cin, Cout, work_w.data_ptr() + band, at('gw'),
                                                     None if bias is None else at('gb'), stream), 'gd3d_sparse_conv_backward_weight')
     torch.cuda.synchronize()
+    sizes = dict(ints, num=2, **floats)
     for k, t in bufs.items():
         guard = S if t.dtype == torch.float32 else 77
-        assert (t[:G] == guard).all() and (t[-G:] == guard).all(), f'{k}: a guard band was written'
+        assert (t[:off[k]] == guard).all() and (t[off[k] + sizes[k]:] == guard).all(), f'{k}: a guard band was written'
     for k in INT_OUTPUTS:
         if want[k] is None:
             assert (bufs[k] == 77).all(), 'nbr_t of a submanifold index is not written'
@@ -105,8 +114,45 @@ def test_nothing_is_written_beyond_the_outputs_and_the_workspaces(name):
     for w in (work_i, work_w):
         assert (w[:band] == 0x5a).all() and (w[-band:] == 0x5a).all(), 'a workspace band was written'
     o64 = ref.expected_values(name)[0]
-    got = {k: (None if o64[k] is None else bufs[k][G:-G].cpu().numpy().reshape(o64[k].shape)) for k in floats}
+    got = {k: (None if o64[k] is None else bufs[k][off[k]:off[k] + floats[k]].cpu().numpy().reshape(o64[k].shape)) for k in floats}
     check_values(name, DEV, got)                                  # every element written: no sentinel survives the bound
+    return got
+
+
+@pytest.mark.parametrize('name', GUARD_CASES)
+def test_nothing_is_written_beyond_the_outputs_and_the_workspaces(name):
+    run_c_entries_between_bands(name, 0)
+
+
+@pytest.mark.parametrize('name', [n for n in GUARD_CASES if ref.CASES[n]['cout'] % 4 == 0])
+def test_out_and_gx_4_bytes_past_an_aligned_address_take_the_element_wise_stores(name):
+    """Co % 4 == 0 with a misaligned base: the scalar stores of the same arithmetic, the same bits, nothing outside the outputs"""
+    assert ref.CASES[name]['cin'] % 4 == 0
+    got, aligned = run_c_entries_between_bands(name, 1), run_c_entries_between_bands(name, 0)
+    for k in ('out', 'gx'):
+        assert got[k].tobytes() == aligned[k].tobytes(), f'{name}: {k} differs between the 16-byte and the element-wise stores'
+
+
+@pytest.mark.parametrize('geom', ['subm', 's2p1'])
+def test_index_over_300_samples(geom):
+    check_many_samples(geom, DEV)
+    twin, got = run_index(ref.many_samples_case(geom), 'cpu'), run_index(ref.many_samples_case(geom), DEV)
+    for k in INT_OUTPUTS:
+        if getattr(got, k) is not None:
+            assert torch.equal(getattr(got, k).cpu(), getattr(twin, k)), f'{geom}: {k} differs from the twin'
+
+
+def test_static_form_at_max_out_0_and_1():
+    check_max_out_0_and_1(DEV)
+
+
+def test_batch_size_zero_leaves_every_row_inactive():
+    check_batch_zero(DEV)
+
+
+@pytest.mark.parametrize('name', ['subm_9x12x10_c4_16', 's2p1_9x12x10_c5_16'])
+def test_a_non_finite_value_reaches_only_what_reads_it(name):
+    check_nonfinite_containment(name, DEV)
 
 
 def test_modules_equal_the_functional_form():

@@ -1,8 +1,9 @@
 """fp16 / bf16 sparse 3D convolution on the MI355X (csrc/sparse_conv_16.hip): the cases of tests/sparse_conv_16_cases.py on cuda:0,
 through the helpers of tests/test_cpu_sparse_conv_16.py.  The 16-bit outputs lie within E + u16 (|want| + E) + s of the fp64 dense-conv3d
 oracle on the rounded operands, the fp32 weight and bias gradients within (L + 2) 2^-24 A, and all four are bit-identical from run to
-run; the 20 000-row sweeps; the C entries on sentinel-filled buffers with guard bands, aligned and shifted by 2 bytes; the static form
-of a two-layer stack recorded and replayed in one graph; MlvlSparseEncoder in bf16 layer by layer; dense(); the device guard."""
+run; the 20 000-row sweeps; the C entries on sentinel-filled buffers with guard bands, aligned and shifted by 2 bytes (all bases, and one
+operand at a time), the dense() entries likewise; non-finite inputs and sums beyond the range; the static form of a two-layer stack
+recorded and replayed in one graph; MlvlSparseEncoder in bf16 layer by layer; dense(); the device guard."""
 import numpy as np
 import pytest
 import torch
@@ -11,8 +12,8 @@ import mmdet3d_gaussian_amd as amd
 import sparse_conv_16_cases as c16
 import sparse_conv_ref as ref
 from mmdet3d_gaussian_amd import _lib
-from test_cpu_sparse_conv import ENC_B, ENC_SHAPES, SWEEPS, build_encoder, encoder_inputs, run_index
-from test_cpu_sparse_conv_16 import KINDS, check_dense_16, check_modules_16, check_values_16, convs_of, run_values_16
+from test_cpu_sparse_conv import ENC_B, ENC_SHAPES, SWEEPS, build_encoder, check_nonfinite_containment, encoder_inputs, run_index
+from test_cpu_sparse_conv_16 import KINDS, check_dense_16, check_modules_16, check_range_16, check_values_16, convs_of, run_values_16
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -48,13 +49,10 @@ def test_sweep_of_20000_rows_in_bf16(name):
         assert got[k].tobytes() == again[k].tobytes(), f'{name}: {k} differs from run to run'
 
 
-@pytest.mark.parametrize('shift', [0, 1], ids=['aligned', 'shifted_2_bytes'])
-@pytest.mark.parametrize('kind', KINDS)
-@pytest.mark.parametrize('name', c16.GUARD_CASES)
-def test_nothing_is_written_beyond_the_outputs_and_the_workspace(name, kind, shift):
+def run_c_entries_between_bands(name, kind, shift):
     """the 16-bit C entry points on sentinel-filled buffers with a guard band either side of every output and of the workspace: every
-    element of every output is written, the bands stay untouched; with every 16-bit base shifted by one element (2 bytes) the
-    element-wise loads and stores give the same values"""
+    element of every output is written, the bands stay untouched.  shift: elements (of 2 bytes) past an aligned address, for the gathered
+    operand ('src': features, grad_out), for 'weight' and for the 16-bit outputs ('out': out, grad_features).  -> the four results"""
     dtype, code = c16.DTYPES[kind], {'fp16': 1, 'bf16': 2}[kind]
     case, want = ref.case_of(name), ref.expected_index(name)
     X, W, bias, gY = (None if a is None else torch.from_numpy(a).to(DEV) for a in ref.operands(name))
@@ -63,26 +61,26 @@ def test_nothing_is_written_beyond_the_outputs_and_the_workspace(name, kind, shi
     lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
     G, band = 64, 4096
 
-    def shifted(t):                                               # a 16-bit copy whose base is `shift` elements past an aligned allocation
+    def shifted(t, by):                                           # a 16-bit copy whose base is `by` elements past an aligned allocation
         buf = torch.empty(t.numel() + 8, dtype=dtype, device=DEV)
-        buf[shift:shift + t.numel()] = t.to(dtype).flatten()
-        return buf
-    x16, w16, g16 = shifted(X), shifted(W), shifted(gY)
-    at16 = lambda t: t.data_ptr() + 2 * shift
+        buf[by:by + t.numel()] = t.to(dtype).flatten()
+        assert buf.data_ptr() % 16 == 0
+        return buf, buf.data_ptr() + 2 * by
+    (x16, x_at), (w16, w_at), (g16, g_at) = shifted(X, shift['src']), shifted(W, shift['weight']), shifted(gY, shift['src'])
     sizes = dict(out=(R * Cout, dtype), gx=(N * Cin, dtype), gw=(K * Cin * Cout, torch.float32), gb=(Cout, torch.float32))
     bufs = {k: torch.full((n + 2 * G,), S, dtype=dt, device=DEV) for k, (n, dt) in sizes.items()}
-    off = dict(out=G + shift, gx=G + shift, gw=G, gb=G)
+    off = dict(out=G + shift['out'], gx=G + shift['out'], gw=G, gb=G)
     at = lambda k: bufs[k].data_ptr() + off[k] * bufs[k].element_size()
     nbytes = lib.gd3d_sparse_conv_backward_weight_workspace_bytes(R, K, Cin, Cout)
     assert nbytes % 256 == 0
     work = torch.full((nbytes + 2 * band,), 0x5a, dtype=torch.uint8, device=DEV)
     assert (work.data_ptr() + band) % 256 == 0
     nbr, nbr_t, num = index.nbr.data_ptr(), None if case['subm'] else index.nbr_t.data_ptr(), index.num.data_ptr()
-    _lib.check(lib.gd3d_sparse_conv_forward_16(at16(x16), at16(w16), None if bias is None else bias.data_ptr(), nbr, num, N, R, K, Cin, Cout, code,
+    _lib.check(lib.gd3d_sparse_conv_forward_16(x_at, w_at, None if bias is None else bias.data_ptr(), nbr, num, N, R, K, Cin, Cout, code,
                                                at('out'), stream), 'gd3d_sparse_conv_forward_16')
-    _lib.check(lib.gd3d_sparse_conv_backward_input_16(at16(g16), at16(w16), nbr if case['subm'] else nbr_t, int(case['subm']), N, R, K, Cin, Cout, code,
+    _lib.check(lib.gd3d_sparse_conv_backward_input_16(g_at, w_at, nbr if case['subm'] else nbr_t, int(case['subm']), N, R, K, Cin, Cout, code,
                                                       at('gx'), stream), 'gd3d_sparse_conv_backward_input_16')
-    _lib.check(lib.gd3d_sparse_conv_backward_weight_16(at16(x16), at16(g16), nbr, num, N, R, K, Cin, Cout, code, work.data_ptr() + band, at('gw'),
+    _lib.check(lib.gd3d_sparse_conv_backward_weight_16(x_at, g_at, nbr, num, N, R, K, Cin, Cout, code, work.data_ptr() + band, at('gw'),
                                                        None if bias is None else at('gb'), stream), 'gd3d_sparse_conv_backward_weight_16')
     torch.cuda.synchronize()
     got = {}
@@ -94,6 +92,68 @@ def test_nothing_is_written_beyond_the_outputs_and_the_workspace(name, kind, shi
     o64 = c16.expected_values(name, kind)[0]
     got = {k: (None if o64[k] is None else got[k].reshape(o64[k].shape)) for k in sizes}
     check_values_16(name, DEV, kind, got)                         # every element written: no sentinel survives the bound
+    return got
+
+
+@pytest.mark.parametrize('shift', [0, 1], ids=['aligned', 'shifted_2_bytes'])
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('name', c16.GUARD_CASES)
+def test_nothing_is_written_beyond_the_outputs_and_the_workspace(name, kind, shift):
+    """with every 16-bit base shifted by one element (2 bytes) the element-wise loads and stores give the same values"""
+    run_c_entries_between_bands(name, kind, dict(src=shift, weight=shift, out=shift))
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('name', ['subm_rows_tile_plus_1', 'down_7x11x13_c16_32'])
+def test_one_misaligned_operand_at_a_time_gives_the_aligned_calls_bits(name, kind):
+    """the gather, the weight staging and the stores each fall back to their element-wise form on their own: the same arithmetic, so
+    the same bits as the call on aligned operands (include/gd3d.h)"""
+    aligned = run_c_entries_between_bands(name, kind, dict(src=0, weight=0, out=0))
+    for which in ('src', 'weight', 'out'):
+        got = run_c_entries_between_bands(name, kind, dict(dict(src=0, weight=0, out=0), **{which: 1}))
+        for k in ('out', 'gx', 'gw', 'gb'):
+            assert got[k].tobytes() == aligned[k].tobytes(), f'{name} {kind}: {k} changes with a misaligned {which}'
+
+
+@pytest.mark.parametrize('shift', [0, 1], ids=['aligned', 'shifted_2_bytes'])
+@pytest.mark.parametrize('C', [3, 4], ids=['odd_count', 'even_count'])
+def test_dense_16_entries_between_bands(C, shift):
+    """gd3d_sparse_to_dense_16 / _backward_16 on banded buffers, C * D * H * W = 315 (odd) and 420 (even) elements from an aligned base
+    and from one 2 bytes past it: the fill's tail-only, neither, head-only and head-and-tail forms.  Every element between the bands
+    is written and equals the fp32 route's; the bands stay untouched."""
+    shape, B, G = (3, 5, 7), 1, 64
+    rng = np.random.default_rng(25)
+    rows = np.concatenate([ref.random_coors(rng, 20, shape, B), np.array([[-1, -1, -1, -1], [1, 0, 0, 0], [0, 3, 0, 0]], np.int32)])
+    coors, N, n = torch.from_numpy(rows).to(DEV), len(rows), C * B * shape[0] * shape[1] * shape[2]
+    lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
+    for dtype in c16.DTYPES.values():
+        feats = torch.from_numpy(rng.standard_normal((N, C)).astype(np.float32)).to(DEV).to(dtype)
+        want = amd.sparse_to_dense(feats.float(), coors, shape, B).to(dtype)
+        dense = torch.full((n + 2 * G,), S, dtype=dtype, device=DEV)
+        lo = G + shift
+        assert dense.data_ptr() % 16 == 0 and (dense.data_ptr() + 2 * lo) % 4 == 2 * shift
+        _lib.check(lib.gd3d_sparse_to_dense_16(feats.data_ptr(), coors.data_ptr(), N, C, B, *shape, dense.data_ptr() + 2 * lo, stream), 'gd3d_sparse_to_dense_16')
+        torch.cuda.synchronize()
+        assert (dense[:lo] == S).all() and (dense[lo + n:] == S).all(), 'a guard band was written'
+        assert torch.equal(dense[lo:lo + n].reshape(want.shape), want) and want.any()
+        gx = torch.full((N * C + 2 * G,), S, dtype=dtype, device=DEV)
+        _lib.check(lib.gd3d_sparse_to_dense_backward_16(dense.data_ptr() + 2 * lo, coors.data_ptr(), N, C, B, *shape, gx.data_ptr() + 2 * lo, stream),
+                   'gd3d_sparse_to_dense_backward_16')
+        torch.cuda.synchronize()
+        assert (gx[:lo] == S).all() and (gx[lo + N * C:] == S).all(), 'a guard band was written'
+        back = gx[lo:lo + N * C].reshape(N, C)
+        assert torch.equal(back[:20], feats[:20]) and not back[20:].any()     # the gather of what was scattered; inactive rows zero
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('name', ['subm_9x12x10_c4_16', 's2p1_9x12x10_c5_16'])
+def test_a_non_finite_value_reaches_only_what_reads_it(name, kind):
+    check_nonfinite_containment(name, DEV, c16.DTYPES[kind])
+
+
+@pytest.mark.parametrize('kind', KINDS)
+def test_a_sum_beyond_the_range_is_inf_not_the_largest_finite_value(kind):
+    check_range_16(DEV, kind)
 
 
 def test_modules_equal_the_functional_form():
