@@ -1385,6 +1385,41 @@ int gd3d_sparse_to_dense_16_cpu(const void* features, const int32_t* coors, int6
 int gd3d_sparse_to_dense_backward_16_cpu(const void* grad_dense, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D,
                                          int32_t H, int32_t W, void* grad_features);
 
+/* ------------------------------------------------------------------------------------
+ * Sparse 3D convolution with a fused epilogue (an addition inside ABI 6; csrc/sparse_conv.hip, csrc/sparse_conv_16.hip, DESIGN.md
+ * §3.20): an eval-mode BatchNorm folded to a per-channel scale and shift, the residual add of a basic block and a ReLU inside the
+ * forward launch, over the SAME tables.  The plain entries above are untouched: their launches keep their code and their bits.
+ * gd3d_sparse_conv_forward_fused : features, weight, nbr, num, N, R, K, Cin, Cout, out as gd3d_sparse_conv_forward.  scale and shift:
+ *   fp32 (Cout), each nullable.  residual: (R, Cout), nullable; it must not share a byte with out (GD3D_E_BADARG).  act: GD3D_ACT_NONE or
+ *   GD3D_ACT_RELU, anything else GD3D_E_BADARG (nothing is written).  With acc the accumulated sum of gd3d_sparse_conv_forward,
+ *   unchanged, every element of a row that has a valid neighbour is ONE fixed fp32 sequence:
+ *     t = scale ? fmaf(acc, scale[c], shift ? shift[c] : 0) : acc + (shift ? shift[c] : 0)
+ *     t = residual ? t + residual[o][c] : t
+ *     t = act == GD3D_ACT_RELU ? (t < 0 ? 0 : t) : t            (a NaN passes, as torch.relu)
+ *   A row without a valid neighbour (an inactive row, a row at or past num[0]) is ZERO whatever shift and residual hold; its residual
+ *   row is not read.  scale == NULL, residual == NULL, GD3D_ACT_NONE gives gd3d_sparse_conv_forward's bits with bias = shift; so does
+ *   a scale of ones.  One launch, no atomics: the same bits from run to run.
+ * gd3d_sparse_conv_forward_fused_16 : features, weight, residual and out in `dtype`, scale and shift fp32.  The same sequence on the fp32
+ *   accumulator with the residual widened, then ONE rounding to nearest even.  The residual is read 16 bytes a lane where Cout % 8 == 0 and
+ *   its base is 16-byte aligned, element by element otherwise, whichever way out is stored: the same bits on every path.
+ * Limits, error codes and the empty case (R == 0) are those of gd3d_sparse_conv_forward[_16].
+ * `_cpu` twins: the twins' loops of the plain entries, then the sequence above (fmaf included; the 16-bit twin rounds once).
+ * ---------------------------------------------------------------------------------- */
+#define GD3D_ACT_NONE 0
+#define GD3D_ACT_RELU 1
+int gd3d_sparse_conv_forward_fused(const float* features, const float* weight, const float* scale, const float* shift, const float* residual,
+                                   const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout,
+                                   int32_t act, float* out, void* stream);
+int gd3d_sparse_conv_forward_fused_16(const void* features, const void* weight, const float* scale, const float* shift, const void* residual,
+                                      const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout,
+                                      int32_t act, int32_t dtype, void* out, void* stream);
+int gd3d_sparse_conv_forward_fused_cpu(const float* features, const float* weight, const float* scale, const float* shift,
+                                       const float* residual, const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K,
+                                       int32_t Cin, int32_t Cout, int32_t act, float* out);
+int gd3d_sparse_conv_forward_fused_16_cpu(const void* features, const void* weight, const float* scale, const float* shift,
+                                          const void* residual, const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K,
+                                          int32_t Cin, int32_t Cout, int32_t act, int32_t dtype, void* out);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

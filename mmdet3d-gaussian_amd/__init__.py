@@ -38,6 +38,9 @@
                                  restated): neighbour tables in one stream-ordered build, one launch per layer forward, no atomics;
                                  ``compute_dtype=torch.float16 / torch.bfloat16 / 'auto'`` (off by default) runs a layer on 16-bit
                                  operands on the matrix cores with fp32 accumulation and fp32 parameter gradients
+  * ``fuse_sparse_conv_bn`` / ``FusedSparseConv`` / ``FusedSparseBasicBlock`` / ``SparseEncoder.fuse()`` — the eval BatchNorm, the residual
+                                 add and the ReLU of a sparse layer inside the convolution's launch (``sparse_conv(..., scale=, shift=,
+                                 residual=, activation=)``): one fixed fp32 sequence per element, one rounding on the 16-bit path
   * ``GraphedStep``            — a launch-bound loss slice, forward and backward, captured once as a hipGraph and replayed
 Everything outside §8 that earlier rounds built (frozen, DESIGN_EXTRAS.md) lives in ``mmdet3d_gaussian_amd.extras``.
 
@@ -69,8 +72,8 @@ from .voxelize import HardSimpleVFE, Voxelization, dynamic_voxelize, hard_voxeli
 from .pillar_feat import PillarFeatureDecorator, PointVoxelStatsCalculator, pillar_decorate, point_voxel_stats
 from .view_net import PointPillarsScatter, multi_view_voxelize, pillar_scatter, to_cylindrical, to_spherical, view_sample
 from .simota import Point3DRangeGenerator, SimOTABEVAssigner, simota_assign
-from .sparse_conv import (MlvlSparseEncoder, SparseBasicBlock, SparseConv3d, SparseConvIndex, SparseConvTensor, SparseEncoder, SparseModule,
-                          SparseSequential, SubMConv3d, make_sparse_convmodule, sparse_conv, sparse_conv_index, sparse_to_dense)
+from .sparse_conv import (FusedSparseBasicBlock, FusedSparseConv, MlvlSparseEncoder, SparseBasicBlock, SparseConv3d, SparseConvIndex, SparseConvTensor, SparseEncoder, SparseModule,
+                          SparseSequential, SubMConv3d, fuse_sparse_conv_bn, make_sparse_convmodule, sparse_conv, sparse_conv_index, sparse_to_dense)
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
                         anchor_head_decoded_loss_fused, center_head_gd_loss, center_head_losses)
 from . import extras
@@ -98,4 +101,4 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'pillar_decorate', 'PillarFeatureDecorator', 'multi_view_voxelize', 'to_cylindrical', 'to_spherical', 'pillar_scatter',
            'PointPillarsScatter', 'view_sample', 'simota_assign', 'SimOTABEVAssigner', 'Point3DRangeGenerator', 'sparse_conv_index', 'sparse_conv',
            'sparse_to_dense', 'SparseConvIndex', 'SparseConvTensor', 'SparseModule', 'SubMConv3d', 'SparseConv3d', 'SparseSequential', 'SparseBasicBlock',
-           'make_sparse_convmodule', 'SparseEncoder', 'MlvlSparseEncoder', 'extras']
+           'make_sparse_convmodule', 'SparseEncoder', 'MlvlSparseEncoder', 'fuse_sparse_conv_bn', 'FusedSparseConv', 'FusedSparseBasicBlock', 'extras']

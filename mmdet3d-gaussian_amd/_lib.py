@@ -341,6 +341,10 @@ SYMBOLS = {
     'gd3d_sparse_conv_backward_weight_16_cpu': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     'gd3d_sparse_to_dense_16_cpu': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     'gd3d_sparse_to_dense_backward_16_cpu': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    'gd3d_sparse_conv_forward_fused': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'gd3d_sparse_conv_forward_fused_16': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'gd3d_sparse_conv_forward_fused_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    'gd3d_sparse_conv_forward_fused_16_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 

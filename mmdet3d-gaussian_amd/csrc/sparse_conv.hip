@@ -12,7 +12,9 @@
 //   gemm_kernel   output stationary: a workgroup owns TILE_M rows x 16, 32 or 64 channels (the smallest tile that holds Cout), walks the offsets, skips (workgroup-uniformly)
 //                 an offset no row of the tile uses, stages the gathered rows and the weight slice in LDS, accumulates with fmaf in
 //                 registers and writes every element once.  The input gradient is the same kernel over the transposed table and
-//                 weight.  No atomics: the bits replay.
+//                 weight.  No atomics: the bits replay.  FUSED (gd3d_sparse_conv_forward_fused): the epilogue of the
+//                 forward form with a per-channel scale, a residual row and a ReLU — a compile-time variant: the plain instances
+//                 keep their code.
 //   wgrad_kernel  per (row chunk, offset, tile of W[j] of 16, 32 or 64 channels a side): partial sums into the workspace; wfinish_kernel adds the chunks in
 //                 ascending order.  bias_kernel / the same finish for the bias gradient.
 // Compiled with -ffp-contract=off (the tables replay bit for bit in csrc/sparse_conv_cpu.cpp); the multiply-adds are explicit fmaf.
@@ -213,12 +215,19 @@ struct GemmArgs {
   long long n_src, rows;
   int K, Cr, Co, flip;     // flip: the table's column of offset j is K - 1 - j (the submanifold transpose)
   float* out;              // (rows, Co)
+  // the FUSED epilogue only: t = fmaf(acc, scale, bias) (+ residual), ReLU; `bias` is the folded shift
+  const float* scale;      // (Co) or null
+  const float* residual;   // (rows, Co) or null; read at live rows only
+  int act;                 // GD3D_ACT_*
+  int vec_res;             // Co % 4 == 0 and `residual` 16-byte aligned
 };
 
 // TRANS: the weight slice is read transposed (the input gradient: Cr = Cout, Co = Cin).  VEC: Co % 4 == 0 and `out` 16-byte aligned.
+// FUSED: the epilogue is one fixed fp32 sequence per element of a live row — fmaf(acc, scale, shift) or acc + shift, + residual, ReLU
+// (a NaN passes) — and zero for every other row, whose residual is not read.
 // TN: the output channels of one workgroup, 16, 32 or 64 — the smallest that holds Co, so that a 16-channel layer keeps every thread
 // busy: TN / 4 threads lie along the channels (4 each), the other BLOCK / (TN / 4) along the TILE_M rows (TN / 16 rows each).
-template <bool TRANS, bool VEC, int TN>
+template <bool TRANS, bool VEC, int TN, bool FUSED = false>
 __global__ __launch_bounds__(BLOCK) void gemm_kernel(const GemmArgs a) {
   constexpr int CT = TN / 4, RPT = TILE_M * CT / BLOCK;
   __shared__ int nb[TILE_M];
@@ -281,7 +290,33 @@ __global__ __launch_bounds__(BLOCK) void gemm_kernel(const GemmArgs a) {
     if (row >= a.rows) continue;
     const bool live = used[ty * RPT + i] != 0;                   // a row without neighbours (inactive, or past the count) is zero, bias or not
     float o[4];
-    for (int q = 0; q < 4; ++q) o[q] = live ? acc[i][q] + ((a.bias != nullptr && c + q < a.Co) ? a.bias[c + q] : 0.0f) : 0.0f;
+    if constexpr (FUSED) {
+      float res[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (live && a.residual != nullptr) {
+        const float* src = a.residual + row * a.Co + c;
+        if (a.vec_res) {                                           // 4 | Co: a piece that starts inside the row ends inside it
+          if (c < a.Co) {
+            const float4 v = *reinterpret_cast<const float4*>(src);
+            res[0] = v.x; res[1] = v.y; res[2] = v.z; res[3] = v.w;
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (c + q < a.Co) res[q] = src[q];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const bool in = c + q < a.Co;
+        const float sh = (a.bias != nullptr && in) ? a.bias[c + q] : 0.0f;
+        float v = a.scale != nullptr ? __builtin_fmaf(acc[i][q], in ? a.scale[c + q] : 0.0f, sh) : acc[i][q] + sh;
+        if (a.residual != nullptr) v = v + res[q];
+        if (a.act == GD3D_ACT_RELU) v = v < 0.0f ? 0.0f : v;
+        o[q] = live ? v : 0.0f;
+      }
+    } else {
+      for (int q = 0; q < 4; ++q) o[q] = live ? acc[i][q] + ((a.bias != nullptr && c + q < a.Co) ? a.bias[c + q] : 0.0f) : 0.0f;
+    }
     float* dst = a.out + row * a.Co + c;
     if (VEC) {
       if (c < a.Co) *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
@@ -306,7 +341,24 @@ static int launch_gemm_tile(const GemmArgs& a, bool trans, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
+template <int TN>
+static int launch_fused_tile(const GemmArgs& a, hipStream_t s) {
+  const dim3 grid((unsigned)((a.rows + TILE_M - 1) / TILE_M), (unsigned)((a.Co + TN - 1) / TN));
+  if (a.Co % 4 == 0 && aligned16(a.out)) hipLaunchKernelGGL((gemm_kernel<false, true, TN, true>), grid, dim3(BLOCK), 0, s, a);
+  else hipLaunchKernelGGL((gemm_kernel<false, false, TN, true>), grid, dim3(BLOCK), 0, s, a);
+  return (int)hipGetLastError();
+}
+
 static int tile_of(int channels) { return channels <= 16 ? 16 : (channels <= 32 ? 32 : 64); }   // the smallest tile that holds them, at most 64
+
+static int launch_fused(GemmArgs& a, hipStream_t s) {
+  a.vec_res = a.residual != nullptr && a.Co % 4 == 0 && aligned16(a.residual);
+  switch (tile_of(a.Co)) {
+    case 16: return launch_fused_tile<16>(a, s);
+    case 32: return launch_fused_tile<32>(a, s);
+    default: return launch_fused_tile<TILE_N>(a, s);
+  }
+}
 
 static int launch_gemm(const GemmArgs& a, bool trans, hipStream_t s) {
   switch (tile_of(a.Co)) {
@@ -589,7 +641,25 @@ int gd3d_sparse_conv_forward(const float* features, const float* weight, const f
   GemmArgs a;
   a.src = features; a.W = weight; a.bias = bias; a.table = nbr; a.num = (const long long*)num; a.n_src = N; a.rows = R;
   a.K = K; a.Cr = Cin; a.Co = Cout; a.flip = 0; a.out = out;
+  a.scale = nullptr; a.residual = nullptr; a.act = GD3D_ACT_NONE; a.vec_res = 0;
   return launch_gemm(a, false, (hipStream_t)stream);
+}
+
+int gd3d_sparse_conv_forward_fused(const float* features, const float* weight, const float* scale, const float* shift, const float* residual,
+                                   const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout,
+                                   int32_t act, float* out, void* stream) {
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (N < 0 || R < 0 || (act != GD3D_ACT_NONE && act != GD3D_ACT_RELU)) return GD3D_E_BADARG;
+  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  if (R == 0) return 0;
+  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
+  if (residual != nullptr && ranges_overlap(residual, out, sizeof(float) * (size_t)R * (size_t)Cout)) return GD3D_E_BADARG;
+  GemmArgs a;
+  a.src = features; a.W = weight; a.bias = shift; a.table = nbr; a.num = (const long long*)num; a.n_src = N; a.rows = R;
+  a.K = K; a.Cr = Cin; a.Co = Cout; a.flip = 0; a.out = out;
+  a.scale = scale; a.residual = residual; a.act = act; a.vec_res = 0;
+  return launch_fused(a, (hipStream_t)stream);
 }
 
 int gd3d_sparse_conv_backward_input(const float* grad_out, const float* weight, const int32_t* table, int32_t flip, int64_t N,
@@ -603,6 +673,7 @@ int gd3d_sparse_conv_backward_input(const float* grad_out, const float* weight, 
   GemmArgs a;
   a.src = grad_out; a.W = weight; a.bias = nullptr; a.table = table; a.num = nullptr; a.n_src = R; a.rows = N;
   a.K = K; a.Cr = Cout; a.Co = Cin; a.flip = flip ? 1 : 0; a.out = grad_features;
+  a.scale = nullptr; a.residual = nullptr; a.act = GD3D_ACT_NONE; a.vec_res = 0;
   return launch_gemm(a, true, (hipStream_t)stream);
 }
 

@@ -15,6 +15,8 @@
 //                 kernel over the transposed table and weight.  No atomics: the bits replay.
 //                 Cr % 8 != 0 or a misaligned base: the gather loads element by element; Co % 8 != 0 or a misaligned output: the
 //                 stores are element by element.  Same arithmetic on either path.
+//                 FUSED (gd3d_sparse_conv_forward_fused_16): the forward form with a per-channel scale, a residual row
+//                 and a ReLU in the epilogue, the tile staged unrounded in fp32 — a compile-time variant, the plain instances keep their code.
 //   wgrad_kernel  csrc/sparse_conv.hip's scheme and summation order on operands widened from 16 bits (the products of two 16-bit
 //                 values are exact in fp32): partial sums per chunk of rows, wfinish_kernel adds them in ascending order.  fp32 out.
 //   dense_kernel  the copy kernels for 2-byte elements.
@@ -86,10 +88,21 @@ struct GemmArgs {
   int vec_in, vec_out;     // Cr % 8 == 0 and src 16-byte aligned; Co % 8 == 0 and out 16-byte aligned
   int vec_w;               // W 16-byte aligned and 8 | its contiguous axis as the kernel reads it (Co forward, Cr transposed)
   uint16_t* out;           // (rows, Co)
+  // the FUSED epilogue only: t = fmaf(acc, scale, bias) (+ residual), ReLU, one rounding; `bias` is the folded shift
+  const float* scale;      // (Co) fp32 or null
+  const uint16_t* residual;   // (rows, Co) or null; read at live rows only
+  int act;                 // GD3D_ACT_*
+  int vec_res;             // Co % 8 == 0 and `residual` 16-byte aligned: independent of vec_out
 };
 
+constexpr int FPAD = 4;                     // floats between the rows of the fused epilogue's fp32 tile: rows stay 16-byte aligned, and the 4 rows
+                                            // between two lane groups are 16 banks apart (TN + 4 = 4 mod 8): a half-wave's ds_write_b32 do not conflict
+
 // TRANS: the weight is read transposed (the input gradient: Cr = Cout, Co = Cin).
-template <class E, bool TRANS, int TN>
+// FUSED (gd3d_sparse_conv_forward_fused_16): a lane applies scale and shift to its accumulators and stages them
+// UNROUNDED, in fp32, in the per-wave tile; the row-major read-back adds the residual (16 bytes a load), applies the ReLU, rounds ONCE
+// and stores 16 bytes a lane.  A compile-time variant: the plain instances keep their code.
+template <class E, bool TRANS, int TN, bool FUSED = false>
 __global__ __launch_bounds__(BLOCK) void gemm_kernel(const GemmArgs a) {
   constexpr int NT = TN / 16, OP = TN + PAD;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -209,7 +222,72 @@ __global__ __launch_bounds__(BLOCK) void gemm_kernel(const GemmArgs a) {
     }
   }
   __syncthreads();                                               // the slab is free: a wave turns its tiles through it
-  uint16_t* ot = reinterpret_cast<uint16_t*>(smem) + wave * 16 * OP;   // [16][TN + PAD]
+  if constexpr (FUSED) {
+    constexpr int OPF = TN + FPAD;
+    float* otf = reinterpret_cast<float*>(smem) + wave * 16 * OPF;   // [16][TN + FPAD] fp32
+    const bool relu = a.act == GD3D_ACT_RELU;
+    for (int rt = 0; rt < RT; ++rt) {
+      const int rbase = (wave * RT + rt) * 16;
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        const int c = n * 16 + r16;
+        const bool in = col0 + c < a.Co;
+        const float b = (a.bias != nullptr && in) ? a.bias[col0 + c] : 0.0f;
+        const float sc = (a.scale != nullptr && in) ? a.scale[col0 + c] : 0.0f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int r = g * 4 + q;
+          const float v = a.scale != nullptr ? __builtin_fmaf(acc[rt][n][q], sc, b) : acc[rt][n][q] + b;
+          otf[r * OPF + c] = live[rbase + r] ? v : 0.0f;           // a row without neighbours stays zero: its residual is not read below
+        }
+      }
+      __syncthreads();
+      if (a.vec_out) {
+        constexpr int PIECES = TN / 8;
+        for (int idx = lane; idx < 16 * PIECES; idx += 64) {
+          const int r = idx / PIECES, p = idx - r * PIECES;
+          const long long row = row0 + rbase + r;
+          const int c = col0 + p * 8;
+          if (row < a.rows && c < a.Co) {                          // 8 | Co: a piece that starts inside the row ends inside it
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(otf + r * OPF + p * 8);
+            const f32x4 hi = *reinterpret_cast<const f32x4*>(otf + r * OPF + p * 8 + 4);
+            float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            if (a.residual != nullptr && live[rbase + r]) {
+              const uint16_t* src = a.residual + row * a.Co + c;
+              if (a.vec_res) {
+                const u32x4 w = *reinterpret_cast<const u32x4*>(src);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                  v[2 * i] = v[2 * i] + E::widen((uint16_t)(w[i] & 0xffffu));
+                  v[2 * i + 1] = v[2 * i + 1] + E::widen((uint16_t)(w[i] >> 16));
+                }
+              } else {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = v[i] + E::widen(src[i]);
+              }
+            }
+            uint32_t h[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) h[i] = E::narrow(relu && v[i] < 0.0f ? 0.0f : v[i]);
+            *reinterpret_cast<u32x4*>(a.out + row * a.Co + c) = u32x4{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+          }
+        }
+      } else {
+        for (int idx = lane; idx < 16 * TN; idx += 64) {
+          const int r = idx / TN, c = idx - r * TN;
+          const long long row = row0 + rbase + r;
+          if (row < a.rows && col0 + c < a.Co) {
+            float v = otf[r * OPF + c];
+            if (a.residual != nullptr && live[rbase + r]) v = v + E::widen(a.residual[row * a.Co + col0 + c]);
+            a.out[row * a.Co + col0 + c] = E::narrow(relu && v < 0.0f ? 0.0f : v);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    return;
+  }
+  uint16_t* ot =reinterpret_cast<uint16_t*>(smem) + wave * 16 * OP;   // [16][TN + PAD]
   for (int rt = 0; rt < RT; ++rt) {
     const int rbase = (wave * RT + rt) * 16;
 #pragma unroll
@@ -243,28 +321,32 @@ __global__ __launch_bounds__(BLOCK) void gemm_kernel(const GemmArgs a) {
   }
 }
 
+// fused: the forward form with the FUSED epilogue (never transposed)
 template <class E, int TN>
-static int launch_gemm_tile(GemmArgs& a, bool trans, hipStream_t s) {
+static int launch_gemm_tile(GemmArgs& a, bool trans, bool fused, hipStream_t s) {
   const int ktp = (a.K * a.Cr + 31) & ~31;
   a.chunk = (size_t)TN * (ktp + PAD) * 2 <= (size_t)WHOLE_BYTES ? ktp : CHUNK;
   size_t lds = (size_t)TN * (a.chunk + PAD) * 2;
-  const size_t turn = (size_t)WAVES * 16 * (TN + PAD) * 2;       // the epilogue's tiles lie in the same bytes
+  const size_t turn = fused ? (size_t)WAVES * 16 * (TN + FPAD) * 4     // the epilogue's tiles lie in the same bytes: fp32 in the fused form
+                            : (size_t)WAVES * 16 * (TN + PAD) * 2;
   lds = lds > turn ? lds : turn;
   const dim3 grid((unsigned)((a.rows + ROWS - 1) / ROWS), (unsigned)((a.Co + TN - 1) / TN));
-  if (trans) hipLaunchKernelGGL((gemm_kernel<E, true, TN>), grid, dim3(BLOCK), lds, s, a);
+  if (fused) hipLaunchKernelGGL((gemm_kernel<E, false, TN, true>), grid, dim3(BLOCK), lds, s, a);
+  else if (trans) hipLaunchKernelGGL((gemm_kernel<E, true, TN>), grid, dim3(BLOCK), lds, s, a);
   else hipLaunchKernelGGL((gemm_kernel<E, false, TN>), grid, dim3(BLOCK), lds, s, a);
   return (int)hipGetLastError();
 }
 
 template <class E>
-static int launch_gemm(GemmArgs& a, bool trans, hipStream_t s) {
+static int launch_gemm(GemmArgs& a, bool trans, hipStream_t s, bool fused = false) {
   a.vec_in = a.Cr % 8 == 0 && aligned16(a.src);
   a.vec_out = a.Co % 8 == 0 && aligned16(a.out);
   a.vec_w = (trans ? a.Cr : a.Co) % 8 == 0 && aligned16(a.W);
+  a.vec_res = fused && a.residual != nullptr && a.Co % 8 == 0 && aligned16(a.residual);
   switch (tile_of(a.Co)) {
-    case 16: return launch_gemm_tile<E, 16>(a, trans, s);
-    case 32: return launch_gemm_tile<E, 32>(a, trans, s);
-    default: return launch_gemm_tile<E, 64>(a, trans, s);
+    case 16: return launch_gemm_tile<E, 16>(a, trans, fused, s);
+    case 32: return launch_gemm_tile<E, 32>(a, trans, fused, s);
+    default: return launch_gemm_tile<E, 64>(a, trans, fused, s);
   }
 }
 
@@ -496,7 +578,26 @@ int gd3d_sparse_conv_forward_16(const void* features, const void* weight, const 
   GemmArgs a;
   a.src = (const uint16_t*)features; a.W = (const uint16_t*)weight; a.bias = bias; a.table = nbr; a.num = (const long long*)num;
   a.n_src = N; a.rows = R; a.K = K; a.Cr = Cin; a.Co = Cout; a.flip = 0; a.out = (uint16_t*)out;
+  a.scale = nullptr; a.residual = nullptr; a.act = GD3D_ACT_NONE;
   return dtype == GD3D_DTYPE_F16 ? launch_gemm<F16>(a, false, (hipStream_t)stream) : launch_gemm<BF16>(a, false, (hipStream_t)stream);
+}
+
+int gd3d_sparse_conv_forward_fused_16(const void* features, const void* weight, const float* scale, const float* shift, const void* residual,
+                                      const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout,
+                                      int32_t act, int32_t dtype, void* out, void* stream) {
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (!dtype_ok(dtype) || N < 0 || R < 0 || (act != GD3D_ACT_NONE && act != GD3D_ACT_RELU)) return GD3D_E_BADARG;
+  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  if (R == 0) return 0;
+  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
+  if ((((uintptr_t)features | (uintptr_t)weight | (uintptr_t)residual | (uintptr_t)out) & 1u) != 0) return GD3D_E_BADARG;
+  if (residual != nullptr && ranges_overlap(residual, out, sizeof(uint16_t) * (size_t)R * (size_t)Cout)) return GD3D_E_BADARG;
+  GemmArgs a;
+  a.src = (const uint16_t*)features; a.W = (const uint16_t*)weight; a.bias = shift; a.table = nbr; a.num = (const long long*)num;
+  a.n_src = N; a.rows = R; a.K = K; a.Cr = Cin; a.Co = Cout; a.flip = 0; a.out = (uint16_t*)out;
+  a.scale = scale; a.residual = (const uint16_t*)residual; a.act = act;
+  return dtype == GD3D_DTYPE_F16 ? launch_gemm<F16>(a, false, (hipStream_t)stream, true) : launch_gemm<BF16>(a, false, (hipStream_t)stream, true);
 }
 
 int gd3d_sparse_conv_backward_input_16(const void* grad_out, const void* weight, const int32_t* table, int32_t flip, int64_t N,
@@ -512,6 +613,7 @@ int gd3d_sparse_conv_backward_input_16(const void* grad_out, const void* weight,
   GemmArgs a;
   a.src = (const uint16_t*)grad_out; a.W = (const uint16_t*)weight; a.bias = nullptr; a.table = table; a.num = nullptr;
   a.n_src = R; a.rows = N; a.K = K; a.Cr = Cout; a.Co = Cin; a.flip = flip ? 1 : 0; a.out = (uint16_t*)grad_features;
+  a.scale = nullptr; a.residual = nullptr; a.act = GD3D_ACT_NONE;
   return dtype == GD3D_DTYPE_F16 ? launch_gemm<F16>(a, true, (hipStream_t)stream) : launch_gemm<BF16>(a, true, (hipStream_t)stream);
 }
 

@@ -95,6 +95,31 @@ int gd3d_sparse_conv_forward_16_cpu(const void* features, const void* weight, co
   }
 }
 
+int gd3d_sparse_conv_forward_fused_16_cpu(const void* features, const void* weight, const float* scale, const float* shift,
+                                          const void* residual, const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K,
+                                          int32_t Cin, int32_t Cout, int32_t act, int32_t dtype, void* out) {
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (!dtype_ok(dtype) || N < 0 || R < 0 || (act != GD3D_ACT_NONE && act != GD3D_ACT_RELU)) return GD3D_E_BADARG;
+  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  if (R == 0) return 0;
+  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
+  if (odd(features) || odd(weight) || odd(residual) || odd(out)) return GD3D_E_BADARG;
+  if (residual != nullptr && ranges_overlap(residual, out, sizeof(uint16_t) * (size_t)R * (size_t)Cout)) return GD3D_E_BADARG;
+  try {
+    const std::vector<float> x = widen(features, N * Cin, dtype), w = widen(weight, (int64_t)K * Cin * Cout, dtype);
+    const std::vector<float> res = widen(residual, R * Cout, dtype);
+    std::vector<float> o((size_t)(R * Cout));                    // the fp32 twin's sequence on the widened operands, then the one rounding
+    const int e = gd3d_sparse_conv_forward_fused_cpu(N > 0 ? x.data() : nullptr, w.data(), scale, shift, residual != nullptr ? res.data() : nullptr,
+                                                     nbr, num, N, R, K, Cin, Cout, act, o.data());
+    if (e != 0) return e;
+    narrow(o, dtype, out);
+    return 0;
+  } catch (const std::bad_alloc&) {
+    return GD3D_E_HOST;
+  }
+}
+
 int gd3d_sparse_conv_backward_input_16_cpu(const void* grad_out, const void* weight, const int32_t* table, int32_t flip, int64_t N,
                                            int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* grad_features) {
   const int rc = check_channels(K, Cin, Cout);

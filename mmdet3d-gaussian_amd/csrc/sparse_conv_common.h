@@ -2,6 +2,7 @@
 // shared by csrc/sparse_conv.hip and csrc/sparse_conv_cpu.cpp: which rows are active, the 64-bit keys, the offsets, the per-axis range
 // checks made BEFORE anything is linearised, and the look-up in a sorted key list.  Integers only: both targets give the same tables.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/gd3d.h"
@@ -126,6 +127,12 @@ inline void weight_parts(int64_t R, int64_t kcc, int64_t* parts, int64_t* chunk)
   if (c < WG_ROWS) c = WG_ROWS;
   *chunk = c;
   *parts = R > 0 ? (R + c - 1) / c : 0;
+}
+
+// whether two buffers of `bytes` bytes share a byte (the fused forward: the residual must not overlap the output)
+inline bool ranges_overlap(const void* a, const void* b, size_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
 }
 
 inline int check_channels(int32_t K, int32_t Cin, int32_t Cout) {

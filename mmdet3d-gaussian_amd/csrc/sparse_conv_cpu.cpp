@@ -174,6 +174,32 @@ int gd3d_sparse_conv_forward_cpu(const float* features, const float* weight, con
   return 0;
 }
 
+int gd3d_sparse_conv_forward_fused_cpu(const float* features, const float* weight, const float* scale, const float* shift,
+                                       const float* residual, const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K,
+                                       int32_t Cin, int32_t Cout, int32_t act, float* out) {
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (N < 0 || R < 0 || (act != GD3D_ACT_NONE && act != GD3D_ACT_RELU)) return GD3D_E_BADARG;
+  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  if (R == 0) return 0;
+  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
+  if (residual != nullptr && ranges_overlap(residual, out, sizeof(float) * (size_t)R * (size_t)Cout)) return GD3D_E_BADARG;
+  const long long limit = limit_of(num, R);
+  gemm(features, weight, nullptr, nbr, limit, N, R, K, Cin, Cout, false, false, out);
+  for (int64_t r = 0; r < limit; ++r) {                          // the rows past the limit and the rows without a neighbour stay zero
+    if (!row_live(nbr + r * K, K, N)) continue;
+    float* o = out + r * Cout;
+    for (int c = 0; c < Cout; ++c) {
+      const float sh = shift != nullptr ? shift[c] : 0.0f;
+      float t = scale != nullptr ? __builtin_fmaf(o[c], scale[c], sh) : o[c] + sh;
+      if (residual != nullptr) t = t + residual[r * Cout + c];
+      if (act == GD3D_ACT_RELU) t = t < 0.0f ? 0.0f : t;
+      o[c] = t;
+    }
+  }
+  return 0;
+}
+
 int gd3d_sparse_conv_backward_input_cpu(const float* grad_out, const float* weight, const int32_t* table, int32_t flip, int64_t N,
                                         int64_t R, int32_t K, int32_t Cin, int32_t Cout, float* grad_features) {
   const int rc = check_channels(K, Cin, Cout);

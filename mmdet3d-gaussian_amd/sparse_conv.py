@@ -11,7 +11,9 @@ gradient; three for the weight and bias gradients; no atomics, the bits replay),
 tensors go to the kernels on the current stream, CPU tensors to the library's `_cpu` twins.  By default fp32: another dtype is evaluated
 in fp32 and cast back.  `compute_dtype=torch.float16 / torch.bfloat16 / 'auto'` (a keyword of `sparse_conv`, of every layer and of every
 builder here) selects the mixed-precision form (csrc/sparse_conv_16.hip): 16-bit operands on the matrix cores, fp32
-accumulation, a 16-bit output, fp32 weight and bias gradients.  Dilation must be 1.
+accumulation, a 16-bit output, fp32 weight and bias gradients.  `scale=, shift=, residual=, activation=` on `sparse_conv`, and
+`fuse_sparse_conv_bn` / `SparseEncoder.fuse()` on the modules, put an eval BatchNorm, a block's residual add and the ReLU into the
+forward launch.  Dilation must be 1.
 """
 import ctypes
 import math
@@ -130,6 +132,26 @@ def _weight3(weight, who):
     return weight.reshape(-1, weight.size(-2), weight.size(-1))
 
 
+def _backward_entries(x, w, gy, nbr, nbr_t, num, subm, need_x, need_w, has_bias, dtype):
+    """the backward entries on contiguous operands of the kernels' types (dtype None: fp32) -> (gx, gw, gb) as the kernels wrote them,
+    None where not asked for"""
+    N, (K, Cin, Cout), R, dev = x.size(0), w.shape, nbr.size(0), x.device
+    suffix, code = ('', ()) if dtype is None else ('_16', (_DTYPE_CODES[dtype],))
+    ptr = _host.ptr_or_null
+    gx = gw = gb = None
+    if need_x:
+        gx = torch.empty((N, Cin), dtype=dtype or torch.float32, device=dev)
+        _host.call('gd3d_sparse_conv_backward_input' + suffix, dev,
+                   (ptr(gy), ptr(w), ptr(nbr if subm else nbr_t), int(subm), N, R, K, Cin, Cout, *code, ptr(gx)))
+    if need_w:
+        gw = torch.empty((K, Cin, Cout), dtype=torch.float32, device=dev)              # fp32 also on the 16-bit path: master weights get unrounded gradients
+        gb = torch.empty((Cout,), dtype=torch.float32, device=dev) if has_bias else None
+        work = _workspace(_weight_workspace_bytes(R, K, Cin, Cout), dev)
+        _host.call('gd3d_sparse_conv_backward_weight' + suffix, dev,
+                   (ptr(x), ptr(gy), ptr(nbr), ptr(num), N, R, K, Cin, Cout, *code, ptr(work), ptr(gw), ptr(gb)))
+    return gx, gw, gb
+
+
 class _SparseConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, weight, bias, nbr, nbr_t, num, subm):
@@ -148,24 +170,10 @@ class _SparseConv(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, w, nbr, nbr_t, num = ctx.saved_tensors
         subm, has_bias, x_dtype, w_dtype, b_dtype, w_shape = ctx.state
-        gy = _host.f32c(grad_out)
-        N, (K, Cin, Cout), R, dev = x.size(0), w.shape, nbr.size(0), x.device
-        ptr = _host.ptr_or_null
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty((N, Cin), dtype=torch.float32, device=dev)
-            _host.call('gd3d_sparse_conv_backward_input', dev,
-                       (ptr(gy), ptr(w), ptr(nbr if subm else nbr_t), int(subm), N, R, K, Cin, Cout, ptr(gx)))
-            gx = gx.to(x_dtype)
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            gw = torch.empty((K, Cin, Cout), dtype=torch.float32, device=dev)
-            gb = torch.empty((Cout,), dtype=torch.float32, device=dev) if has_bias else None
-            work = _workspace(_weight_workspace_bytes(R, K, Cin, Cout), dev)
-            _host.call('gd3d_sparse_conv_backward_weight', dev,
-                       (ptr(x), ptr(gy), ptr(nbr), ptr(num), N, R, K, Cin, Cout, ptr(work), ptr(gw), ptr(gb)))
-            gw = gw.to(w_dtype).reshape(w_shape)
-            gb = gb.to(b_dtype) if has_bias else None
-        return gx, gw, gb, None, None, None, None
+        gx, gw, gb = _backward_entries(x, w, _host.f32c(grad_out), nbr, nbr_t, num, subm, ctx.needs_input_grad[0],
+                                       ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]), has_bias, None)
+        return (None if gx is None else gx.to(x_dtype), None if gw is None else gw.to(w_dtype).reshape(w_shape),
+                None if gb is None else gb.to(b_dtype), None, None, None, None)
 
 
 _DTYPE_CODES = {torch.float16: 1, torch.bfloat16: 2}          # GD3D_DTYPE_F16, GD3D_DTYPE_BF16 (include/gd3d.h)
@@ -223,27 +231,82 @@ class _SparseConv16(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, w, nbr, nbr_t, num = ctx.saved_tensors
         subm, has_bias, x_dtype, w_dtype, b_dtype, w_shape, dtype = ctx.state
-        gy = _as16(grad_out, dtype)
+        gx, gw, gb = _backward_entries(x, w, _as16(grad_out, dtype), nbr, nbr_t, num, subm, ctx.needs_input_grad[0],
+                                       ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]), has_bias, dtype)
+        return (None if gx is None else gx.to(x_dtype), None if gw is None else gw.to(w_dtype).reshape(w_shape),
+                None if gb is None else gb.to(b_dtype), None, None, None, None, None)
+
+
+_ACT_CODES = {None: 0, 'relu': 1}                             # GD3D_ACT_NONE, GD3D_ACT_RELU (include/gd3d.h)
+
+
+class _SparseConvFused(torch.autograd.Function):
+    """conv -> * scale + shift -> + residual -> ReLU in ONE forward launch (gd3d_sparse_conv_forward_fused[_16]).
+    dtype None: fp32 operands; torch.float16 / torch.bfloat16: 16-bit features, weight, residual and output, fp32 scale and shift.
+    Differentiable w.r.t. features, weight, bias and residual; scale and shift are constants (a frozen BatchNorm)."""
+
+    @staticmethod
+    def forward(ctx, features, weight, bias, residual, scale, shift, nbr, nbr_t, num, subm, activation, dtype):
+        cast = _host.f32c if dtype is None else (lambda t: _as16(t, dtype))
+        x, w = cast(features), cast(weight)
+        res = None if residual is None else cast(residual)
+        sc = None if scale is None else _host.f32c(scale)
+        sh = None if shift is None else _host.f32c(shift)
+        if bias is not None:                                                           # the conv's own bias, folded on the host: shift' = bias * scale + shift
+            b = _host.f32c(bias)
+            b = b if sc is None else b * sc
+            sh = b if sh is None else b + sh
         N, (K, Cin, Cout), R, dev = x.size(0), w.shape, nbr.size(0), x.device
-        code, ptr = _DTYPE_CODES[dtype], _host.ptr_or_null
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty((N, Cin), dtype=dtype, device=dev)
-            _host.call('gd3d_sparse_conv_backward_input_16', dev,
-                       (ptr(gy), ptr(w), ptr(nbr if subm else nbr_t), int(subm), N, R, K, Cin, Cout, code, ptr(gx)))
-            gx = gx.to(x_dtype)
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            gw = torch.empty((K, Cin, Cout), dtype=torch.float32, device=dev)          # fp32 out of the kernel: master weights get unrounded gradients
-            gb = torch.empty((Cout,), dtype=torch.float32, device=dev) if has_bias else None
-            work = _workspace(_weight_workspace_bytes(R, K, Cin, Cout), dev)
-            _host.call('gd3d_sparse_conv_backward_weight_16', dev,
-                       (ptr(x), ptr(gy), ptr(nbr), ptr(num), N, R, K, Cin, Cout, code, ptr(work), ptr(gw), ptr(gb)))
-            gw = gw.to(w_dtype).reshape(w_shape)
-            gb = gb.to(b_dtype) if has_bias else None
-        return gx, gw, gb, None, None, None, None, None
+        out = torch.empty((R, Cout), dtype=dtype or torch.float32, device=dev)
+        ptr = _host.ptr_or_null
+        code = () if dtype is None else (_DTYPE_CODES[dtype],)
+        _host.call('gd3d_sparse_conv_forward_fused' if dtype is None else 'gd3d_sparse_conv_forward_fused_16', dev,
+                   (ptr(x), ptr(w), ptr(sc), ptr(sh), ptr(res), ptr(nbr), ptr(num), N, R, K, Cin, Cout, _ACT_CODES[activation], *code, ptr(out)))
+        ctx.save_for_backward(x, w, nbr, nbr_t, num, sc, out if activation == 'relu' else None)
+        ctx.state = (subm, bias is not None, features.dtype, weight.dtype, None if bias is None else bias.dtype,
+                     None if residual is None else residual.dtype, weight.shape, dtype)
+        return out if dtype is not None or features.dtype == torch.float32 else out.to(features.dtype)
+
+    @staticmethod
+    @_host.guard_double_backward
+    def backward(ctx, grad_out):
+        x, w, nbr, nbr_t, num, sc, out = ctx.saved_tensors
+        subm, has_bias, x_dtype, w_dtype, b_dtype, r_dtype, w_shape, dtype = ctx.state
+        g = grad_out if dtype is not None else _host.f32c(grad_out)
+        if out is not None:
+            g = g * (out > 0)                                                          # the ReLU's gradient, exact
+        gres = g.to(r_dtype) if r_dtype is not None and ctx.needs_input_grad[3] else None
+        gy = g if sc is None else g.float() * sc                                       # what reaches the convolution: the existing backward entries run on it
+        gy = _host.f32c(gy) if dtype is None else _as16(gy, dtype)
+        gx, gw, gb = _backward_entries(x, w, gy, nbr, nbr_t, num, subm, ctx.needs_input_grad[0],
+                                       ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]), has_bias, dtype)
+        gx = None if gx is None else gx.to(x_dtype)
+        gw = None if gw is None else gw.to(w_dtype).reshape(w_shape)
+        gb = None if gb is None else gb.to(b_dtype)
+        return gx, gw, gb, gres, None, None, None, None, None, None, None, None
 
 
-def sparse_conv(features, weight, bias, index, compute_dtype=None):
+def _check_fused_operands(scale, shift, residual, activation, features, Cout, R):
+    if activation not in _ACT_CODES:
+        raise RuntimeError(f"sparse_conv: activation must be None or 'relu', got {activation!r}")
+    for name, t in (('scale', scale), ('shift', shift)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.shape != (Cout,) or not t.dtype.is_floating_point:
+            raise RuntimeError(f'shape mismatch: sparse_conv: {name} must be a floating-point ({Cout},) tensor, got {tuple(getattr(t, "shape", ()))}')
+        if t.requires_grad:
+            raise RuntimeError(f'sparse_conv: {name} is a constant of the fused layer (a frozen BatchNorm) and must not require grad')
+        if t.device != features.device:
+            raise RuntimeError(f'sparse_conv: {name} is on {t.device}, features on {features.device}')
+    if residual is not None:
+        if not isinstance(residual, torch.Tensor) or residual.shape != (R, Cout) or not residual.dtype.is_floating_point:
+            raise RuntimeError(f'shape mismatch: sparse_conv: residual must be a floating-point ({R}, {Cout}) tensor, got '
+                               f'{tuple(getattr(residual, "shape", ()))}')
+        if residual.device != features.device:
+            raise RuntimeError(f'sparse_conv: residual is on {residual.device}, features on {features.device}')
+
+
+def sparse_conv(features, weight, bias, index, compute_dtype=None, *, scale=None, shift=None, residual=None, activation=None):
     """One sparse convolution layer over the tables of `sparse_conv_index` -> (R, Cout), differentiable w.r.t. features, weight, bias.
 
     out[o] = sum over the offsets j with index.nbr[o, j] >= 0 of features[nbr[o, j]] @ weight[j] (+ bias); weight is spconv 1.x's
@@ -256,7 +319,15 @@ def sparse_conv(features, weight, bias, index, compute_dtype=None):
     features and weight are cast to it (nothing is done where they already are), the bias stays fp32, the products are accumulated in fp32 on
     the matrix cores and rounded once; the output comes back in compute_dtype, grad_features in the features' dtype, and the weight and
     bias gradients are computed in fp32 and cast to the parameters' dtypes.  'auto': the features' dtype if it is one of the two, else the
-    autocast dtype where autocast is enabled for the features' device, else None."""
+    autocast dtype where autocast is enabled for the features' device, else None.
+
+    scale, shift, residual, activation (keyword-only): the fused layer — ONE forward launch evaluates
+    act((conv + bias) * scale + shift + residual) on the rows that have a valid neighbour and writes zero to every other row, whatever
+    shift and residual hold.  scale, shift: (Cout,) constants (an eval BatchNorm folded: `fuse_sparse_conv_bn`), kept in fp32; a tensor that
+    requires grad raises.  residual: (R, Cout), the identity of a basic block.  activation: None or 'relu'.  The conv's own bias is folded on
+    the host, shift' = bias * scale + shift, and each output element is one fixed fp32 sequence — fmaf(acc, scale, shift'), + residual, the
+    ReLU — rounded once on the 16-bit path.  Differentiable w.r.t. features, weight, bias and residual: g = grad_out * (out > 0) under the
+    ReLU, grad_residual = g, and the backward launches above run on g * scale.  With all four None the call is the one it always was."""
     if not isinstance(index, SparseConvIndex):
         raise RuntimeError('sparse_conv: index must be the record sparse_conv_index returns')
     w = _weight3(weight, 'sparse_conv')
@@ -274,6 +345,9 @@ def sparse_conv(features, weight, bias, index, compute_dtype=None):
         if t is not None and t.device != features.device:
             raise RuntimeError(f'sparse_conv: {name} is on {t.device}, features on {features.device}')
     dtype = _resolve_compute_dtype(compute_dtype, features)
+    if scale is not None or shift is not None or residual is not None or activation is not None:
+        _check_fused_operands(scale, shift, residual, activation, features, Cout, index.nbr.size(0))
+        return _SparseConvFused.apply(features, w, bias, residual, scale, shift, index.nbr, index.nbr_t, index.num, index.subm, activation, dtype)
     if dtype is not None:
         return _SparseConv16.apply(features, w, bias, index.nbr, index.nbr_t, index.num, index.subm, dtype)
     return _SparseConv.apply(features, w, bias, index.nbr, index.nbr_t, index.num, index.subm)
@@ -395,7 +469,8 @@ class SparseConvolution(SparseModule):
     def build_index(self, x):
         return sparse_conv_index(x.indices, x.spatial_shape, x.batch_size, self.kernel_size, self.stride, self.padding, self.subm, self.max_out)
 
-    def forward(self, x):
+    def index_of(self, x):
+        """the index of this layer over x's rows: the one stored under `indice_key`, or a new one (stored under the key)"""
         if not isinstance(x, SparseConvTensor):
             raise RuntimeError(f'{type(self).__name__} takes a SparseConvTensor, got {type(x).__name__}')
         index = x.find_indice_pair(self.indice_key)
@@ -406,10 +481,17 @@ class SparseConvolution(SparseModule):
             index = self.build_index(x)
             if self.indice_key is not None:
                 x.indice_dict[self.indice_key] = index
-        out = SparseConvTensor(sparse_conv(x.features, self.weight, self.bias, index, self.compute_dtype),
-                               x.indices if self.subm else index.out_coors, index.out_shape, x.batch_size, x.grid)
+        return index
+
+    def output_of(self, x, index, features):
+        """the layer's output tensor: `features` on the output rows of `index`, x's lineage"""
+        out = SparseConvTensor(features, x.indices if self.subm else index.out_coors, index.out_shape, x.batch_size, x.grid)
         out.indice_dict = x.indice_dict
         return out
+
+    def forward(self, x):
+        index = self.index_of(x)
+        return self.output_of(x, index, sparse_conv(x.features, self.weight, self.bias, index, self.compute_dtype))
 
     def extra_repr(self):
         return (f'{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, '
@@ -536,6 +618,111 @@ def make_sparse_convmodule(in_channels, out_channels, kernel_size, indice_key, s
     return SparseSequential(*layers)
 
 
+# ---- conv + BatchNorm + residual + ReLU in one launch ----------------------------------------------------------------
+
+def _fold_batchnorm(bn):
+    """an eval-mode BatchNorm1d as y = x * scale + shift -> (scale, shift), computed in fp64 and kept in fp32"""
+    if not isinstance(bn, nn.BatchNorm1d):
+        raise RuntimeError(f'fuse_sparse_conv_bn: only BatchNorm1d is folded, got {type(bn).__name__}')
+    if bn.training:
+        raise RuntimeError('fuse_sparse_conv_bn: a BatchNorm in training mode normalises by batch statistics and cannot be folded; call .eval() first')
+    if bn.running_mean is None or bn.running_var is None:
+        raise RuntimeError('fuse_sparse_conv_bn: a BatchNorm without running statistics (track_running_stats=False) cannot be folded')
+    mean, var = bn.running_mean.detach().double(), bn.running_var.detach().double()
+    gamma = torch.ones_like(var) if bn.weight is None else bn.weight.detach().double()
+    beta = torch.zeros_like(var) if bn.bias is None else bn.bias.detach().double()
+    scale = gamma / torch.sqrt(var + bn.eps)
+    return scale.float(), (beta - mean * scale).float()
+
+
+class FusedSparseConv(SparseModule):
+    """A `SubMConv3d` / `SparseConv3d` with the eval BatchNorm1d and / or the ReLU that followed it, evaluated in ONE launch
+    (`sparse_conv(..., scale, shift, residual, activation)`).  `conv` is the layer itself: its parameters, `indice_key`, `max_out` and
+    `compute_dtype` are shared, not copied.  scale, shift: fp32 buffers (None without a BatchNorm).  forward(x, residual=None)."""
+
+    def __init__(self, conv, norm=None, activation=None):
+        super().__init__()
+        if not isinstance(conv, SparseConvolution):
+            raise RuntimeError(f'FusedSparseConv: conv must be a SubMConv3d or a SparseConv3d, got {type(conv).__name__}')
+        if activation not in _ACT_CODES:
+            raise RuntimeError(f"FusedSparseConv: activation must be None or 'relu', got {activation!r}")
+        scale, shift = (None, None) if norm is None else _fold_batchnorm(norm)
+        if scale is not None and scale.numel() != conv.out_channels:
+            raise RuntimeError(f'FusedSparseConv: the BatchNorm has {scale.numel()} features, the convolution {conv.out_channels} output channels')
+        self.conv = conv
+        self.register_buffer('scale', None if scale is None else scale.to(conv.weight.device))
+        self.register_buffer('shift', None if shift is None else shift.to(conv.weight.device))
+        self.activation = activation
+
+    indice_key = property(lambda self: self.conv.indice_key)
+    max_out = property(lambda self: self.conv.max_out)
+    compute_dtype = property(lambda self: self.conv.compute_dtype)
+
+    def forward(self, x, residual=None):
+        conv = self.conv
+        index = conv.index_of(x)
+        return conv.output_of(x, index, sparse_conv(x.features, conv.weight, conv.bias, index, conv.compute_dtype, scale=self.scale, shift=self.shift,
+                                                    residual=residual, activation=self.activation))
+
+    def extra_repr(self):
+        return (f'norm={self.scale is not None}, activation={self.activation!r}, indice_key={self.indice_key!r}, max_out={self.max_out!r}'
+                + ('' if self.compute_dtype is None else f', compute_dtype={self.compute_dtype!r}'))
+
+
+class FusedSparseBasicBlock(SparseModule):
+    """A `SparseBasicBlock` in two launches: conv1 + norm1 + relu, then conv2 + norm2 + identity + relu.  A `downsample` is evaluated first."""
+
+    def __init__(self, block):
+        super().__init__()
+        if not isinstance(block, SparseBasicBlock):
+            raise RuntimeError(f'FusedSparseBasicBlock: block must be a SparseBasicBlock, got {type(block).__name__}')
+        self.conv1 = FusedSparseConv(block.conv1, block.norm1, 'relu')
+        self.conv2 = FusedSparseConv(block.conv2, block.norm2, 'relu')
+        self.downsample = None if block.downsample is None else fuse_sparse_conv_bn(block.downsample)
+
+    def forward(self, x):
+        identity = x.features
+        if self.downsample is not None:
+            identity = self.downsample(x)
+        return self.conv2(self.conv1(x), residual=getattr(identity, 'features', identity))
+
+
+def _fuse_sequential(seq):
+    """in place: every conv of `seq` that is followed by an eval BatchNorm1d and / or an nn.ReLU becomes one FusedSparseConv under the
+    conv's name; a conv that nothing follows (a pre-activation order) stays"""
+    items, fused, i = list(seq._modules.items()), OrderedDict(), 0
+    while i < len(items):
+        name, module = items[i]
+        i += 1
+        if type(module) in (SubMConv3d, SparseConv3d, SparseConvolution):
+            norm = act = None
+            if i < len(items) and isinstance(items[i][1], nn.modules.batchnorm._BatchNorm):
+                norm, i = items[i][1], i + 1
+            if i < len(items) and isinstance(items[i][1], nn.ReLU):
+                act, i = 'relu', i + 1
+            if norm is not None or act is not None:
+                module = FusedSparseConv(module, norm, act)
+        fused[name] = module
+    seq._modules = fused
+
+
+def fuse_sparse_conv_bn(module):
+    """mmcv's `fuse_conv_bn` for the sparse encoder: in place, and returns the module (a `SparseBasicBlock` handed in directly comes back
+    as its fused replacement).  Inside every `SparseSequential` a `SubMConv3d` / `SparseConv3d` followed by an eval-mode `BatchNorm1d` and / or
+    an `nn.ReLU` becomes a `FusedSparseConv`; every `SparseBasicBlock` becomes a `FusedSparseBasicBlock`.  scale = gamma / sqrt(running_var
+    + eps) and shift = beta - running_mean * scale are computed in fp64 and held as fp32 buffers (affine=False: gamma = 1, beta = 0).  A
+    BatchNorm in training mode, or one without running statistics, raises.  For inference and frozen-BN fine-tuning: the fused layers stay
+    differentiable w.r.t. the conv's parameters and their input.  In the static `max_out` form the rows past the count come out zero, as
+    `sparse_conv` promises, where the unfused BatchNorm turned them into `shift`."""
+    if isinstance(module, SparseBasicBlock):
+        return FusedSparseBasicBlock(module)
+    for name, child in list(module.named_children()):
+        module._modules[name] = fuse_sparse_conv_bn(child)
+    if isinstance(module, SparseSequential):
+        _fuse_sequential(module)
+    return module
+
+
 class SparseEncoder(nn.Module):
     """mmdet3d 0.x's `SparseEncoder`, restated from its published sparse_encoder.py (absent from the reference tree: not pinned):
     CenterPoint's `pts_middle_encoder` (configs/_base_/models/centerpoint_01voxel_second_secfpn_nus.py:10-19).  forward returns
@@ -599,6 +786,10 @@ class SparseEncoder(nn.Module):
 
     def forward(self, voxel_features, coors, batch_size):
         return self.encode(voxel_features, coors, batch_size)[1]
+
+    def fuse(self):
+        """`fuse_sparse_conv_bn` on this encoder (in eval mode): every conv -> BatchNorm1d -> ReLU and every basic block in fused launches"""
+        return fuse_sparse_conv_bn(self)
 
 
 class MlvlSparseEncoder(SparseEncoder):
