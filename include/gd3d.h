@@ -1420,6 +1420,51 @@ int gd3d_sparse_conv_forward_fused_16_cpu(const void* features, const void* weig
                                           const void* residual, const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K,
                                           int32_t Cin, int32_t Cout, int32_t act, int32_t dtype, void* out);
 
+/* ------------------------------------------------------------------------------------
+ * Batch normalisation over the LIVE rows of a sparse tensor, with the residual add and the ReLU of a basic block in the same pass (an
+ * addition inside ABI 6; csrc/sparse_bn.hip, csrc/sparse_bn_common.h).  features, residual (nullable), out, grad_out,
+ * grad_features, grad_residual (nullable): (R, C) in `dtype` — 0: fp32, GD3D_DTYPE_F16, GD3D_DTYPE_BF16 (widened on load, rounded to
+ * nearest even once on store); every statistic, weight, bias and parameter gradient is fp32 (C).  coors (R, 4) int32 [b, z, y, x]: row i is
+ * LIVE when all four entries are >= 0, b < B and (z, y, x) lies inside (D, H, W) — gd3d_sparse_conv_index's rule, read on the device;
+ * n is the number of live rows, never read back.  1 <= C <= 256 (GD3D_E_TOOLARGE above), R < 2^31; act: GD3D_ACT_NONE / GD3D_ACT_RELU.
+ * gd3d_sparse_bn_forward, training != 0: per channel mean and biased var over the live rows (per-tile mean and centred sums merged by
+ *   Chan's formula in ascending tile order; never E[x^2] - E[x]^2), invstd = 1 / sqrt(var + eps), written to save_mean / save_invstd;
+ *     out = act((x - mean) * (invstd * weight) + bias + residual)   on live rows (weight NULL: 1, bias NULL: 0),
+ *     out = 0                                                         on dead rows, whatever features and residual hold there (a select).
+ *   When n >= 2 and the pointer is not NULL: running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with
+ *   var n / (n - 1), *num_batches_tracked += 1 — written by the finishing launch.  n < 2 leaves the three untouched (n = 0: out is all zero;
+ *   n = 1: out = act(bias + residual) on the live row).  At most 3 launches, `workspace` of gd3d_sparse_bn_workspace_bytes(R, C) bytes.
+ *   training == 0: out = act(x * scale + shift + residual) on live rows, scale = weight / sqrt(running_var + eps), shift = bias -
+ *   running_mean * scale; 0 on dead rows; ONE launch; nothing else is written, workspace and save_* may be NULL.
+ *   residual must not share a byte with out (GD3D_E_BADARG).  R == 0: save_mean = 0, save_invstd = 1 / sqrt(eps), nothing else.
+ * gd3d_sparse_bn_backward: g = grad_out where the row is live and (act == GD3D_ACT_RELU) the saved `out` is > 0, else 0.
+ *   grad_residual = g; grad_bias = sum g; grad_weight = sum g xhat, xhat = (x - mean) * invstd (each nullable);
+ *   training != 0 (mean, invstd_or_var = save_mean, save_invstd): grad_features = weight invstd (g - sum g / n - xhat sum(g xhat) / n);
+ *   training == 0 (mean, invstd_or_var = running_mean, running_var; a frozen BatchNorm): grad_features = g scale.
+ *   Dead rows of grad_features and grad_residual are zero.  At most 3 launches (one in eval without parameter gradients).
+ * No atomics, and the order of every sum depends on (R, C) and dtype alone: the same bits from run to run and under graph replay,
+ * whatever the dead rows hold.  An operand whose base is 16-byte aligned, with C % 4 == 0 (fp32) or C % 8 == 0 (16 bits), is read and
+ * written 16 bytes a lane; anything else element by element, with the same bits.
+ * `_cpu` twins (csrc/sparse_bn_cpu.cpp): the same element sequences; the sums in fp64 per tile, rounded once — the tests' bound, not the bit.
+ * ---------------------------------------------------------------------------------- */
+size_t gd3d_sparse_bn_workspace_bytes(int64_t R, int32_t C);
+int gd3d_sparse_bn_forward(const void* features, const int32_t* coors, const void* residual, const float* weight, const float* bias,
+                           float* running_mean, float* running_var, int64_t* num_batches_tracked, int64_t R, int32_t C, int32_t B, int32_t D,
+                           int32_t H, int32_t W, int32_t training, float momentum, float eps, int32_t act, int32_t dtype, void* workspace,
+                           void* out, float* save_mean, float* save_invstd, void* stream);
+int gd3d_sparse_bn_backward(const void* grad_out, const void* features, const void* out, const int32_t* coors, const float* weight,
+                            const float* mean, const float* invstd_or_var, int64_t R, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W,
+                            int32_t training, float eps, int32_t act, int32_t dtype, void* workspace, void* grad_features, void* grad_residual,
+                            float* grad_weight, float* grad_bias, void* stream);
+int gd3d_sparse_bn_forward_cpu(const void* features, const int32_t* coors, const void* residual, const float* weight, const float* bias,
+                               float* running_mean, float* running_var, int64_t* num_batches_tracked, int64_t R, int32_t C, int32_t B,
+                               int32_t D, int32_t H, int32_t W, int32_t training, float momentum, float eps, int32_t act, int32_t dtype,
+                               void* workspace, void* out, float* save_mean, float* save_invstd);
+int gd3d_sparse_bn_backward_cpu(const void* grad_out, const void* features, const void* out, const int32_t* coors, const float* weight,
+                                const float* mean, const float* invstd_or_var, int64_t R, int32_t C, int32_t B, int32_t D, int32_t H,
+                                int32_t W, int32_t training, float eps, int32_t act, int32_t dtype, void* workspace, void* grad_features,
+                                void* grad_residual, float* grad_weight, float* grad_bias);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

@@ -41,6 +41,9 @@
   * ``fuse_sparse_conv_bn`` / ``FusedSparseConv`` / ``FusedSparseBasicBlock`` / ``SparseEncoder.fuse()`` — the eval BatchNorm, the residual
                                  add and the ReLU of a sparse layer inside the convolution's launch (``sparse_conv(..., scale=, shift=,
                                  residual=, activation=)``): one fixed fp32 sequence per element, one rounding on the 16-bit path
+  * ``sparse_batch_norm`` / ``SparseBatchNorm1d`` / ``SparseNormBasicBlock`` / ``convert_sparse_batchnorm`` / ``SparseEncoder.convert_norm()``
+                               — batch normalisation over the LIVE rows of a sparse tensor with the residual add and the ReLU in the same
+                                 pass, training and eval, forward and backward: what training in the static ``max_out`` form needs
   * ``GraphedStep``            — a launch-bound loss slice, forward and backward, captured once as a hipGraph and replayed
 Everything outside §8 that earlier rounds built (frozen, DESIGN_EXTRAS.md) lives in ``mmdet3d_gaussian_amd.extras``.
 
@@ -72,6 +75,7 @@ from .voxelize import HardSimpleVFE, Voxelization, dynamic_voxelize, hard_voxeli
 from .pillar_feat import PillarFeatureDecorator, PointVoxelStatsCalculator, pillar_decorate, point_voxel_stats
 from .view_net import PointPillarsScatter, multi_view_voxelize, pillar_scatter, to_cylindrical, to_spherical, view_sample
 from .simota import Point3DRangeGenerator, SimOTABEVAssigner, simota_assign
+from .sparse_bn import SparseBatchNorm1d, SparseNormBasicBlock, convert_sparse_batchnorm, sparse_batch_norm
 from .sparse_conv import (FusedSparseBasicBlock, FusedSparseConv, MlvlSparseEncoder, SparseBasicBlock, SparseConv3d, SparseConvIndex, SparseConvTensor, SparseEncoder, SparseModule,
                           SparseSequential, SubMConv3d, fuse_sparse_conv_bn, make_sparse_convmodule, sparse_conv, sparse_conv_index, sparse_to_dense)
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
@@ -101,4 +105,5 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'pillar_decorate', 'PillarFeatureDecorator', 'multi_view_voxelize', 'to_cylindrical', 'to_spherical', 'pillar_scatter',
            'PointPillarsScatter', 'view_sample', 'simota_assign', 'SimOTABEVAssigner', 'Point3DRangeGenerator', 'sparse_conv_index', 'sparse_conv',
            'sparse_to_dense', 'SparseConvIndex', 'SparseConvTensor', 'SparseModule', 'SubMConv3d', 'SparseConv3d', 'SparseSequential', 'SparseBasicBlock',
-           'make_sparse_convmodule', 'SparseEncoder', 'MlvlSparseEncoder', 'fuse_sparse_conv_bn', 'FusedSparseConv', 'FusedSparseBasicBlock', 'extras']
+           'make_sparse_convmodule', 'SparseEncoder', 'MlvlSparseEncoder', 'fuse_sparse_conv_bn', 'FusedSparseConv', 'FusedSparseBasicBlock', 'sparse_batch_norm',
+           'SparseBatchNorm1d', 'SparseNormBasicBlock', 'convert_sparse_batchnorm', 'extras']

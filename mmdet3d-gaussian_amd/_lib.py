@@ -345,6 +345,12 @@ SYMBOLS = {
     'gd3d_sparse_conv_forward_fused_16': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     'gd3d_sparse_conv_forward_fused_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     'gd3d_sparse_conv_forward_fused_16_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    # batch normalisation over the live rows of a sparse tensor (csrc/sparse_bn.hip)
+    'gd3d_sparse_bn_workspace_bytes': (_sz, [_i64, _i32]),
+    'gd3d_sparse_bn_forward': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_sparse_bn_backward': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_sparse_bn_forward_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'gd3d_sparse_bn_backward_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 

@@ -698,7 +698,9 @@ def _fuse_sequential(seq):
             norm = act = None
             if i < len(items) and isinstance(items[i][1], nn.modules.batchnorm._BatchNorm):
                 norm, i = items[i][1], i + 1
-            if i < len(items) and isinstance(items[i][1], nn.ReLU):
+                if getattr(norm, 'activation', None) == 'relu':                        # a SparseBatchNorm1d carries its ReLU (sparse_bn.py)
+                    act = 'relu'
+            if act is None and i < len(items) and isinstance(items[i][1], nn.ReLU):
                 act, i = 'relu', i + 1
             if norm is not None or act is not None:
                 module = FusedSparseConv(module, norm, act)
@@ -713,7 +715,9 @@ def fuse_sparse_conv_bn(module):
     + eps) and shift = beta - running_mean * scale are computed in fp64 and held as fp32 buffers (affine=False: gamma = 1, beta = 0).  A
     BatchNorm in training mode, or one without running statistics, raises.  For inference and frozen-BN fine-tuning: the fused layers stay
     differentiable w.r.t. the conv's parameters and their input.  In the static `max_out` form the rows past the count come out zero, as
-    `sparse_conv` promises, where the unfused BatchNorm turned them into `shift`."""
+    `sparse_conv` promises, where the unfused BatchNorm turned them into `shift`.  An eval `SparseBatchNorm1d` (sparse_bn.py) folds as a
+    `BatchNorm1d` does and its `activation` is carried into the `FusedSparseConv`; a converted basic block fuses to the same
+    `FusedSparseBasicBlock`."""
     if isinstance(module, SparseBasicBlock):
         return FusedSparseBasicBlock(module)
     for name, child in list(module.named_children()):
@@ -790,6 +794,12 @@ class SparseEncoder(nn.Module):
     def fuse(self):
         """`fuse_sparse_conv_bn` on this encoder (in eval mode): every conv -> BatchNorm1d -> ReLU and every basic block in fused launches"""
         return fuse_sparse_conv_bn(self)
+
+    def convert_norm(self):
+        """`convert_sparse_batchnorm` on this encoder (opt-in, in place): every BatchNorm1d (+ ReLU) and every basic block on the live-row
+        `SparseBatchNorm1d` — what training in the static form needs; `.eval().fuse()` still works afterwards"""
+        from .sparse_bn import convert_sparse_batchnorm
+        return convert_sparse_batchnorm(self)
 
 
 class MlvlSparseEncoder(SparseEncoder):
