@@ -1465,6 +1465,33 @@ int gd3d_sparse_bn_backward_cpu(const void* grad_out, const void* features, cons
                                 int32_t W, int32_t training, float eps, int32_t act, int32_t dtype, void* workspace, void* grad_features,
                                 void* grad_residual, float* grad_weight, float* grad_bias);
 
+/* ------------------------------------------------------------------------------------
+ * Max pooling over the tables of gd3d_sparse_conv_index (spconv 1.x's SparseMaxPool3d; an addition inside ABI 6; csrc/sparse_pool.hip,
+ * csrc/sparse_pool_common.h).  features, grad_features: (N, C); out, grad_out: (R, C), all in `dtype` — 0: fp32,
+ * GD3D_DTYPE_F16, GD3D_DTYPE_BF16.  nbr (R, K), nbr_t (N, K) int32: the tables of a strided (not submanifold) index.  1 <= C <= 256,
+ * 1 <= K <= 27 (GD3D_E_TOOLARGE above), N, R < 2^31.
+ * gd3d_sparse_max_pool_forward: out[o, c] = max over the offsets j with 0 <= nbr[o, j] < N of features[nbr[o, j], c].  Every row is
+ *   written; a row at or past num[0] (num nullable: every row counts) and a row without a valid neighbour are ZERO, not -inf.  The
+ *   comparison is written out — a candidate replaces the maximum when it is greater or is a NaN — so a NaN in the window gives NaN
+ *   (torch's max_pool3d rule; fmaxf would drop it) and a window of -inf gives -inf.  The output element is a COPY of an input element: no
+ *   rounding in any type.
+ * gd3d_sparse_max_pool_backward: grad_features[i, c] = the sum, in ascending j, over the offsets with o = nbr_t[i, j] in [0, R) and
+ *   features[i, c] == out[o, c] of grad_out[o, c] — spconv 1.x's equality rule: EVERY tied input of a window receives the gradient; a NaN
+ *   window compares unequal and passes none.  The sum is accumulated in fp32 and rounded once to a 16-bit dtype.  Every row is written;
+ *   an inactive row, and one whose outputs were all dropped, is zero.
+ * One launch each way, a gather in both directions: no atomics, the same bits from run to run and under graph replay.  An operand whose
+ * base is 16-byte aligned, with C % 4 == 0 (fp32) or C % 8 == 0 (16 bits), is read and written 16 bytes a lane; anything else element by
+ * element, with the same bits.  `_cpu` twins (csrc/sparse_pool_cpu.cpp): the same sequence per element, the same bits.
+ * ---------------------------------------------------------------------------------- */
+int gd3d_sparse_max_pool_forward(const void* features, const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K, int32_t C,
+                                 int32_t dtype, void* out, void* stream);
+int gd3d_sparse_max_pool_backward(const void* grad_out, const void* features, const void* out, const int32_t* nbr_t, int64_t N, int64_t R,
+                                  int32_t K, int32_t C, int32_t dtype, void* grad_features, void* stream);
+int gd3d_sparse_max_pool_forward_cpu(const void* features, const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K,
+                                     int32_t C, int32_t dtype, void* out);
+int gd3d_sparse_max_pool_backward_cpu(const void* grad_out, const void* features, const void* out, const int32_t* nbr_t, int64_t N,
+                                      int64_t R, int32_t K, int32_t C, int32_t dtype, void* grad_features);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

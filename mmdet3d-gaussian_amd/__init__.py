@@ -44,6 +44,11 @@
   * ``sparse_batch_norm`` / ``SparseBatchNorm1d`` / ``SparseNormBasicBlock`` / ``convert_sparse_batchnorm`` / ``SparseEncoder.convert_norm()``
                                — batch normalisation over the LIVE rows of a sparse tensor with the residual add and the ReLU in the same
                                  pass, training and eval, forward and backward: what training in the static ``max_out`` form needs
+  * ``sparse_inverse_conv`` / ``sparse_conv_index_inverse`` / ``SparseInverseConv3d`` / ``make_sparse_inverse_convmodule`` / ``sparse_max_pool`` /
+    ``SparseMaxPool3d`` / ``ToDense`` / ``SparseUNet`` — the way back up: spconv 1.x's inverse convolution as the existing launches over the
+                                 swapped tables of the strided layer it undoes, max pooling over the same tables (one gather launch
+                                 each way, the output a copy of an input element, ties share the gradient), and mmdet3d's sparse U-Net
+                                 middle encoder with per-voxel ``seg_features``
   * ``GraphedStep``            — a launch-bound loss slice, forward and backward, captured once as a hipGraph and replayed
 Everything outside §8 that earlier rounds built (frozen, DESIGN_EXTRAS.md) lives in ``mmdet3d_gaussian_amd.extras``.
 
@@ -78,6 +83,8 @@ from .simota import Point3DRangeGenerator, SimOTABEVAssigner, simota_assign
 from .sparse_bn import SparseBatchNorm1d, SparseNormBasicBlock, convert_sparse_batchnorm, sparse_batch_norm
 from .sparse_conv import (FusedSparseBasicBlock, FusedSparseConv, MlvlSparseEncoder, SparseBasicBlock, SparseConv3d, SparseConvIndex, SparseConvTensor, SparseEncoder, SparseModule,
                           SparseSequential, SubMConv3d, fuse_sparse_conv_bn, make_sparse_convmodule, sparse_conv, sparse_conv_index, sparse_to_dense)
+from .sparse_conv import SparseInverseConv3d, SparseUNet, ToDense, make_sparse_inverse_convmodule, sparse_conv_index_inverse, sparse_inverse_conv
+from .sparse_pool import SparseMaxPool3d, sparse_max_pool
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
                         anchor_head_decoded_loss_fused, center_head_gd_loss, center_head_losses)
 from . import extras
@@ -106,4 +113,5 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'PointPillarsScatter', 'view_sample', 'simota_assign', 'SimOTABEVAssigner', 'Point3DRangeGenerator', 'sparse_conv_index', 'sparse_conv',
            'sparse_to_dense', 'SparseConvIndex', 'SparseConvTensor', 'SparseModule', 'SubMConv3d', 'SparseConv3d', 'SparseSequential', 'SparseBasicBlock',
            'make_sparse_convmodule', 'SparseEncoder', 'MlvlSparseEncoder', 'fuse_sparse_conv_bn', 'FusedSparseConv', 'FusedSparseBasicBlock', 'sparse_batch_norm',
-           'SparseBatchNorm1d', 'SparseNormBasicBlock', 'convert_sparse_batchnorm', 'extras']
+           'SparseBatchNorm1d', 'SparseNormBasicBlock', 'convert_sparse_batchnorm', 'sparse_conv_index_inverse', 'sparse_inverse_conv', 'SparseInverseConv3d',
+           'make_sparse_inverse_convmodule', 'sparse_max_pool', 'SparseMaxPool3d', 'ToDense', 'SparseUNet', 'extras']

@@ -351,6 +351,11 @@ SYMBOLS = {
     'gd3d_sparse_bn_backward': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gd3d_sparse_bn_forward_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'gd3d_sparse_bn_backward_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    # max pooling over the tables of a sparse convolution index (csrc/sparse_pool.hip)
+    'gd3d_sparse_max_pool_forward': (_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    'gd3d_sparse_max_pool_backward': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    'gd3d_sparse_max_pool_forward_cpu': (_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    'gd3d_sparse_max_pool_backward_cpu': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 

@@ -14,6 +14,12 @@ builder here) selects the mixed-precision form (csrc/sparse_conv_16.hip, DESIGN.
 accumulation, a 16-bit output, fp32 weight and bias gradients.  `scale=, shift=, residual=, activation=` on `sparse_conv`, and
 `fuse_sparse_conv_bn` / `SparseEncoder.fuse()` on the modules, put an eval BatchNorm, a block's residual add and the ReLU into the
 forward launch.  Dilation must be 1.
+
+The way back up: `sparse_conv_index` keeps the rows it was built over (`in_coors`, `in_shape`), and
+`sparse_conv_index_inverse` hands the same tables back with the roles swapped, so `sparse_inverse_conv` / `SparseInverseConv3d` (spconv 1.x's
+inverse convolution) are the launches above over `nbr_t` — no new kernel, every form included; `make_sparse_inverse_convmodule` is
+mmdet3d's conv module around one.  `ToDense` is `x.dense()` as a module, `SparseUNet` mmdet3d's encoder-decoder middle encoder, which
+returns per-voxel `seg_features` next to the BEV map.  Max pooling over the same tables lives in sparse_pool.py.
 """
 import ctypes
 import math
@@ -35,10 +41,12 @@ class SparseConvIndex(NamedTuple):
     out_shape: tuple                     # (oD, oH, oW)
     nbr: torch.Tensor                    # (R, K) int32: the input row output row o reads through offset j, or -1
     nbr_t: Optional[torch.Tensor]        # (N, K) int32: the output row that reads input row i through offset j, or -1; None for subm
-    num: torch.Tensor                    # (2,) int64 on the device: rows kept, true count
-    out_batch_cnt: torch.Tensor          # (B,) int32: kept rows per sample
+    num: Optional[torch.Tensor]          # (2,) int64 on the device: rows kept, true count; None in an inverse view (every row counts)
+    out_batch_cnt: Optional[torch.Tensor]   # (B,) int32: kept rows per sample; None in an inverse view
     subm: bool = False
     num_in: int = 0                      # N, the input rows the tables were built over
+    in_coors: Optional[torch.Tensor] = None   # (N, 4) int32 contiguous: those rows (what `sparse_conv_index_inverse` hands back as outputs)
+    in_shape: Optional[tuple] = None     # the input spatial_shape (D, H, W)
 
 
 def _triple(v, name):
@@ -122,7 +130,24 @@ def sparse_conv_index(coors, spatial_shape, batch_size, kernel_size, stride=1, p
     if not subm and max_out is None:
         kept = int(num[0])                                                           # the one read-back
         out_coors, nbr = out_coors[:kept], nbr[:kept]
-    return SparseConvIndex(out_coors, o, nbr, nbr_t, num, cnt, subm, N)
+    return SparseConvIndex(out_coors, o, nbr, nbr_t, num, cnt, subm, N, c, n)
+
+
+def sparse_conv_index_inverse(index):
+    """The record of the INVERSE layer of a strided layer's `index`: the same tensors with the roles swapped, nothing built, nothing copied.
+
+    nbr = index.nbr_t (N, K), nbr_t = index.nbr (R, K), out_coors = index.in_coors, out_shape = index.in_shape, num_in = R, subm = False.
+    The offset numbering stays the forward layer's, as in spconv 1.x, whose inverse layer swaps the pair lists and keeps j.  num is None
+    (every entry takes a null count: all N rows are considered; the rows that no kept output reaches hold -1 throughout and come out zero)
+    and so is out_batch_cnt, which nothing here reads.  A submanifold index and a record without `in_coors` raise."""
+    if not isinstance(index, SparseConvIndex):
+        raise RuntimeError('sparse_conv_index_inverse: index must be the record sparse_conv_index returns')
+    if index.subm or index.nbr_t is None:
+        raise RuntimeError('sparse_conv_index_inverse: a submanifold index has no inverse layer (its outputs are its inputs); only the index of '
+                           'a SparseConv3d can be inverted')
+    if index.in_coors is None or index.in_shape is None:
+        raise RuntimeError('sparse_conv_index_inverse: the record does not carry in_coors / in_shape (it was not made by sparse_conv_index)')
+    return SparseConvIndex(index.in_coors, tuple(index.in_shape), index.nbr_t, index.nbr, None, None, False, index.nbr.size(0), None, None)
 
 
 def _weight3(weight, who):
@@ -353,6 +378,20 @@ def sparse_conv(features, weight, bias, index, compute_dtype=None, *, scale=None
     return _SparseConv.apply(features, w, bias, index.nbr, index.nbr_t, index.num, index.subm)
 
 
+def sparse_inverse_conv(features, weight, bias, index, compute_dtype=None, *, scale=None, shift=None, residual=None, activation=None):
+    """spconv 1.x's inverse convolution over the tables of the FORWARD layer's `index` (a strided `sparse_conv_index`) -> (N, Cout):
+    `sparse_conv` over `sparse_conv_index_inverse(index)` — the same launches, forward and backward, the 16-bit and the fused forms included.
+
+    out[i] = sum over the offsets j with index.nbr_t[i, j] >= 0 of features[nbr_t[i, j]] @ weight[j] (+ bias), features (R, Cin) on the
+    forward layer's output rows, out on its input rows; weight (kz, ky, kx, Cin, Cout) or (K, Cin, Cout), the offset j numbered as in the
+    forward layer.  It equals the dense `conv_transpose3d` of the densified features read at the forward layer's input sites.
+    The rule for a row without a valid neighbour holds: that row is ZERO, bias or not — an inactive input row, an active input that no
+    output cell reaches (a stride above the kernel, a truncated edge), an input whose outputs were all dropped by `max_out`.  spconv writes
+    the bias to such a row; mmdet3d builds these layers without bias, where the two agree."""
+    return sparse_conv(features, weight, bias, sparse_conv_index_inverse(index), compute_dtype, scale=scale, shift=shift, residual=residual,
+                       activation=activation)
+
+
 class _SparseToDense(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, coors, shape, B):
@@ -515,6 +554,49 @@ class SparseConv3d(SparseConvolution):
                          compute_dtype=compute_dtype)
 
 
+class SparseInverseConv3d(SparseConvolution):
+    """spconv 1.x's inverse convolution (its positional signature): undoes the geometry of the `SparseConv3d` that stored its index under
+    `indice_key` — the output lies on that layer's INPUT rows (`indices`, `spatial_shape`), through the same tables with the roles swapped
+    (`sparse_inverse_conv`).  Builds nothing and leaves `indice_dict` as it was; a missing key raises.  A row without a valid neighbour is
+    zero, bias or not (spconv writes the bias there)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, indice_key, bias=True, *, compute_dtype=None):
+        super().__init__(in_channels, out_channels, kernel_size, 1, 0, 1, bias, False, indice_key, compute_dtype=compute_dtype)
+
+    def build_index(self, x):
+        raise RuntimeError(f'{type(self).__name__} builds no index: it needs the one a SparseConv3d stored under indice_key {self.indice_key!r}')
+
+    def index_of(self, x):
+        """the inverse view of the index stored under `indice_key` (`sparse_conv_index_inverse`); x must lie on that layer's output rows"""
+        if not isinstance(x, SparseConvTensor):
+            raise RuntimeError(f'{type(self).__name__} takes a SparseConvTensor, got {type(x).__name__}')
+        index = x.find_indice_pair(self.indice_key)
+        if index is None:
+            raise RuntimeError(f'{type(self).__name__}: no index is stored under indice_key {self.indice_key!r}: the SparseConv3d it inverts must '
+                               'run first, with the same key, on this tensor\'s lineage')
+        if index.subm:
+            raise RuntimeError(f'{type(self).__name__}: the index stored under indice_key {self.indice_key!r} is a submanifold layer\'s: there is '
+                               'nothing to invert')
+        if index.nbr.size(1) != math.prod(self.kernel_size) or index.nbr.size(0) != x.features.size(0):
+            raise RuntimeError(f'{type(self).__name__}: the index stored under indice_key {self.indice_key!r} has {index.nbr.size(1)} offsets and '
+                               f'{index.nbr.size(0)} output rows, this layer {math.prod(self.kernel_size)} offsets and the tensor '
+                               f'{x.features.size(0)} rows')
+        return sparse_conv_index_inverse(index)
+
+    def extra_repr(self):
+        return (f'{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, bias={self.bias is not None}, '
+                f'indice_key={self.indice_key!r}' + ('' if self.compute_dtype is None else f', compute_dtype={self.compute_dtype!r}'))
+
+
+class ToDense(SparseModule):
+    """spconv 1.x's `ToDense`: `x.dense()` as a module -> (B, C, D, H, W)."""
+
+    def forward(self, x):
+        if not isinstance(x, SparseConvTensor):
+            raise RuntimeError(f'ToDense takes a SparseConvTensor, got {type(x).__name__}')
+        return x.dense()
+
+
 class SparseSequential(SparseModule):
     """spconv 1.x's container: sparse modules take the tensor, every other `nn.Module` (BatchNorm1d, ReLU) is applied to `.features`."""
 
@@ -594,12 +676,12 @@ class SparseBasicBlock(SparseModule):
         return out
 
 
-def make_sparse_convmodule(in_channels, out_channels, kernel_size, indice_key, stride=1, padding=0, conv_type='SubMConv3d', norm_cfg=None,
-                           order=('conv', 'norm', 'act'), compute_dtype=None):
-    """mmdet3d's sparse conv module: the layers of `order` — conv (no bias), BatchNorm1d(eps, momentum from norm_cfg), ReLU — in a
-    `SparseSequential`.  compute_dtype (an addition) is handed to the conv."""
+def _convmodule(who, types, in_channels, out_channels, kernel_size, indice_key, stride, padding, conv_type, norm_cfg, order, compute_dtype):
+    """the layers of `order` — conv (no bias) of one of `types`, BatchNorm1d(eps, momentum from norm_cfg), ReLU — in a `SparseSequential`"""
     if not isinstance(order, tuple) or len(order) > 3 or not set(order) <= {'conv', 'norm', 'act'}:
-        raise RuntimeError(f"make_sparse_convmodule: order must be a tuple over 'conv', 'norm', 'act', got {order!r}")
+        raise RuntimeError(f"{who}: order must be a tuple over 'conv', 'norm', 'act', got {order!r}")
+    if 'conv' in order and conv_type not in types:
+        raise RuntimeError(f'{who}: conv_type {conv_type!r} is not built here ({", ".join(types)})')
     layers = []
     for layer in order:
         if layer == 'conv':
@@ -609,13 +691,31 @@ def make_sparse_convmodule(in_channels, out_channels, kernel_size, indice_key, s
             elif conv_type == 'SparseConv3d':
                 layers.append(SparseConv3d(in_channels, out_channels, kernel_size, stride, padding, bias=False, indice_key=indice_key,
                                            compute_dtype=compute_dtype))
-            else:
-                raise RuntimeError(f'make_sparse_convmodule: conv_type {conv_type!r} is not built here (SubMConv3d, SparseConv3d)')
+            else:                                                                      # stride and padding are not used, as in mmdet3d
+                layers.append(SparseInverseConv3d(in_channels, out_channels, kernel_size, indice_key, bias=False, compute_dtype=compute_dtype))
         elif layer == 'norm':
             layers.append(_norm1d(norm_cfg, out_channels))
         else:
             layers.append(nn.ReLU(inplace=True))
     return SparseSequential(*layers)
+
+
+def make_sparse_convmodule(in_channels, out_channels, kernel_size, indice_key, stride=1, padding=0, conv_type='SubMConv3d', norm_cfg=None,
+                           order=('conv', 'norm', 'act'), compute_dtype=None):
+    """mmdet3d's sparse conv module: the layers of `order` — conv (no bias), BatchNorm1d(eps, momentum from norm_cfg), ReLU — in a
+    `SparseSequential`.  compute_dtype (an addition) is handed to the conv.  conv_type: 'SubMConv3d' or 'SparseConv3d'; the module around a
+    'SparseInverseConv3d' is built by `make_sparse_inverse_convmodule`."""
+    return _convmodule('make_sparse_convmodule', ('SubMConv3d', 'SparseConv3d'), in_channels, out_channels, kernel_size, indice_key, stride, padding,
+                       conv_type, norm_cfg, order, compute_dtype)
+
+
+def make_sparse_inverse_convmodule(in_channels, out_channels, kernel_size, indice_key, norm_cfg=None, order=('conv', 'norm', 'act'),
+                                   compute_dtype=None):
+    """mmdet3d's `make_sparse_convmodule(conv_type='SparseInverseConv3d')`: a `SparseInverseConv3d` (no bias) over the index stored under
+    `indice_key`, BatchNorm1d and ReLU in the order of `order`, in a `SparseSequential`.  mmdet3d ignores stride and padding for this type;
+    here they are not taken."""
+    return _convmodule('make_sparse_inverse_convmodule', ('SparseInverseConv3d',), in_channels, out_channels, kernel_size, indice_key, 1, 0,
+                       'SparseInverseConv3d', norm_cfg, order, compute_dtype)
 
 
 # ---- conv + BatchNorm + residual + ReLU in one launch (DESIGN.md §3.20) ----------------------------------------------------------------
@@ -694,7 +794,7 @@ def _fuse_sequential(seq):
     while i < len(items):
         name, module = items[i]
         i += 1
-        if type(module) in (SubMConv3d, SparseConv3d, SparseConvolution):
+        if type(module) in (SubMConv3d, SparseConv3d, SparseInverseConv3d, SparseConvolution):
             norm = act = None
             if i < len(items) and isinstance(items[i][1], nn.modules.batchnorm._BatchNorm):
                 norm, i = items[i][1], i + 1
@@ -809,3 +909,66 @@ class MlvlSparseEncoder(SparseEncoder):
     def forward(self, voxel_features, coors, batch_size):
         encode_features, spatial_features = self.encode(voxel_features, coors, batch_size)
         return dict(encode_features=encode_features, spatial_features=spatial_features)
+
+
+class SparseUNet(SparseEncoder):
+    """mmdet3d 0.x's `SparseUNet` middle encoder (Part-A2's), restated from its published sparse_unet.py (absent from the reference tree: not
+    pinned): `SparseEncoder`'s conv_input, encoder_layers and conv_out, and a decoder that goes back up stage by stage.  Decoder block n
+    (4 .. 1): `lateral_layer{n}` a `SparseBasicBlock` on 'subm{n}', `merge_layer{n}` a SubMConv3d module over the concatenated [bottom,
+    lateral] features on 'subm{n}', `upsample_layer{n}` a `SparseInverseConv3d` module over the index the encoder stored under 'spconv{n}'
+    (block 1: a SubMConv3d module on 'subm1').  The decoder builds no index of its own.
+    forward returns dict(spatial_features (B, C * D, H, W), seg_features (num_voxels, decoder_channels[-1][-1])): per-voxel features on the
+    input voxels, in the input's row order."""
+
+    def __init__(self, in_channels, sparse_shape, order=('conv', 'norm', 'act'), norm_cfg=dict(type='BN1d', eps=1e-3, momentum=0.01),
+                 base_channels=16, output_channels=128, encoder_channels=((16,), (32, 32, 32), (64, 64, 64), (64, 64, 64)),
+                 encoder_paddings=((1,), (1, 1, 1), (1, 1, 1), ((0, 1, 1), 1, 1)),
+                 decoder_channels=((64, 64, 64), (64, 64, 32), (32, 32, 16), (16, 16, 16)), decoder_paddings=((1, 0), (1, 0), (0, 0), (0, 1)),
+                 compute_dtype=None):
+        super().__init__(in_channels, sparse_shape, order, norm_cfg, base_channels, output_channels, encoder_channels, encoder_paddings,
+                         'conv_module', compute_dtype)
+        if len(decoder_channels) != len(encoder_channels) or any(len(tuple(c)) != 3 for c in decoder_channels):
+            raise RuntimeError(f'SparseUNet: decoder_channels must hold one (lateral, merge, upsample) triple per encoder stage, got {decoder_channels!r}')
+        self.decoder_channels, self.decoder_paddings = decoder_channels, decoder_paddings
+        self.make_decoder_layers(norm_cfg, tuple(encoder_channels[-1])[-1])
+
+    def make_decoder_layers(self, norm_cfg, in_channels):
+        block_num = len(self.decoder_channels)
+        for i, block_channels in enumerate(self.decoder_channels):
+            n, paddings = block_num - i, self.decoder_paddings[i]
+            setattr(self, f'lateral_layer{n}', SparseBasicBlock(in_channels, block_channels[0], norm_cfg=norm_cfg, indice_key=f'subm{n}',
+                                                                compute_dtype=self.compute_dtype))
+            setattr(self, f'merge_layer{n}', make_sparse_convmodule(in_channels * 2, block_channels[1], 3, norm_cfg=norm_cfg, padding=paddings[0],
+                                                                    indice_key=f'subm{n}', conv_type='SubMConv3d', compute_dtype=self.compute_dtype))
+            if n != 1:
+                setattr(self, f'upsample_layer{n}', make_sparse_inverse_convmodule(in_channels, block_channels[2], 3, norm_cfg=norm_cfg,
+                                                                                   indice_key=f'spconv{n}', compute_dtype=self.compute_dtype))
+            else:                                                        # the last block stays on the input rows: a submanifold layer
+                setattr(self, f'upsample_layer{n}', make_sparse_convmodule(in_channels, block_channels[2], 3, norm_cfg=norm_cfg, padding=paddings[1],
+                                                                           indice_key='subm1', conv_type='SubMConv3d', compute_dtype=self.compute_dtype))
+            in_channels = block_channels[2]
+
+    @staticmethod
+    def reduce_channel(x, out_channels):
+        """x.features (n, C) -> (n, out_channels): the sum over groups of C / out_channels adjacent channels"""
+        n, in_channels = x.features.shape
+        if in_channels % out_channels != 0 or in_channels < out_channels:
+            raise RuntimeError(f'SparseUNet.reduce_channel: {in_channels} channels cannot be reduced to {out_channels}')
+        x.features = x.features.view(n, out_channels, -1).sum(dim=2)
+        return x
+
+    def decoder_layer_forward(self, x_lateral, x_bottom, lateral_layer, merge_layer, upsample_layer):
+        x = lateral_layer(x_lateral)
+        x.features = torch.cat((x_bottom.features, x.features), dim=1)
+        x_merge = merge_layer(x)
+        x = self.reduce_channel(x, x_merge.features.shape[1])
+        x.features = x_merge.features + x.features
+        return upsample_layer(x)
+
+    def forward(self, voxel_features, coors, batch_size):
+        encode_features, spatial_features = self.encode(voxel_features, coors, batch_size)
+        x = encode_features[-1]
+        for n in range(self.stage_num, 0, -1):
+            x = self.decoder_layer_forward(encode_features[n - 1], x, getattr(self, f'lateral_layer{n}'), getattr(self, f'merge_layer{n}'),
+                                           getattr(self, f'upsample_layer{n}'))
+        return dict(spatial_features=spatial_features, seg_features=x.features)
