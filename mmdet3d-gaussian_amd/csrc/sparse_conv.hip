@@ -1,6 +1,7 @@
 // sparse_conv.hip — sparse 3D convolution (spconv 1.x's SubMConv3d / SparseConv3d, restated: include/gd3d.h, gd3d_sparse_conv_*;
-// DESIGN.md §3.18) for gfx950: the index build, the forward and input-gradient implicit GEMM, the two-stage weight gradient, and
-// SparseConvTensor.dense() with its backward.  Every call is one stream-ordered run of launches that reads nothing back.
+// DESIGN.md §3.18) for gfx950: the index build and the fp32 forward and input-gradient implicit GEMM.  The weight gradient of every
+// element type is csrc/sparse_conv_wgrad.hip's, SparseConvTensor.dense() csrc/sparse_dense.hip's, the 16-bit GEMM csrc/sparse_conv_16.hip's.
+// Every call is one stream-ordered run of launches that reads nothing back.
 //   index build   key_kernel     one int64 key per input row, ((b * D + z) * H + y) * W + x, or the sentinel B*D*H*W for an inactive row
 //                 radix sort     (key, row) pairs, stable: a look-up by lower bound finds the LOWEST row of a duplicated cell.  rocPRIM's
 //                                device radix sort, as in hard_voxel.hip.
@@ -15,8 +16,6 @@
 //                 weight.  No atomics: the bits replay.  FUSED (gd3d_sparse_conv_forward_fused): the epilogue of the
 //                 forward form with a per-channel scale, a residual row and a ReLU — a compile-time variant: the plain instances
 //                 keep their code.
-//   wgrad_kernel  per (row chunk, offset, tile of W[j] of 16, 32 or 64 channels a side): partial sums into the workspace; wfinish_kernel adds the chunks in
-//                 ascending order.  bias_kernel / the same finish for the bias gradient.
 // Compiled with -ffp-contract=off (the tables replay bit for bit in csrc/sparse_conv_cpu.cpp); the multiply-adds are explicit fmaf.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,7 +31,6 @@ namespace sparse_conv {
 
 constexpr int BLOCK = 256;
 
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static unsigned blocks_of(long long threads) { return (unsigned)((threads + BLOCK - 1) / BLOCK); }
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
@@ -349,8 +347,6 @@ static int launch_fused_tile(const GemmArgs& a, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-static int tile_of(int channels) { return channels <= 16 ? 16 : (channels <= 32 ? 32 : 64); }   // the smallest tile that holds them, at most 64
-
 static int launch_fused(GemmArgs& a, hipStream_t s) {
   a.vec_res = a.residual != nullptr && a.Co % 4 == 0 && aligned16(a.residual);
   switch (tile_of(a.Co)) {
@@ -366,186 +362,6 @@ static int launch_gemm(const GemmArgs& a, bool trans, hipStream_t s) {
     case 32: return launch_gemm_tile<32>(a, trans, s);
     default: return launch_gemm_tile<TILE_N>(a, trans, s);
   }
-}
-
-// ---- the weight gradient ---------------------------------------------------------------------------------------------------------------
-
-struct WgradArgs {
-  const float *X, *gY;
-  const int32_t* nbr;
-  const long long* num;
-  long long n_src, rows, chunk, parts;
-  int K, Cin, Cout, tiles_co;
-  float *part_w, *part_b;   // (parts, K, Cin, Cout) and (parts, Cout)
-  float *gW, *gb;           // gb nullable
-};
-
-__device__ __forceinline__ long long row_limit(const long long* num, long long rows) {
-  if (num == nullptr) return rows;
-  const long long k = num[0];
-  return k < rows ? (k < 0 ? 0 : k) : rows;
-}
-
-// grid (parts, K, tiles of TI x TO of W[j]): the partial sum of chunk p.  TI, TO in {16, 32, 64}: the smallest tiles that hold Cin and
-// Cout; a thread owns TI / 16 x TO / 16 elements.
-template <int TI, int TO>
-__global__ __launch_bounds__(BLOCK) void wgrad_kernel(const WgradArgs a) {
-  constexpr int MI = TI / 16, MO = TO / 16;
-  __shared__ int nb[WG_ROWS];
-  __shared__ float Xg[WG_ROWS][TI];
-  __shared__ float Gy[WG_ROWS][TO];
-  const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-  const int j = blockIdx.y;
-  const int ci0 = (blockIdx.z / a.tiles_co) * TI, co0 = (blockIdx.z % a.tiles_co) * TO;
-  const long long limit = row_limit(a.num, a.rows);
-  const long long begin = (long long)blockIdx.x * a.chunk;
-  long long end = begin + a.chunk;
-  end = end < limit ? end : limit;
-  float acc[MI][MO];
-  for (int i = 0; i < MI; ++i)
-    for (int q = 0; q < MO; ++q) acc[i][q] = 0.0f;
-  for (long long r0 = begin; r0 < end; r0 += WG_ROWS) {          // begin, end, r0: the same for the whole workgroup
-    int v = -1;
-    if (t < WG_ROWS && r0 + t < end) {
-      v = a.nbr[(r0 + t) * a.K + j];
-      if (v < 0 || v >= a.n_src) v = -1;
-    }
-    if (t < WG_ROWS) nb[t] = v;
-    if (!__syncthreads_or(v >= 0)) continue;
-    for (int idx = t; idx < WG_ROWS * TI; idx += BLOCK) {
-      const int r = idx / TI, c = idx % TI;
-      const int row = nb[r];
-      Xg[r][c] = (row >= 0 && ci0 + c < a.Cin) ? a.X[(long long)row * a.Cin + ci0 + c] : 0.0f;
-    }
-    for (int idx = t; idx < WG_ROWS * TO; idx += BLOCK) {
-      const int r = idx / TO, c = idx % TO;
-      Gy[r][c] = (nb[r] >= 0 && co0 + c < a.Cout) ? a.gY[(r0 + r) * a.Cout + co0 + c] : 0.0f;
-    }
-    __syncthreads();
-    for (int r = 0; r < WG_ROWS; ++r) {
-      float x[MI], g[MO];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) x[i] = Xg[r][ty * MI + i];
-#pragma unroll
-      for (int q = 0; q < MO; ++q) g[q] = Gy[r][tx * MO + q];
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int q = 0; q < MO; ++q) acc[i][q] = __builtin_fmaf(x[i], g[q], acc[i][q]);
-    }
-    __syncthreads();
-  }
-  float* dst = a.part_w + ((long long)blockIdx.x * a.K + j) * a.Cin * a.Cout;
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int ci = ci0 + ty * MI + i;
-    if (ci >= a.Cin) continue;
-#pragma unroll
-    for (int q = 0; q < MO; ++q) {
-      const int co = co0 + tx * MO + q;
-      if (co < a.Cout) dst[(long long)ci * a.Cout + co] = acc[i][q];
-    }
-  }
-}
-
-template <int TI>
-static void launch_wgrad_in(WgradArgs& a, int to, hipStream_t s) {
-  a.tiles_co = (a.Cout + to - 1) / to;
-  const dim3 grid((unsigned)a.parts, (unsigned)a.K, (unsigned)(((a.Cin + TI - 1) / TI) * a.tiles_co));
-  switch (to) {
-    case 16: hipLaunchKernelGGL((wgrad_kernel<TI, 16>), grid, dim3(BLOCK), 0, s, a); break;
-    case 32: hipLaunchKernelGGL((wgrad_kernel<TI, 32>), grid, dim3(BLOCK), 0, s, a); break;
-    default: hipLaunchKernelGGL((wgrad_kernel<TI, 64>), grid, dim3(BLOCK), 0, s, a); break;
-  }
-}
-
-static void launch_wgrad(WgradArgs& a, hipStream_t s) {
-  const int to = tile_of(a.Cout);
-  switch (tile_of(a.Cin)) {
-    case 16: launch_wgrad_in<16>(a, to, s); break;
-    case 32: launch_wgrad_in<32>(a, to, s); break;
-    default: launch_wgrad_in<64>(a, to, s); break;
-  }
-}
-
-// grid (parts): column sums of gY over the chunk's rows that have a neighbour.  The workgroup's threads form 256 / CP groups of CP >= Cout
-// columns (CP a power of two); group g adds the rows g, g + groups, ... of every 256-row step, then the groups are added in ascending order.
-__global__ __launch_bounds__(BLOCK) void bias_kernel(const WgradArgs a, const int CP) {
-  __shared__ int live[BLOCK];
-  __shared__ float red[BLOCK];
-  const int t = threadIdx.x, col = t % CP, grp = t / CP, groups = BLOCK / CP;
-  const long long limit = row_limit(a.num, a.rows);
-  const long long begin = (long long)blockIdx.x * a.chunk;
-  long long end = begin + a.chunk;
-  end = end < limit ? end : limit;
-  float acc = 0.0f;
-  for (long long r0 = begin; r0 < end; r0 += BLOCK) {
-    int any = 0;
-    if (r0 + t < end) {
-      for (int j = 0; j < a.K; ++j) {
-        const int v = a.nbr[(r0 + t) * a.K + j];
-        any |= v >= 0 && v < a.n_src;
-      }
-    }
-    live[t] = any;
-    __syncthreads();
-    const int rn = end - r0 < BLOCK ? (int)(end - r0) : BLOCK;
-    if (col < a.Cout)
-      for (int r = grp; r < rn; r += groups)
-        if (live[r]) acc += a.gY[(r0 + r) * a.Cout + col];
-    __syncthreads();
-  }
-  red[t] = acc;
-  __syncthreads();
-  if (grp == 0 && col < a.Cout) {
-    float s = 0.0f;
-    for (int g = 0; g < groups; ++g) s += red[g * CP + col];
-    a.part_b[(long long)blockIdx.x * a.Cout + col] = s;
-  }
-}
-
-// the chunks' partial sums added in ascending chunk order
-__global__ __launch_bounds__(BLOCK) void wfinish_kernel(const WgradArgs a) {
-  const long long kcc = (long long)a.K * a.Cin * a.Cout;
-  const long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x;
-  if (idx < kcc) {
-    float s = 0.0f;
-    for (long long p = 0; p < a.parts; ++p) s += a.part_w[p * kcc + idx];
-    a.gW[idx] = s;
-  } else if (a.gb != nullptr && idx - kcc < a.Cout) {
-    const long long c = idx - kcc;
-    float s = 0.0f;
-    for (long long p = 0; p < a.parts; ++p) s += a.part_b[p * a.Cout + c];
-    a.gb[c] = s;
-  }
-}
-
-// ---- dense() ---------------------------------------------------------------------------------------------------------------------------
-
-// a thread per (row, channel); BACKWARD: the gather
-template <bool BACKWARD>
-__global__ __launch_bounds__(BLOCK) void dense_kernel(const float* __restrict__ src, const int32_t* __restrict__ coors, long long n, int C,
-                                                      const Geo g, float* __restrict__ dst) {
-  const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
-  if (t >= n * C) return;
-  const long long i = t / C;
-  const int ch = (int)(t - i * C);
-  const int32_t* c = coors + i * 4;
-  const bool in = row_active(c, g);
-  const long long plane = (long long)g.n[0] * g.n[1] * g.n[2];
-  const long long at = in ? ((long long)c[0] * C + ch) * plane + ((long long)c[1] * g.n[1] + c[2]) * g.n[2] + c[3] : 0;
-  if (BACKWARD) dst[t] = in ? src[at] : 0.0f;
-  else if (in) dst[at] = src[t];
-}
-
-static int dense_geo(int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W, Geo* g) {
-  const int32_t shape[3] = {D, H, W}, one[3] = {1, 1, 1}, zero[3] = {0, 0, 0};
-  if (C < 1) return GD3D_E_BADARG;
-  if (C > MAX_C) return GD3D_E_TOOLARGE;
-  const int rc = make_geo(N, B, shape, one, one, zero, 0, g);
-  if (rc != 0) return rc;
-  if (g->in_sent > (1LL << 62) / C || N * C > (1LL << 40)) return GD3D_E_TOOLARGE;
-  return 0;
 }
 
 }  // namespace sparse_conv
@@ -632,12 +448,9 @@ int gd3d_sparse_conv_index(const int32_t* coors, int64_t N, int32_t B, const int
 
 int gd3d_sparse_conv_forward(const float* features, const float* weight, const float* bias, const int32_t* nbr, const int64_t* num,
                              int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, float* out, void* stream) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (N < 0 || R < 0) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (R == 0) return 0;
-  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
+  bool run;
+  const int rc = check_gemm_call(4, 0, R, N, K, Cin, Cout, true, features, weight, nbr, nullptr, out, &run);
+  if (rc != 0 || !run) return rc;
   GemmArgs a;
   a.src = features; a.W = weight; a.bias = bias; a.table = nbr; a.num = (const long long*)num; a.n_src = N; a.rows = R;
   a.K = K; a.Cr = Cin; a.Co = Cout; a.flip = 0; a.out = out;
@@ -648,13 +461,9 @@ int gd3d_sparse_conv_forward(const float* features, const float* weight, const f
 int gd3d_sparse_conv_forward_fused(const float* features, const float* weight, const float* scale, const float* shift, const float* residual,
                                    const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout,
                                    int32_t act, float* out, void* stream) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (N < 0 || R < 0 || (act != GD3D_ACT_NONE && act != GD3D_ACT_RELU)) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (R == 0) return 0;
-  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
-  if (residual != nullptr && ranges_overlap(residual, out, sizeof(float) * (size_t)R * (size_t)Cout)) return GD3D_E_BADARG;
+  bool run;
+  const int rc = check_gemm_call(4, 0, R, N, K, Cin, Cout, act_ok(act), features, weight, nbr, residual, out, &run);
+  if (rc != 0 || !run) return rc;
   GemmArgs a;
   a.src = features; a.W = weight; a.bias = shift; a.table = nbr; a.num = (const long long*)num; a.n_src = N; a.rows = R;
   a.K = K; a.Cr = Cin; a.Co = Cout; a.flip = 0; a.out = out;
@@ -664,84 +473,14 @@ int gd3d_sparse_conv_forward_fused(const float* features, const float* weight, c
 
 int gd3d_sparse_conv_backward_input(const float* grad_out, const float* weight, const int32_t* table, int32_t flip, int64_t N,
                                     int64_t R, int32_t K, int32_t Cin, int32_t Cout, float* grad_features, void* stream) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (N < 0 || R < 0 || (flip && N != R)) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || N * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (N == 0) return 0;
-  if (weight == nullptr || table == nullptr || grad_features == nullptr || (R > 0 && grad_out == nullptr)) return GD3D_E_BADARG;
+  bool run;
+  const int rc = check_gemm_call(4, 0, N, R, K, Cin, Cout, !flip || N == R, grad_out, weight, table, nullptr, grad_features, &run);
+  if (rc != 0 || !run) return rc;
   GemmArgs a;
   a.src = grad_out; a.W = weight; a.bias = nullptr; a.table = table; a.num = nullptr; a.n_src = R; a.rows = N;
   a.K = K; a.Cr = Cout; a.Co = Cin; a.flip = flip ? 1 : 0; a.out = grad_features;
   a.scale = nullptr; a.residual = nullptr; a.act = GD3D_ACT_NONE; a.vec_res = 0;
   return launch_gemm(a, true, (hipStream_t)stream);
-}
-
-size_t gd3d_sparse_conv_backward_weight_workspace_bytes(int64_t R, int32_t K, int32_t Cin, int32_t Cout) {
-  if (R <= 0 || check_channels(K, Cin, Cout) != 0) return 256;
-  int64_t parts, chunk;
-  weight_parts(R, (int64_t)K * Cin * Cout, &parts, &chunk);
-  return up256(sizeof(float) * (size_t)parts * (size_t)K * Cin * Cout) + up256(sizeof(float) * (size_t)parts * Cout);
-}
-
-int gd3d_sparse_conv_backward_weight(const float* features, const float* grad_out, const int32_t* nbr, const int64_t* num, int64_t N,
-                                     int64_t R, int32_t K, int32_t Cin, int32_t Cout, void* workspace, float* grad_weight,
-                                     float* grad_bias, void* stream) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (N < 0 || R < 0 || grad_weight == nullptr) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t kcc = (int64_t)K * Cin * Cout;
-  if (R == 0 || N == 0) {                                        // no pair: the gradients are zeros
-    int e = gd3d::fill_words(grad_weight, sizeof(float) * (size_t)kcc, 0u, s);
-    if (e == 0 && grad_bias != nullptr) e = gd3d::fill_words(grad_bias, sizeof(float) * (size_t)Cout, 0u, s);
-    return e;
-  }
-  if (features == nullptr || grad_out == nullptr || nbr == nullptr || workspace == nullptr || ((uintptr_t)workspace & 255) != 0)
-    return GD3D_E_BADARG;
-  WgradArgs a;
-  a.X = features; a.gY = grad_out; a.nbr = nbr; a.num = (const long long*)num; a.n_src = N; a.rows = R;
-  weight_parts(R, kcc, (int64_t*)&a.parts, (int64_t*)&a.chunk);
-  a.K = K; a.Cin = Cin; a.Cout = Cout; a.tiles_co = 1;
-  a.part_w = (float*)workspace;
-  a.part_b = (float*)((char*)workspace + up256(sizeof(float) * (size_t)a.parts * (size_t)kcc));
-  a.gW = grad_weight; a.gb = grad_bias;
-  launch_wgrad(a, s);
-  if (grad_bias != nullptr) {
-    int cp = 1;
-    while (cp < Cout) cp <<= 1;                                  // <= 256 = BLOCK
-    hipLaunchKernelGGL(bias_kernel, dim3((unsigned)a.parts), dim3(BLOCK), 0, s, a, cp);
-  }
-  hipLaunchKernelGGL(wfinish_kernel, dim3(blocks_of(kcc + Cout)), dim3(BLOCK), 0, s, a);
-  return (int)hipGetLastError();
-}
-
-int gd3d_sparse_to_dense(const float* features, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W,
-                         float* dense, void* stream) {
-  Geo g;
-  const int rc = dense_geo(N, C, B, D, H, W, &g);
-  if (rc != 0) return rc;
-  if (B == 0) return 0;
-  if (dense == nullptr) return GD3D_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  const int e = gd3d::fill_words(dense, sizeof(float) * (size_t)g.in_sent * (size_t)C, 0u, s);
-  if (e != 0 || N == 0) return e;
-  if (features == nullptr || coors == nullptr) return GD3D_E_BADARG;
-  hipLaunchKernelGGL(dense_kernel<false>, dim3(blocks_of(N * C)), dim3(BLOCK), 0, s, features, coors, (long long)N, (int)C, g, dense);
-  return (int)hipGetLastError();
-}
-
-int gd3d_sparse_to_dense_backward(const float* grad_dense, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H,
-                                  int32_t W, float* grad_features, void* stream) {
-  Geo g;
-  const int rc = dense_geo(N, C, B, D, H, W, &g);
-  if (rc != 0) return rc;
-  if (N == 0) return 0;
-  if (coors == nullptr || grad_features == nullptr || (B > 0 && grad_dense == nullptr)) return GD3D_E_BADARG;
-  hipLaunchKernelGGL(dense_kernel<true>, dim3(blocks_of(N * C)), dim3(BLOCK), 0, (hipStream_t)stream, grad_dense, coors, (long long)N,
-                     (int)C, g, grad_features);
-  return (int)hipGetLastError();
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // sparse_conv_16.hip — the fp16 / bf16 forms of the sparse 3D convolution (include/gd3d.h, gd3d_sparse_conv_*_16)
-// for gfx950: the forward and input-gradient implicit GEMM on v_mfma_f32_16x16x32_{f16,bf16}, the two-stage weight gradient on 16-bit
-// operands, and dense() with its backward for 2-byte elements.  The tables are those of csrc/sparse_conv.hip's index build.
+// for gfx950: the forward and input-gradient implicit GEMM on v_mfma_f32_16x16x32_{f16,bf16}.  The tables are those of
+// csrc/sparse_conv.hip's index build, the element types those of csrc/sparse_conv_elem16.h; the weight gradient on 16-bit operands is
+// csrc/sparse_conv_wgrad.hip's, dense() for 2-byte elements csrc/sparse_dense.hip's.
 //   gemm_kernel   output stationary.  A workgroup of 4 waves owns ROWS = 128 rows x TN = 16, 32 or 64 output channels (the smallest tile
 //                 that holds Cout); a wave owns RT = 2 tiles of 16 rows.  The reduction axis is the concatenation (offset j, channel c),
 //                 K * Cr long, walked 32 at a time.  A operand: lane l loads the 16-byte piece src[table[row l&15][j]][c .. c+7] of its
@@ -17,16 +18,13 @@
 //                 stores are element by element.  Same arithmetic on either path.
 //                 FUSED (gd3d_sparse_conv_forward_fused_16): the forward form with a per-channel scale, a residual row
 //                 and a ReLU in the epilogue, the tile staged unrounded in fp32 — a compile-time variant, the plain instances keep their code.
-//   wgrad_kernel  csrc/sparse_conv.hip's scheme and summation order on operands widened from 16 bits (the products of two 16-bit
-//                 values are exact in fp32): partial sums per chunk of rows, wfinish_kernel adds them in ascending order.  fp32 out.
-//   dense_kernel  the copy kernels for 2-byte elements.
-// Compiled with -ffp-contract=off; the multiply-adds of the weight gradient are explicit fmaf.
+// Compiled with -ffp-contract=off: the epilogues' fp32 sequences are written out, the fused one's multiply-add as an explicit fmaf.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/gd3d.h"
-#include "gd3d_fill.h"
 #include "sparse_conv_common.h"
+#include "sparse_conv_elem16.h"
 
 namespace sparse_conv16 {
 
@@ -42,37 +40,7 @@ constexpr int WHOLE_BYTES = 32 << 10;       // a weight slab up to this size sta
 static_assert(ROWS == WAVES * RT * 16, "TILE_M16 is the row tile of this kernel");
 static_assert(ROWS <= BLOCK, "one thread per row in the prologue");
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// the two element types: 16-bit storage as uint16_t, one rounding to nearest even on the way out
-struct F16 {
-  static __device__ __forceinline__ f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ float widen(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-  static __device__ __forceinline__ uint16_t narrow(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }
-};
-struct BF16 {
-  static __device__ __forceinline__ f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ float widen(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
-  static __device__ __forceinline__ uint16_t narrow(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-};
-
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-static unsigned blocks_of(long long threads) { return (unsigned)((threads + BLOCK - 1) / BLOCK); }
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-static int tile_of(int channels) { return channels <= 16 ? 16 : (channels <= 32 ? 32 : 64); }
-
-__device__ __forceinline__ long long row_limit(const long long* num, long long rows) {
-  if (num == nullptr) return rows;
-  const long long k = num[0];
-  return k < rows ? (k < 0 ? 0 : k) : rows;
-}
 
 // ---- the implicit GEMM ---------------------------------------------------------------------------------------------------------------
 
@@ -350,216 +318,6 @@ static int launch_gemm(GemmArgs& a, bool trans, hipStream_t s, bool fused = fals
   }
 }
 
-// ---- the weight gradient ---------------------------------------------------------------------------------------------------------------
-
-struct WgradArgs {
-  const uint16_t *X, *gY;
-  const int32_t* nbr;
-  const long long* num;
-  long long n_src, rows, chunk, parts;
-  int K, Cin, Cout, tiles_co;
-  float *part_w, *part_b;   // (parts, K, Cin, Cout) and (parts, Cout)
-  float *gW, *gb;           // gb nullable
-};
-
-// csrc/sparse_conv.hip's wgrad_kernel on operands widened from 16 bits: the same tiles, the same order of the fmaf
-template <class E, int TI, int TO>
-__global__ __launch_bounds__(BLOCK) void wgrad_kernel(const WgradArgs a) {
-  constexpr int MI = TI / 16, MO = TO / 16;
-  __shared__ int nb[WG_ROWS];
-  __shared__ float Xg[WG_ROWS][TI];
-  __shared__ float Gy[WG_ROWS][TO];
-  const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-  const int j = blockIdx.y;
-  const int ci0 = (blockIdx.z / a.tiles_co) * TI, co0 = (blockIdx.z % a.tiles_co) * TO;
-  const long long limit = row_limit(a.num, a.rows);
-  const long long begin = (long long)blockIdx.x * a.chunk;
-  long long end = begin + a.chunk;
-  end = end < limit ? end : limit;
-  float acc[MI][MO];
-  for (int i = 0; i < MI; ++i)
-    for (int q = 0; q < MO; ++q) acc[i][q] = 0.0f;
-  for (long long r0 = begin; r0 < end; r0 += WG_ROWS) {          // begin, end, r0: the same for the whole workgroup
-    int v = -1;
-    if (t < WG_ROWS && r0 + t < end) {
-      v = a.nbr[(r0 + t) * a.K + j];
-      if (v < 0 || v >= a.n_src) v = -1;
-    }
-    if (t < WG_ROWS) nb[t] = v;
-    if (!__syncthreads_or(v >= 0)) continue;
-    for (int idx = t; idx < WG_ROWS * TI; idx += BLOCK) {
-      const int r = idx / TI, c = idx % TI;
-      const int row = nb[r];
-      Xg[r][c] = (row >= 0 && ci0 + c < a.Cin) ? E::widen(a.X[(long long)row * a.Cin + ci0 + c]) : 0.0f;
-    }
-    for (int idx = t; idx < WG_ROWS * TO; idx += BLOCK) {
-      const int r = idx / TO, c = idx % TO;
-      Gy[r][c] = (nb[r] >= 0 && co0 + c < a.Cout) ? E::widen(a.gY[(r0 + r) * a.Cout + co0 + c]) : 0.0f;
-    }
-    __syncthreads();
-    for (int r = 0; r < WG_ROWS; ++r) {
-      float x[MI], gy[MO];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) x[i] = Xg[r][ty * MI + i];
-#pragma unroll
-      for (int q = 0; q < MO; ++q) gy[q] = Gy[r][tx * MO + q];
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int q = 0; q < MO; ++q) acc[i][q] = __builtin_fmaf(x[i], gy[q], acc[i][q]);
-    }
-    __syncthreads();
-  }
-  float* dst = a.part_w + ((long long)blockIdx.x * a.K + j) * a.Cin * a.Cout;
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int ci = ci0 + ty * MI + i;
-    if (ci >= a.Cin) continue;
-#pragma unroll
-    for (int q = 0; q < MO; ++q) {
-      const int co = co0 + tx * MO + q;
-      if (co < a.Cout) dst[(long long)ci * a.Cout + co] = acc[i][q];
-    }
-  }
-}
-
-template <class E, int TI>
-static void launch_wgrad_in(WgradArgs& a, int to, hipStream_t s) {
-  a.tiles_co = (a.Cout + to - 1) / to;
-  const dim3 grid((unsigned)a.parts, (unsigned)a.K, (unsigned)(((a.Cin + TI - 1) / TI) * a.tiles_co));
-  switch (to) {
-    case 16: hipLaunchKernelGGL((wgrad_kernel<E, TI, 16>), grid, dim3(BLOCK), 0, s, a); break;
-    case 32: hipLaunchKernelGGL((wgrad_kernel<E, TI, 32>), grid, dim3(BLOCK), 0, s, a); break;
-    default: hipLaunchKernelGGL((wgrad_kernel<E, TI, 64>), grid, dim3(BLOCK), 0, s, a); break;
-  }
-}
-
-template <class E>
-static void launch_wgrad(WgradArgs& a, hipStream_t s) {
-  const int to = tile_of(a.Cout);
-  switch (tile_of(a.Cin)) {
-    case 16: launch_wgrad_in<E, 16>(a, to, s); break;
-    case 32: launch_wgrad_in<E, 32>(a, to, s); break;
-    default: launch_wgrad_in<E, 64>(a, to, s); break;
-  }
-}
-
-// csrc/sparse_conv.hip's bias_kernel on a widened grad_out
-template <class E>
-__global__ __launch_bounds__(BLOCK) void bias_kernel(const WgradArgs a, const int CP) {
-  __shared__ int live[BLOCK];
-  __shared__ float red[BLOCK];
-  const int t = threadIdx.x, col = t % CP, grp = t / CP, groups = BLOCK / CP;
-  const long long limit = row_limit(a.num, a.rows);
-  const long long begin = (long long)blockIdx.x * a.chunk;
-  long long end = begin + a.chunk;
-  end = end < limit ? end : limit;
-  float acc = 0.0f;
-  for (long long r0 = begin; r0 < end; r0 += BLOCK) {
-    int any = 0;
-    if (r0 + t < end) {
-      for (int j = 0; j < a.K; ++j) {
-        const int v = a.nbr[(r0 + t) * a.K + j];
-        any |= v >= 0 && v < a.n_src;
-      }
-    }
-    live[t] = any;
-    __syncthreads();
-    const int rn = end - r0 < BLOCK ? (int)(end - r0) : BLOCK;
-    if (col < a.Cout)
-      for (int r = grp; r < rn; r += groups)
-        if (live[r]) acc += E::widen(a.gY[(r0 + r) * a.Cout + col]);
-    __syncthreads();
-  }
-  red[t] = acc;
-  __syncthreads();
-  if (grp == 0 && col < a.Cout) {
-    float s = 0.0f;
-    for (int gi = 0; gi < groups; ++gi) s += red[gi * CP + col];
-    a.part_b[(long long)blockIdx.x * a.Cout + col] = s;
-  }
-}
-
-// the chunks' partial sums added in ascending chunk order
-__global__ __launch_bounds__(BLOCK) void wfinish_kernel(const WgradArgs a) {
-  const long long kcc = (long long)a.K * a.Cin * a.Cout;
-  const long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x;
-  if (idx < kcc) {
-    float s = 0.0f;
-    for (long long p = 0; p < a.parts; ++p) s += a.part_w[p * kcc + idx];
-    a.gW[idx] = s;
-  } else if (a.gb != nullptr && idx - kcc < a.Cout) {
-    const long long c = idx - kcc;
-    float s = 0.0f;
-    for (long long p = 0; p < a.parts; ++p) s += a.part_b[p * a.Cout + c];
-    a.gb[c] = s;
-  }
-}
-
-template <class E>
-static int run_wgrad(WgradArgs& a, hipStream_t s) {
-  launch_wgrad<E>(a, s);
-  if (a.gb != nullptr) {
-    int cp = 1;
-    while (cp < a.Cout) cp <<= 1;                                // <= 256 = BLOCK
-    hipLaunchKernelGGL(bias_kernel<E>, dim3((unsigned)a.parts), dim3(BLOCK), 0, s, a, cp);
-  }
-  hipLaunchKernelGGL(wfinish_kernel, dim3(blocks_of((long long)a.K * a.Cin * a.Cout + a.Cout)), dim3(BLOCK), 0, s, a);
-  return (int)hipGetLastError();
-}
-
-// ---- dense() ---------------------------------------------------------------------------------------------------------------------------
-
-// a thread per (row, channel); BACKWARD: the gather
-template <bool BACKWARD>
-__global__ __launch_bounds__(BLOCK) void dense_kernel(const uint16_t* __restrict__ src, const int32_t* __restrict__ coors, long long n, int C,
-                                                      const Geo g, uint16_t* __restrict__ dst) {
-  const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
-  if (t >= n * C) return;
-  const long long i = t / C;
-  const int ch = (int)(t - i * C);
-  const int32_t* c = coors + i * 4;
-  const bool in = row_active(c, g);
-  const long long plane = (long long)g.n[0] * g.n[1] * g.n[2];
-  const long long at = in ? ((long long)c[0] * C + ch) * plane + ((long long)c[1] * g.n[1] + c[2]) * g.n[2] + c[3] : 0;
-  if (BACKWARD) dst[t] = in ? src[at] : (uint16_t)0;
-  else if (in) dst[at] = src[t];
-}
-
-// the element before the first and after the last whole word of a 2-byte buffer
-__global__ void edge_kernel(uint16_t* head, uint16_t* tail) {
-  if (head != nullptr) *head = 0;
-  if (tail != nullptr) *tail = 0;
-}
-
-// n zeros of 2 bytes: whole words through the library's fill, an odd element at either end on its own
-static int fill_zero16(uint16_t* p, size_t n, hipStream_t s) {
-  if (n == 0) return 0;
-  uint16_t* head = ((uintptr_t)p & 2u) ? p : nullptr;
-  uint16_t* body = head != nullptr ? p + 1 : p;
-  const size_t rest = head != nullptr ? n - 1 : n;
-  uint16_t* tail = (rest & 1) ? body + rest - 1 : nullptr;
-  int e = 0;
-  if (rest / 2 > 0) e = gd3d::fill_words(body, (rest / 2) * 4, 0u, s);
-  if (e == 0 && (head != nullptr || tail != nullptr)) {
-    hipLaunchKernelGGL(edge_kernel, dim3(1), dim3(1), 0, s, head, tail);
-    e = (int)hipGetLastError();
-  }
-  return e;
-}
-
-static int dense_geo(int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W, Geo* g) {
-  const int32_t shape[3] = {D, H, W}, one[3] = {1, 1, 1}, zero[3] = {0, 0, 0};
-  if (C < 1) return GD3D_E_BADARG;
-  if (C > MAX_C) return GD3D_E_TOOLARGE;
-  const int rc = make_geo(N, B, shape, one, one, zero, 0, g);
-  if (rc != 0) return rc;
-  if (g->in_sent > (1LL << 62) / C || N * C > (1LL << 40)) return GD3D_E_TOOLARGE;
-  return 0;
-}
-
-static bool dtype_ok(int32_t dtype) { return dtype == GD3D_DTYPE_F16 || dtype == GD3D_DTYPE_BF16; }
-
 }  // namespace sparse_conv16
 
 using namespace sparse_conv16;
@@ -568,13 +326,9 @@ extern "C" {
 
 int gd3d_sparse_conv_forward_16(const void* features, const void* weight, const float* bias, const int32_t* nbr, const int64_t* num,
                                 int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* out, void* stream) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (!dtype_ok(dtype) || N < 0 || R < 0) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (R == 0) return 0;
-  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
-  if ((((uintptr_t)features | (uintptr_t)weight | (uintptr_t)out) & 1u) != 0) return GD3D_E_BADARG;
+  bool run;
+  const int rc = check_gemm_call(2, dtype, R, N, K, Cin, Cout, true, features, weight, nbr, nullptr, out, &run);
+  if (rc != 0 || !run) return rc;
   GemmArgs a;
   a.src = (const uint16_t*)features; a.W = (const uint16_t*)weight; a.bias = bias; a.table = nbr; a.num = (const long long*)num;
   a.n_src = N; a.rows = R; a.K = K; a.Cr = Cin; a.Co = Cout; a.flip = 0; a.out = (uint16_t*)out;
@@ -585,14 +339,9 @@ int gd3d_sparse_conv_forward_16(const void* features, const void* weight, const 
 int gd3d_sparse_conv_forward_fused_16(const void* features, const void* weight, const float* scale, const float* shift, const void* residual,
                                       const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout,
                                       int32_t act, int32_t dtype, void* out, void* stream) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (!dtype_ok(dtype) || N < 0 || R < 0 || (act != GD3D_ACT_NONE && act != GD3D_ACT_RELU)) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (R == 0) return 0;
-  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
-  if ((((uintptr_t)features | (uintptr_t)weight | (uintptr_t)residual | (uintptr_t)out) & 1u) != 0) return GD3D_E_BADARG;
-  if (residual != nullptr && ranges_overlap(residual, out, sizeof(uint16_t) * (size_t)R * (size_t)Cout)) return GD3D_E_BADARG;
+  bool run;
+  const int rc = check_gemm_call(2, dtype, R, N, K, Cin, Cout, act_ok(act), features, weight, nbr, residual, out, &run);
+  if (rc != 0 || !run) return rc;
   GemmArgs a;
   a.src = (const uint16_t*)features; a.W = (const uint16_t*)weight; a.bias = shift; a.table = nbr; a.num = (const long long*)num;
   a.n_src = N; a.rows = R; a.K = K; a.Cr = Cin; a.Co = Cout; a.flip = 0; a.out = (uint16_t*)out;
@@ -603,74 +352,14 @@ int gd3d_sparse_conv_forward_fused_16(const void* features, const void* weight, 
 int gd3d_sparse_conv_backward_input_16(const void* grad_out, const void* weight, const int32_t* table, int32_t flip, int64_t N,
                                        int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* grad_features,
                                        void* stream) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (!dtype_ok(dtype) || N < 0 || R < 0 || (flip && N != R)) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || N * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (N == 0) return 0;
-  if (weight == nullptr || table == nullptr || grad_features == nullptr || (R > 0 && grad_out == nullptr)) return GD3D_E_BADARG;
-  if ((((uintptr_t)grad_out | (uintptr_t)weight | (uintptr_t)grad_features) & 1u) != 0) return GD3D_E_BADARG;
+  bool run;
+  const int rc = check_gemm_call(2, dtype, N, R, K, Cin, Cout, !flip || N == R, grad_out, weight, table, nullptr, grad_features, &run);
+  if (rc != 0 || !run) return rc;
   GemmArgs a;
   a.src = (const uint16_t*)grad_out; a.W = (const uint16_t*)weight; a.bias = nullptr; a.table = table; a.num = nullptr;
   a.n_src = R; a.rows = N; a.K = K; a.Cr = Cout; a.Co = Cin; a.flip = flip ? 1 : 0; a.out = (uint16_t*)grad_features;
   a.scale = nullptr; a.residual = nullptr; a.act = GD3D_ACT_NONE;
   return dtype == GD3D_DTYPE_F16 ? launch_gemm<F16>(a, true, (hipStream_t)stream) : launch_gemm<BF16>(a, true, (hipStream_t)stream);
-}
-
-int gd3d_sparse_conv_backward_weight_16(const void* features, const void* grad_out, const int32_t* nbr, const int64_t* num, int64_t N,
-                                        int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* workspace,
-                                        float* grad_weight, float* grad_bias, void* stream) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (!dtype_ok(dtype) || N < 0 || R < 0 || grad_weight == nullptr) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t kcc = (int64_t)K * Cin * Cout;
-  if (R == 0 || N == 0) {                                        // no pair: the gradients are zeros
-    int e = gd3d::fill_words(grad_weight, sizeof(float) * (size_t)kcc, 0u, s);
-    if (e == 0 && grad_bias != nullptr) e = gd3d::fill_words(grad_bias, sizeof(float) * (size_t)Cout, 0u, s);
-    return e;
-  }
-  if (features == nullptr || grad_out == nullptr || nbr == nullptr || workspace == nullptr || ((uintptr_t)workspace & 255) != 0)
-    return GD3D_E_BADARG;
-  if ((((uintptr_t)features | (uintptr_t)grad_out) & 1u) != 0) return GD3D_E_BADARG;
-  WgradArgs a;
-  a.X = (const uint16_t*)features; a.gY = (const uint16_t*)grad_out; a.nbr = nbr; a.num = (const long long*)num; a.n_src = N; a.rows = R;
-  weight_parts(R, kcc, (int64_t*)&a.parts, (int64_t*)&a.chunk);
-  a.K = K; a.Cin = Cin; a.Cout = Cout; a.tiles_co = 1;
-  a.part_w = (float*)workspace;
-  a.part_b = (float*)((char*)workspace + up256(sizeof(float) * (size_t)a.parts * (size_t)kcc));
-  a.gW = grad_weight; a.gb = grad_bias;
-  return dtype == GD3D_DTYPE_F16 ? run_wgrad<F16>(a, s) : run_wgrad<BF16>(a, s);
-}
-
-int gd3d_sparse_to_dense_16(const void* features, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W,
-                            void* dense, void* stream) {
-  Geo g;
-  const int rc = dense_geo(N, C, B, D, H, W, &g);
-  if (rc != 0) return rc;
-  if (B == 0) return 0;
-  if (dense == nullptr || ((uintptr_t)dense & 1u) != 0) return GD3D_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  const int e = fill_zero16((uint16_t*)dense, (size_t)g.in_sent * (size_t)C, s);
-  if (e != 0 || N == 0) return e;
-  if (features == nullptr || coors == nullptr || ((uintptr_t)features & 1u) != 0) return GD3D_E_BADARG;
-  hipLaunchKernelGGL(dense_kernel<false>, dim3(blocks_of(N * C)), dim3(BLOCK), 0, s, (const uint16_t*)features, coors, (long long)N, (int)C,
-                     g, (uint16_t*)dense);
-  return (int)hipGetLastError();
-}
-
-int gd3d_sparse_to_dense_backward_16(const void* grad_dense, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H,
-                                     int32_t W, void* grad_features, void* stream) {
-  Geo g;
-  const int rc = dense_geo(N, C, B, D, H, W, &g);
-  if (rc != 0) return rc;
-  if (N == 0) return 0;
-  if (coors == nullptr || grad_features == nullptr || (B > 0 && grad_dense == nullptr)) return GD3D_E_BADARG;
-  if ((((uintptr_t)grad_dense | (uintptr_t)grad_features) & 1u) != 0) return GD3D_E_BADARG;
-  hipLaunchKernelGGL(dense_kernel<true>, dim3(blocks_of(N * C)), dim3(BLOCK), 0, (hipStream_t)stream, (const uint16_t*)grad_dense, coors,
-                     (long long)N, (int)C, g, (uint16_t*)grad_features);
-  return (int)hipGetLastError();
 }
 
 }  // extern "C"

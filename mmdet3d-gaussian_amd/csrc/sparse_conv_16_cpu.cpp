@@ -39,9 +39,6 @@ inline uint16_t narrow_f16(float f) {
   return h;
 }
 
-bool dtype_ok(int32_t dtype) { return dtype == GD3D_DTYPE_F16 || dtype == GD3D_DTYPE_BF16; }
-bool odd(const void* p) { return ((uintptr_t)p & 1u) != 0; }
-
 std::vector<float> widen(const void* p, int64_t n, int32_t dtype) {
   std::vector<float> out((size_t)(p == nullptr || n < 0 ? 0 : n));
   const uint16_t* s = (const uint16_t*)p;
@@ -60,29 +57,15 @@ void narrow(const std::vector<float>& v, int32_t dtype, void* p) {
     for (size_t i = 0; i < v.size(); ++i) d[i] = narrow_bf16(v[i]);
 }
 
-int dense_geo(int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W, Geo* g) {
-  const int32_t shape[3] = {D, H, W}, one[3] = {1, 1, 1}, zero[3] = {0, 0, 0};
-  if (C < 1) return GD3D_E_BADARG;
-  if (C > MAX_C) return GD3D_E_TOOLARGE;
-  const int rc = make_geo(N, B, shape, one, one, zero, 0, g);
-  if (rc != 0) return rc;
-  if (g->in_sent > (1LL << 62) / C || N * C > (1LL << 40)) return GD3D_E_TOOLARGE;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
 
 int gd3d_sparse_conv_forward_16_cpu(const void* features, const void* weight, const float* bias, const int32_t* nbr, const int64_t* num,
                                     int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* out) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (!dtype_ok(dtype) || N < 0 || R < 0) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (R == 0) return 0;
-  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
-  if (odd(features) || odd(weight) || odd(out)) return GD3D_E_BADARG;
+  bool run;
+  const int rc = check_gemm_call(2, dtype, R, N, K, Cin, Cout, true, features, weight, nbr, nullptr, out, &run);
+  if (rc != 0 || !run) return rc;
   try {
     const std::vector<float> x = widen(features, N * Cin, dtype), w = widen(weight, (int64_t)K * Cin * Cout, dtype);
     std::vector<float> o((size_t)(R * Cout));
@@ -98,14 +81,9 @@ int gd3d_sparse_conv_forward_16_cpu(const void* features, const void* weight, co
 int gd3d_sparse_conv_forward_fused_16_cpu(const void* features, const void* weight, const float* scale, const float* shift,
                                           const void* residual, const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K,
                                           int32_t Cin, int32_t Cout, int32_t act, int32_t dtype, void* out) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (!dtype_ok(dtype) || N < 0 || R < 0 || (act != GD3D_ACT_NONE && act != GD3D_ACT_RELU)) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (R == 0) return 0;
-  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
-  if (odd(features) || odd(weight) || odd(residual) || odd(out)) return GD3D_E_BADARG;
-  if (residual != nullptr && ranges_overlap(residual, out, sizeof(uint16_t) * (size_t)R * (size_t)Cout)) return GD3D_E_BADARG;
+  bool run;
+  const int rc = check_gemm_call(2, dtype, R, N, K, Cin, Cout, act_ok(act), features, weight, nbr, residual, out, &run);
+  if (rc != 0 || !run) return rc;
   try {
     const std::vector<float> x = widen(features, N * Cin, dtype), w = widen(weight, (int64_t)K * Cin * Cout, dtype);
     const std::vector<float> res = widen(residual, R * Cout, dtype);
@@ -122,13 +100,9 @@ int gd3d_sparse_conv_forward_fused_16_cpu(const void* features, const void* weig
 
 int gd3d_sparse_conv_backward_input_16_cpu(const void* grad_out, const void* weight, const int32_t* table, int32_t flip, int64_t N,
                                            int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* grad_features) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (!dtype_ok(dtype) || N < 0 || R < 0 || (flip && N != R)) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || N * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (N == 0) return 0;
-  if (weight == nullptr || table == nullptr || grad_features == nullptr || (R > 0 && grad_out == nullptr)) return GD3D_E_BADARG;
-  if (odd(grad_out) || odd(weight) || odd(grad_features)) return GD3D_E_BADARG;
+  bool run;
+  const int rc = check_gemm_call(2, dtype, N, R, K, Cin, Cout, !flip || N == R, grad_out, weight, table, nullptr, grad_features, &run);
+  if (rc != 0 || !run) return rc;
   try {
     const std::vector<float> gy = widen(grad_out, R * Cout, dtype), w = widen(weight, (int64_t)K * Cin * Cout, dtype);
     std::vector<float> gx((size_t)(N * Cin));
@@ -144,11 +118,12 @@ int gd3d_sparse_conv_backward_input_16_cpu(const void* grad_out, const void* wei
 int gd3d_sparse_conv_backward_weight_16_cpu(const void* features, const void* grad_out, const int32_t* nbr, const int64_t* num,
                                             int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* workspace,
                                             float* grad_weight, float* grad_bias) {
+  // not check_wgrad_call: this twin refuses an odd pointer BEFORE it looks for an empty call, and the shared order would change that code
   const int rc = check_channels(K, Cin, Cout);
   if (rc != 0) return rc;
-  if (!dtype_ok(dtype) || N < 0 || R < 0 || grad_weight == nullptr) return GD3D_E_BADARG;
+  if (!elem_ok(2, dtype) || N < 0 || R < 0 || grad_weight == nullptr) return GD3D_E_BADARG;
   if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (odd(features) || odd(grad_out)) return GD3D_E_BADARG;
+  if (odd_ptr(features) || odd_ptr(grad_out)) return GD3D_E_BADARG;
   try {
     const bool empty = R == 0 || N == 0;
     const std::vector<float> x = widen(features, empty ? 0 : N * Cin, dtype), gy = widen(grad_out, empty ? 0 : R * Cout, dtype);
@@ -165,12 +140,12 @@ int gd3d_sparse_to_dense_16_cpu(const void* features, const int32_t* coors, int6
   const int rc = dense_geo(N, C, B, D, H, W, &g);
   if (rc != 0) return rc;
   if (B == 0) return 0;
-  if (dense == nullptr || odd(dense)) return GD3D_E_BADARG;
+  if (dense == nullptr || odd_ptr(dense)) return GD3D_E_BADARG;
   const long long plane = (long long)D * H * W;
   uint16_t* d = (uint16_t*)dense;
   std::memset(d, 0, sizeof(uint16_t) * (size_t)g.in_sent * (size_t)C);
   if (N == 0) return 0;
-  if (features == nullptr || coors == nullptr || odd(features)) return GD3D_E_BADARG;
+  if (features == nullptr || coors == nullptr || odd_ptr(features)) return GD3D_E_BADARG;
   const uint16_t* f = (const uint16_t*)features;
   for (int64_t i = 0; i < N; ++i) {
     const int32_t* c = coors + i * 4;
@@ -188,7 +163,7 @@ int gd3d_sparse_to_dense_backward_16_cpu(const void* grad_dense, const int32_t* 
   if (rc != 0) return rc;
   if (N == 0) return 0;
   if (coors == nullptr || grad_features == nullptr || (B > 0 && grad_dense == nullptr)) return GD3D_E_BADARG;
-  if (odd(grad_dense) || odd(grad_features)) return GD3D_E_BADARG;
+  if (odd_ptr(grad_dense) || odd_ptr(grad_features)) return GD3D_E_BADARG;
   const long long plane = (long long)D * H * W;
   const uint16_t* s = (const uint16_t*)grad_dense;
   uint16_t* gx = (uint16_t*)grad_features;

@@ -1,6 +1,8 @@
 // sparse_conv_common.h — the integer rules of the sparse 3D convolution (include/gd3d.h, gd3d_sparse_conv_*),
-// shared by csrc/sparse_conv.hip and csrc/sparse_conv_cpu.cpp: which rows are active, the 64-bit keys, the offsets, the per-axis range
-// checks made BEFORE anything is linearised, and the look-up in a sorted key list.  Integers only: both targets give the same tables.
+// shared by the device units (csrc/sparse_conv.hip, sparse_conv_16.hip, sparse_conv_wgrad.hip, sparse_dense.hip) and their `_cpu` twins:
+// which rows are active, the 64-bit keys, the offsets, the per-axis range checks made BEFORE anything is linearised, the look-up in a
+// sorted key list, the tiles and chunks of the value kernels, and the argument checks of every value entry.  Integers only: both
+// targets give the same tables and the same return codes.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -138,6 +140,69 @@ inline bool ranges_overlap(const void* a, const void* b, size_t bytes) {
 inline int check_channels(int32_t K, int32_t Cin, int32_t Cout) {
   if (K < 1 || Cin < 1 || Cout < 1) return GD3D_E_BADARG;
   if (K > MAX_K || Cin > MAX_C || Cout > MAX_C) return GD3D_E_TOOLARGE;
+  return 0;
+}
+
+// rows at and past num[0] are zeros; num nullable: every row counts
+SC_HD long long row_limit(const long long* num, long long rows) {
+  if (num == nullptr) return rows;
+  const long long k = num[0];
+  return k < rows ? (k < 0 ? 0 : k) : rows;
+}
+
+inline int tile_of(int channels) { return channels <= 16 ? 16 : (channels <= 32 ? 32 : 64); }   // the smallest channel tile that holds them, at most 64
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// the geometry of dense(): a 1x1x1 layer over (B, D, H, W) with C channels
+inline int dense_geo(int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W, Geo* g) {
+  const int32_t shape[3] = {D, H, W}, one[3] = {1, 1, 1}, zero[3] = {0, 0, 0};
+  if (C < 1) return GD3D_E_BADARG;
+  if (C > MAX_C) return GD3D_E_TOOLARGE;
+  const int rc = make_geo(N, B, shape, one, one, zero, 0, g);
+  if (rc != 0) return rc;
+  if (g->in_sent > (1LL << 62) / C || N * C > (1LL << 40)) return GD3D_E_TOOLARGE;
+  return 0;
+}
+
+// ---- the argument checks of the value entries, device and `_cpu` alike -----------------------------------------------------------------
+// One order everywhere, so that every entry returns the same code for the same arguments: the channels, GD3D_E_BADARG for the scalars,
+// GD3D_E_TOOLARGE, the empty call (0 with *run = false: nothing to compute), null pointers, odd pointers (16-bit forms), the overlap.
+// elem: the operands' element size, 4 (dtype is not looked at) or 2 (dtype one of GD3D_DTYPE_F16 / BF16, operands 2-byte aligned).
+
+inline bool odd_ptr(const void* p) { return ((uintptr_t)p & 1u) != 0; }
+inline bool elem_ok(size_t elem, int32_t dtype) { return elem == 4 || dtype == GD3D_DTYPE_F16 || dtype == GD3D_DTYPE_BF16; }
+inline bool act_ok(int32_t act) { return act == GD3D_ACT_NONE || act == GD3D_ACT_RELU; }
+
+// The GEMM-shaped calls: `rows` output rows of Cout channels gather from `n_src` source rows through `table` — (R, N) in the forward
+// forms, (N, R) in the input gradient.  scalars_ok: what the entry checks of its own scalars (act; flip).  residual: the fused forward's.
+inline int check_gemm_call(size_t elem, int32_t dtype, int64_t rows, int64_t n_src, int32_t K, int32_t Cin, int32_t Cout, bool scalars_ok,
+                           const void* src, const void* weight, const void* table, const void* residual, const void* out, bool* run) {
+  *run = false;
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (!elem_ok(elem, dtype) || rows < 0 || n_src < 0 || !scalars_ok) return GD3D_E_BADARG;
+  if (rows > 0x7fffffffLL || n_src > 0x7fffffffLL || rows * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  if (rows == 0) return 0;
+  if (weight == nullptr || table == nullptr || out == nullptr || (n_src > 0 && src == nullptr)) return GD3D_E_BADARG;
+  if (elem == 2 && (odd_ptr(src) || odd_ptr(weight) || odd_ptr(residual) || odd_ptr(out))) return GD3D_E_BADARG;
+  if (residual != nullptr && ranges_overlap(residual, out, elem * (size_t)rows * (size_t)Cout)) return GD3D_E_BADARG;
+  *run = true;
+  return 0;
+}
+
+// The weight gradient.  *run = false: no pair, the caller writes zeros.  need_work: the device form's 256-byte aligned workspace.
+inline int check_wgrad_call(size_t elem, int32_t dtype, int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, const void* features,
+                            const void* grad_out, const void* nbr, const void* workspace, bool need_work, const void* grad_weight, bool* run) {
+  *run = false;
+  const int rc = check_channels(K, Cin, Cout);
+  if (rc != 0) return rc;
+  if (!elem_ok(elem, dtype) || N < 0 || R < 0 || grad_weight == nullptr) return GD3D_E_BADARG;
+  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
+  if (R == 0 || N == 0) return 0;
+  if (features == nullptr || grad_out == nullptr || nbr == nullptr) return GD3D_E_BADARG;
+  if (need_work && (workspace == nullptr || ((uintptr_t)workspace & 255) != 0)) return GD3D_E_BADARG;
+  if (elem == 2 && (odd_ptr(features) || odd_ptr(grad_out))) return GD3D_E_BADARG;
+  *run = true;
   return 0;
 }
 

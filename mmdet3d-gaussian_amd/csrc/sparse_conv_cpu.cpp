@@ -13,26 +13,10 @@ using namespace sparse_conv;
 
 namespace {
 
-long long limit_of(const int64_t* num, int64_t rows) {
-  if (num == nullptr) return rows;
-  const long long k = num[0];
-  return k < rows ? (k < 0 ? 0 : k) : rows;
-}
-
 bool row_live(const int32_t* nb, int K, int64_t n_src) {
   for (int j = 0; j < K; ++j)
     if (nb[j] >= 0 && nb[j] < n_src) return true;
   return false;
-}
-
-int dense_geo(int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W, Geo* g) {
-  const int32_t shape[3] = {D, H, W}, one[3] = {1, 1, 1}, zero[3] = {0, 0, 0};
-  if (C < 1) return GD3D_E_BADARG;
-  if (C > MAX_C) return GD3D_E_TOOLARGE;
-  const int rc = make_geo(N, B, shape, one, one, zero, 0, g);
-  if (rc != 0) return rc;
-  if (g->in_sent > (1LL << 62) / C || N * C > (1LL << 40)) return GD3D_E_TOOLARGE;
-  return 0;
 }
 
 int index_build(const int32_t* coors, int64_t N, const Geo& g, int64_t max_out, int32_t* out_coors, int32_t* nbr, int32_t* nbr_t,
@@ -164,27 +148,20 @@ int gd3d_sparse_conv_index_cpu(const int32_t* coors, int64_t N, int32_t B, const
 
 int gd3d_sparse_conv_forward_cpu(const float* features, const float* weight, const float* bias, const int32_t* nbr, const int64_t* num,
                                  int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, float* out) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (N < 0 || R < 0) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (R == 0) return 0;
-  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
-  gemm(features, weight, bias, nbr, limit_of(num, R), N, R, K, Cin, Cout, false, false, out);
+  bool run;
+  const int rc = check_gemm_call(4, 0, R, N, K, Cin, Cout, true, features, weight, nbr, nullptr, out, &run);
+  if (rc != 0 || !run) return rc;
+  gemm(features, weight, bias, nbr, row_limit((const long long*)num, R), N, R, K, Cin, Cout, false, false, out);
   return 0;
 }
 
 int gd3d_sparse_conv_forward_fused_cpu(const float* features, const float* weight, const float* scale, const float* shift,
                                        const float* residual, const int32_t* nbr, const int64_t* num, int64_t N, int64_t R, int32_t K,
                                        int32_t Cin, int32_t Cout, int32_t act, float* out) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (N < 0 || R < 0 || (act != GD3D_ACT_NONE && act != GD3D_ACT_RELU)) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (R == 0) return 0;
-  if (weight == nullptr || nbr == nullptr || out == nullptr || (N > 0 && features == nullptr)) return GD3D_E_BADARG;
-  if (residual != nullptr && ranges_overlap(residual, out, sizeof(float) * (size_t)R * (size_t)Cout)) return GD3D_E_BADARG;
-  const long long limit = limit_of(num, R);
+  bool run;
+  const int rc = check_gemm_call(4, 0, R, N, K, Cin, Cout, act_ok(act), features, weight, nbr, residual, out, &run);
+  if (rc != 0 || !run) return rc;
+  const long long limit = row_limit((const long long*)num, R);
   gemm(features, weight, nullptr, nbr, limit, N, R, K, Cin, Cout, false, false, out);
   for (int64_t r = 0; r < limit; ++r) {                          // the rows past the limit and the rows without a neighbour stay zero
     if (!row_live(nbr + r * K, K, N)) continue;
@@ -202,12 +179,9 @@ int gd3d_sparse_conv_forward_fused_cpu(const float* features, const float* weigh
 
 int gd3d_sparse_conv_backward_input_cpu(const float* grad_out, const float* weight, const int32_t* table, int32_t flip, int64_t N,
                                         int64_t R, int32_t K, int32_t Cin, int32_t Cout, float* grad_features) {
-  const int rc = check_channels(K, Cin, Cout);
-  if (rc != 0) return rc;
-  if (N < 0 || R < 0 || (flip && N != R)) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || N * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (N == 0) return 0;
-  if (weight == nullptr || table == nullptr || grad_features == nullptr || (R > 0 && grad_out == nullptr)) return GD3D_E_BADARG;
+  bool run;
+  const int rc = check_gemm_call(4, 0, N, R, K, Cin, Cout, !flip || N == R, grad_out, weight, table, nullptr, grad_features, &run);
+  if (rc != 0 || !run) return rc;
   gemm(grad_out, weight, nullptr, table, N, R, N, K, Cout, Cin, true, flip != 0, grad_features);
   return 0;
 }
@@ -215,18 +189,15 @@ int gd3d_sparse_conv_backward_input_cpu(const float* grad_out, const float* weig
 int gd3d_sparse_conv_backward_weight_cpu(const float* features, const float* grad_out, const int32_t* nbr, const int64_t* num, int64_t N,
                                          int64_t R, int32_t K, int32_t Cin, int32_t Cout, void* workspace, float* grad_weight,
                                          float* grad_bias) {
-  (void)workspace;
-  const int rc = check_channels(K, Cin, Cout);
+  bool run;
+  const int rc = check_wgrad_call(4, 0, N, R, K, Cin, Cout, features, grad_out, nbr, workspace, false, grad_weight, &run);
   if (rc != 0) return rc;
-  if (N < 0 || R < 0 || grad_weight == nullptr) return GD3D_E_BADARG;
-  if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
   const int64_t cc = (int64_t)Cin * Cout;
   for (int64_t i = 0; i < K * cc; ++i) grad_weight[i] = 0.0f;
   if (grad_bias != nullptr)
     for (int c = 0; c < Cout; ++c) grad_bias[c] = 0.0f;
-  if (R == 0 || N == 0) return 0;
-  if (features == nullptr || grad_out == nullptr || nbr == nullptr) return GD3D_E_BADARG;
-  const long long limit = limit_of(num, R);
+  if (!run) return 0;                                            // no pair: the gradients are zeros
+  const long long limit = row_limit((const long long*)num, R);
   for (int64_t r = 0; r < limit; ++r) {
     const float* gy = grad_out + r * Cout;
     if (grad_bias != nullptr && row_live(nbr + r * K, K, N))

@@ -33,12 +33,7 @@ inline size_t elem_size(int32_t dtype) { return dtype == 0 ? 4 : 2; }
 
 inline bool misaligned(const void* p, size_t to) { return ((uintptr_t)p & (to - 1)) != 0; }
 
-// rows at and past num[0] are zeros; num nullable: every row counts
-SC_HD long long row_limit(const long long* num, long long rows) {
-  if (num == nullptr) return rows;
-  const long long k = num[0];
-  return k < rows ? (k < 0 ? 0 : k) : rows;
-}
+using sparse_conv::row_limit;               // rows at and past num[0] are zeros; num nullable: every row counts
 
 // GD3D_E_* or 0: the scalar arguments of every entry, as the sparse-conv entries order their checks
 inline int check_dims(int64_t N, int64_t R, int32_t K, int32_t C, int32_t dtype) {

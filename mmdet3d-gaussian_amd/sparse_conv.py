@@ -4,7 +4,7 @@
 `pts_middle_encoder`.  mmdet3d and spconv are CUDA-only and absent from the reference tree: the op is RESTATED (include/gd3d.h,
 DESIGN.md §3.18) — a sparse convolution equals the dense `conv3d` of the densified input read at the active output sites.
 
-Three calls carry it (csrc/sparse_conv.hip): `sparse_conv_index` builds the neighbour tables of one layer geometry in one stream-ordered
+Three calls carry it (csrc/sparse_conv.hip, csrc/sparse_conv_wgrad.hip, csrc/sparse_dense.hip): `sparse_conv_index` builds the neighbour tables of one layer geometry in one stream-ordered
 run of launches (64-bit keys, a stable radix sort, look-ups by lower bound; the outputs of a strided layer in ascending (b, z, y, x)
 order, as spconv 1.x's GPU path gives them), `sparse_conv` evaluates a layer over a table (one launch forward; one for the input
 gradient; three for the weight and bias gradients; no atomics, the bits replay), `sparse_to_dense` is `SparseConvTensor.dense()`.  CUDA
@@ -177,30 +177,6 @@ def _backward_entries(x, w, gy, nbr, nbr_t, num, subm, need_x, need_w, has_bias,
     return gx, gw, gb
 
 
-class _SparseConv(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, features, weight, bias, nbr, nbr_t, num, subm):
-        x, w = _host.f32c(features), _host.f32c(weight)
-        b = None if bias is None else _host.f32c(bias)
-        N, (K, Cin, Cout), R, dev = x.size(0), w.shape, nbr.size(0), x.device
-        out = torch.empty((R, Cout), dtype=torch.float32, device=dev)
-        ptr = _host.ptr_or_null
-        _host.call('gd3d_sparse_conv_forward', dev, (ptr(x), ptr(w), ptr(b), ptr(nbr), ptr(num), N, R, K, Cin, Cout, ptr(out)))
-        ctx.save_for_backward(x, w, nbr, nbr_t, num)
-        ctx.state = (subm, bias is not None, features.dtype, weight.dtype, None if bias is None else bias.dtype, weight.shape)
-        return out if features.dtype == torch.float32 else out.to(features.dtype)
-
-    @staticmethod
-    @_host.guard_double_backward
-    def backward(ctx, grad_out):
-        x, w, nbr, nbr_t, num = ctx.saved_tensors
-        subm, has_bias, x_dtype, w_dtype, b_dtype, w_shape = ctx.state
-        gx, gw, gb = _backward_entries(x, w, _host.f32c(grad_out), nbr, nbr_t, num, subm, ctx.needs_input_grad[0],
-                                       ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]), has_bias, None)
-        return (None if gx is None else gx.to(x_dtype), None if gw is None else gw.to(w_dtype).reshape(w_shape),
-                None if gb is None else gb.to(b_dtype), None, None, None, None)
-
-
 _DTYPE_CODES = {torch.float16: 1, torch.bfloat16: 2}          # GD3D_DTYPE_F16, GD3D_DTYPE_BF16 (include/gd3d.h)
 
 
@@ -235,58 +211,39 @@ def _as16(t, dtype):
     return t if t.is_contiguous() else t.contiguous()
 
 
-class _SparseConv16(torch.autograd.Function):
-    """`_SparseConv` on 16-bit operands: features, weight and grad_out in `dtype`, the bias and the parameter gradients fp32"""
-
-    @staticmethod
-    def forward(ctx, features, weight, bias, nbr, nbr_t, num, subm, dtype):
-        x, w = _as16(features, dtype), _as16(weight, dtype)
-        b = None if bias is None else _host.f32c(bias)
-        N, (K, Cin, Cout), R, dev = x.size(0), w.shape, nbr.size(0), x.device
-        out = torch.empty((R, Cout), dtype=dtype, device=dev)
-        ptr = _host.ptr_or_null
-        _host.call('gd3d_sparse_conv_forward_16', dev,
-                   (ptr(x), ptr(w), ptr(b), ptr(nbr), ptr(num), N, R, K, Cin, Cout, _DTYPE_CODES[dtype], ptr(out)))
-        ctx.save_for_backward(x, w, nbr, nbr_t, num)                                   # the 16-bit copies
-        ctx.state = (subm, bias is not None, features.dtype, weight.dtype, None if bias is None else bias.dtype, weight.shape, dtype)
-        return out
-
-    @staticmethod
-    @_host.guard_double_backward
-    def backward(ctx, grad_out):
-        x, w, nbr, nbr_t, num = ctx.saved_tensors
-        subm, has_bias, x_dtype, w_dtype, b_dtype, w_shape, dtype = ctx.state
-        gx, gw, gb = _backward_entries(x, w, _as16(grad_out, dtype), nbr, nbr_t, num, subm, ctx.needs_input_grad[0],
-                                       ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]), has_bias, dtype)
-        return (None if gx is None else gx.to(x_dtype), None if gw is None else gw.to(w_dtype).reshape(w_shape),
-                None if gb is None else gb.to(b_dtype), None, None, None, None, None)
-
-
 _ACT_CODES = {None: 0, 'relu': 1}                             # GD3D_ACT_NONE, GD3D_ACT_RELU (include/gd3d.h)
 
 
-class _SparseConvFused(torch.autograd.Function):
-    """conv -> * scale + shift -> + residual -> ReLU in ONE forward launch (gd3d_sparse_conv_forward_fused[_16]).
-    dtype None: fp32 operands; torch.float16 / torch.bfloat16: 16-bit features, weight, residual and output, fp32 scale and shift.
-    Differentiable w.r.t. features, weight, bias and residual; scale and shift are constants (a frozen BatchNorm)."""
+class _SparseConv(torch.autograd.Function):
+    """One layer over its tables, every form.  dtype None: fp32 operands; torch.float16 / torch.bfloat16: 16-bit features, weight, residual,
+    grad_out and output, fp32 bias, scale, shift and parameter gradients.  residual, scale, shift, activation all None: the plain entry
+    (gd3d_sparse_conv_forward[_16]); any of them given: conv -> * scale + shift -> + residual -> ReLU in ONE forward launch
+    (gd3d_sparse_conv_forward_fused[_16]).  Differentiable w.r.t. features, weight, bias and residual; scale and shift are
+    constants (a frozen BatchNorm).  The backward is the same entries in every form (`_backward_entries`)."""
 
     @staticmethod
     def forward(ctx, features, weight, bias, residual, scale, shift, nbr, nbr_t, num, subm, activation, dtype):
-        cast = _host.f32c if dtype is None else (lambda t: _as16(t, dtype))
-        x, w = cast(features), cast(weight)
-        res = None if residual is None else cast(residual)
-        sc = None if scale is None else _host.f32c(scale)
-        sh = None if shift is None else _host.f32c(shift)
-        if bias is not None:                                                           # the conv's own bias, folded on the host: shift' = bias * scale + shift
-            b = _host.f32c(bias)
-            b = b if sc is None else b * sc
-            sh = b if sh is None else b + sh
+        if dtype is None:
+            x, w, code = _host.f32c(features), _host.f32c(weight), ()
+        else:
+            x, w, code = _as16(features, dtype), _as16(weight, dtype), (_DTYPE_CODES[dtype],)
+        b = None if bias is None else _host.f32c(bias)
         N, (K, Cin, Cout), R, dev = x.size(0), w.shape, nbr.size(0), x.device
         out = torch.empty((R, Cout), dtype=dtype or torch.float32, device=dev)
         ptr = _host.ptr_or_null
-        code = () if dtype is None else (_DTYPE_CODES[dtype],)
-        _host.call('gd3d_sparse_conv_forward_fused' if dtype is None else 'gd3d_sparse_conv_forward_fused_16', dev,
-                   (ptr(x), ptr(w), ptr(sc), ptr(sh), ptr(res), ptr(nbr), ptr(num), N, R, K, Cin, Cout, _ACT_CODES[activation], *code, ptr(out)))
+        if residual is None and scale is None and shift is None and activation is None:
+            sc = None
+            _host.call('gd3d_sparse_conv_forward' if dtype is None else 'gd3d_sparse_conv_forward_16', dev,
+                       (ptr(x), ptr(w), ptr(b), ptr(nbr), ptr(num), N, R, K, Cin, Cout, *code, ptr(out)))
+        else:
+            res = None if residual is None else (_host.f32c(residual) if dtype is None else _as16(residual, dtype))
+            sc = None if scale is None else _host.f32c(scale)
+            sh = None if shift is None else _host.f32c(shift)
+            if b is not None:                                                          # the conv's own bias, folded on the host: shift' = bias * scale + shift
+                b = b if sc is None else b * sc
+                sh = b if sh is None else b + sh
+            _host.call('gd3d_sparse_conv_forward_fused' if dtype is None else 'gd3d_sparse_conv_forward_fused_16', dev,
+                       (ptr(x), ptr(w), ptr(sc), ptr(sh), ptr(res), ptr(nbr), ptr(num), N, R, K, Cin, Cout, _ACT_CODES[activation], *code, ptr(out)))
         ctx.save_for_backward(x, w, nbr, nbr_t, num, sc, out if activation == 'relu' else None)
         ctx.state = (subm, bias is not None, features.dtype, weight.dtype, None if bias is None else bias.dtype,
                      None if residual is None else residual.dtype, weight.shape, dtype)
@@ -372,10 +329,7 @@ def sparse_conv(features, weight, bias, index, compute_dtype=None, *, scale=None
     dtype = _resolve_compute_dtype(compute_dtype, features)
     if scale is not None or shift is not None or residual is not None or activation is not None:
         _check_fused_operands(scale, shift, residual, activation, features, Cout, index.nbr.size(0))
-        return _SparseConvFused.apply(features, w, bias, residual, scale, shift, index.nbr, index.nbr_t, index.num, index.subm, activation, dtype)
-    if dtype is not None:
-        return _SparseConv16.apply(features, w, bias, index.nbr, index.nbr_t, index.num, index.subm, dtype)
-    return _SparseConv.apply(features, w, bias, index.nbr, index.nbr_t, index.num, index.subm)
+    return _SparseConv.apply(features, w, bias, residual, scale, shift, index.nbr, index.nbr_t, index.num, index.subm, activation, dtype)
 
 
 def sparse_inverse_conv(features, weight, bias, index, compute_dtype=None, *, scale=None, shift=None, residual=None, activation=None):

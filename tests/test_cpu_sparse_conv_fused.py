@@ -430,6 +430,51 @@ def test_bad_arguments_raise():
         assert n in amd.__all__
 
 
+# form -> (compute_dtype, an epilogue given, the features' dtype, the entries of one forward and one backward in call order,
+#          the dtypes of out, grad_features).  Plain: the plain entry, never the fused one with null operands.  fp32 forms return the features'
+#          dtype, 16-bit forms compute_dtype; grad_features comes back in the features' dtype, the parameter gradients in the parameters'.
+CALL_FORMS = {
+    'plain_fp32': (None, False, torch.float64, ('gd3d_sparse_conv_forward', 'gd3d_sparse_conv_backward_input', 'gd3d_sparse_conv_backward_weight'),
+                   torch.float64, torch.float64),
+    'plain_bf16': (torch.bfloat16, False, torch.float32,
+                   ('gd3d_sparse_conv_forward_16', 'gd3d_sparse_conv_backward_input_16', 'gd3d_sparse_conv_backward_weight_16'),
+                   torch.bfloat16, torch.float32),
+    'fused_fp32': (None, True, torch.float64,
+                   ('gd3d_sparse_conv_forward_fused', 'gd3d_sparse_conv_backward_input', 'gd3d_sparse_conv_backward_weight'),
+                   torch.float64, torch.float64),
+    'fused_bf16': (torch.bfloat16, True, torch.float32,
+                   ('gd3d_sparse_conv_forward_fused_16', 'gd3d_sparse_conv_backward_input_16', 'gd3d_sparse_conv_backward_weight_16'),
+                   torch.bfloat16, torch.float32),
+}
+
+
+@pytest.mark.parametrize('form', CALL_FORMS)
+def test_every_call_form_makes_exactly_its_host_calls(form, monkeypatch):
+    """one forward and one backward of `sparse_conv` per form: the entry points in order (one forward call, the input gradient, the weight
+    gradient), the output's dtype and the gradients' dtypes"""
+    from mmdet3d_gaussian_amd import _host
+    compute_dtype, fused, x_dtype, entries, out_dtype, gx_dtype = CALL_FORMS[form]
+    name = 'subm_9x12x10_c4_16'
+    X, W, bias, scale, shift, residual = tensors_of(name, 'cpu', 'fp32')
+    index = run_index(c16.case_of(name), 'cpu')                           # built before the calls are recorded
+    seen, real = [], _host.call
+
+    def recording(entry, dev, args, cpu_tail=()):
+        seen.append(entry)
+        return real(entry, dev, args, cpu_tail)
+    monkeypatch.setattr(_host, 'call', recording)
+    x, w, b = X.to(x_dtype).requires_grad_(True), W.clone().requires_grad_(True), bias.clone().requires_grad_(True)
+    res = residual.clone().requires_grad_(True) if fused else None
+    kw = dict(scale=scale, shift=shift, residual=res, activation='relu') if fused else {}
+    out = amd.sparse_conv(x, w, b, index, compute_dtype, **kw)
+    assert tuple(seen) == entries[:1] and out.dtype == out_dtype
+    grads = torch.autograd.grad(out, [x, w, b] + ([res] if fused else []), torch.ones_like(out))
+    assert tuple(seen) == entries
+    assert grads[0].dtype == gx_dtype and grads[1].dtype == w.dtype == torch.float32 and grads[2].dtype == b.dtype == torch.float32
+    assert grads[1].shape == w.shape and (not fused or grads[3].dtype == res.dtype)
+    assert all(g.abs().sum() > 0 for g in grads)
+
+
 @pytest.mark.parametrize('kind', ['fp32', 'bf16'])
 @pytest.mark.parametrize('block_type', ['conv_module', 'basicblock'])
 def test_fused_encoder_follows_the_unfused_modules_layer_by_layer(block_type, kind, monkeypatch):

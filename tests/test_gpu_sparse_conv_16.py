@@ -12,6 +12,7 @@ import mmdet3d_gaussian_amd as amd
 import sparse_conv_16_cases as c16
 import sparse_conv_ref as ref
 from mmdet3d_gaussian_amd import _lib
+from mmdet3d_gaussian_amd.sparse_conv import _backward_entries
 from test_cpu_sparse_conv import ENC_B, ENC_SHAPES, SWEEPS, build_encoder, check_nonfinite_containment, encoder_inputs, run_index
 from test_cpu_sparse_conv_16 import KINDS, check_dense_16, check_modules_16, check_range_16, check_values_16, convs_of, run_values_16
 
@@ -47,6 +48,46 @@ def test_sweep_of_20000_rows_in_bf16(name):
     again = run_values_16(name, DEV, 'bf16', index)
     for k in ('out', 'gx', 'gw', 'gb'):
         assert got[k].tobytes() == again[k].tobytes(), f'{name}: {k} differs from run to run'
+
+
+WIDE = 'wide_subm_c65_130'   # 200 rows at 65 -> 130: two input and three output tiles of 64, so blockIdx.z is split with tiles_co = 3
+WGRAD_CASES = tuple(dict.fromkeys(list(c16.VALUE_CASES) + list(c16.DEAD_TILE_CASES))) + (WIDE,)
+
+
+def wgrad_operands(name):
+    """-> (case, X, gY): fp32 operands on the device, fixed by the case"""
+    if name != WIDE:
+        X, _, _, gY = c16.operands(name)
+        return c16.case_of(name), torch.from_numpy(X).to(DEV), torch.from_numpy(gY).to(DEV)
+    rng = np.random.default_rng(26)
+    case = ref._case(ref.random_coors(rng, 200, (9, 12, 10), 2), (9, 12, 10), 2, 'subm', 65, 130)
+    return case, torch.from_numpy(rng.standard_normal((200, 65)).astype(np.float32)).to(DEV), \
+        torch.from_numpy(rng.standard_normal((200, 130)).astype(np.float32)).to(DEV)
+
+
+@pytest.mark.parametrize('name', WGRAD_CASES)
+def test_the_16_bit_weight_gradient_is_the_fp32_entry_on_the_widened_operands_bit_for_bit(name):
+    """gd3d_sparse_conv_backward_weight_16 against gd3d_sparse_conv_backward_weight on the same 16-bit operands widened to fp32 (exact):
+    grad_weight and grad_bias are equal bit for bit, in fp16 and in bf16, with a bias gradient and without.  One source computes both
+    (csrc/sparse_conv_wgrad.hip): the tiles, the 32-row steps, the chunks and the order of every sum are the same by construction."""
+    case, X, gY = wgrad_operands(name)
+    index = run_index(case, DEV)
+    w = torch.empty((index.nbr.size(1), case['cin'], case['cout']), device=DEV)       # its shape alone is read: no input gradient is asked for
+    pairs = bool(((index.nbr >= 0) & (torch.arange(index.nbr.size(0), device=DEV) < index.num[0])[:, None]).any())
+    for kind in KINDS:
+        dtype = c16.DTYPES[kind]
+        x16, g16 = X.to(dtype), gY.to(dtype)
+        for has_bias in (True, False):
+            run = lambda x, g, dt: _backward_entries(x, w, g, index.nbr, index.nbr_t, index.num, case['subm'], False, True, has_bias, dt)[1:]
+            gw16, gb16 = run(x16, g16, dtype)
+            gw32, gb32 = run(x16.float(), g16.float(), None)
+            assert gw16.dtype == torch.float32 and torch.equal(gw16, gw32), f'{name} {kind}: grad_weight differs from the fp32 entry'
+            assert bool(gw16.any()) == pairs and torch.isfinite(gw16).all(), f'{name} {kind}: grad_weight'
+            if has_bias:
+                assert gb16.dtype == torch.float32 and torch.equal(gb16, gb32), f'{name} {kind}: grad_bias differs from the fp32 entry'
+                assert bool(gb16.any()) == pairs
+            else:
+                assert gb16 is None and gb32 is None
 
 
 def run_c_entries_between_bands(name, kind, shift):
