@@ -80,11 +80,13 @@ from .voxelize import HardSimpleVFE, Voxelization, dynamic_voxelize, hard_voxeli
 from .pillar_feat import PillarFeatureDecorator, PointVoxelStatsCalculator, pillar_decorate, point_voxel_stats
 from .view_net import PointPillarsScatter, multi_view_voxelize, pillar_scatter, to_cylindrical, to_spherical, view_sample
 from .simota import Point3DRangeGenerator, SimOTABEVAssigner, simota_assign
-from .sparse_bn import SparseBatchNorm1d, SparseNormBasicBlock, convert_sparse_batchnorm, sparse_batch_norm
-from .sparse_conv import (FusedSparseBasicBlock, FusedSparseConv, MlvlSparseEncoder, SparseBasicBlock, SparseConv3d, SparseConvIndex, SparseConvTensor, SparseEncoder, SparseModule,
-                          SparseSequential, SubMConv3d, fuse_sparse_conv_bn, make_sparse_convmodule, sparse_conv, sparse_conv_index, sparse_to_dense)
-from .sparse_conv import SparseInverseConv3d, SparseUNet, ToDense, make_sparse_inverse_convmodule, sparse_conv_index_inverse, sparse_inverse_conv
+from .sparse_tensor import SparseConvTensor, SparseModule, SparseSequential, ToDense, sparse_to_dense
+from .sparse_conv import (FusedSparseConv, SparseConv3d, SparseConvIndex, SparseInverseConv3d, SubMConv3d, sparse_conv, sparse_conv_index,
+                          sparse_conv_index_inverse, sparse_inverse_conv)
+from .sparse_bn import SparseBatchNorm1d, sparse_batch_norm
 from .sparse_pool import SparseMaxPool3d, sparse_max_pool
+from .sparse_encoder import (FusedSparseBasicBlock, MlvlSparseEncoder, SparseBasicBlock, SparseEncoder, SparseNormBasicBlock, SparseUNet,
+                             convert_sparse_batchnorm, fuse_sparse_conv_bn, make_sparse_convmodule, make_sparse_inverse_convmodule)
 from .head_loss import (anchor_decoded_gd_loss, anchor_head_bbox_loss, anchor_head_decoded_loss,
                         anchor_head_decoded_loss_fused, center_head_gd_loss, center_head_losses)
 from . import extras

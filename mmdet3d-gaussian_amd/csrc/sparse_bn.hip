@@ -21,58 +21,9 @@
 #include "sparse_bn_common.h"
 
 using namespace sparse_bn;
+using namespace sparse_elem;
 
 namespace {
-
-struct F32 {
-  typedef float T;
-  static constexpr int WIDE = 4;
-  static __device__ __forceinline__ float widen(float x) { return x; }
-  static __device__ __forceinline__ float narrow(float x) { return x; }
-};
-struct F16 {
-  typedef uint16_t T;
-  static constexpr int WIDE = 8;
-  static __device__ __forceinline__ float widen(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-  static __device__ __forceinline__ uint16_t narrow(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }
-};
-struct BF16 {
-  typedef uint16_t T;
-  static constexpr int WIDE = 8;
-  static __device__ __forceinline__ float widen(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
-  static __device__ __forceinline__ uint16_t narrow(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-};
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-  T v[V];
-};
-
-// V adjacent elements at p[at] widened to fp32: one 16-byte load where `wide`, V element loads otherwise (V == 1: the element)
-template <typename E, int V>
-__device__ __forceinline__ void load(const typename E::T* p, long long at, bool wide, float* out) {
-  if (V > 1 && wide) {
-    const Pack<typename E::T, V> k = *reinterpret_cast<const Pack<typename E::T, V>*>(p + at);
-#pragma unroll
-    for (int v = 0; v < V; ++v) out[v] = E::widen(k.v[v]);
-  } else {
-#pragma unroll
-    for (int v = 0; v < V; ++v) out[v] = E::widen(p[at + v]);
-  }
-}
-
-template <typename E, int V>
-__device__ __forceinline__ void store(typename E::T* p, long long at, bool wide, const float* in) {
-  if (V > 1 && wide) {
-    Pack<typename E::T, V> k;
-#pragma unroll
-    for (int v = 0; v < V; ++v) k.v[v] = E::narrow(in[v]);
-    *reinterpret_cast<Pack<typename E::T, V>*>(p + at) = k;
-  } else {
-#pragma unroll
-    for (int v = 0; v < V; ++v) p[at + v] = E::narrow(in[v]);
-  }
-}
 
 struct Args {
   const void *x, *res, *gy, *y;          // features, residual, grad_out, the saved output (the ReLU's mask)
@@ -384,7 +335,7 @@ int first_step(int rows) {
 }
 
 void lay_out(Args* a, int64_t R, int32_t C, int32_t dtype) {
-  const Lanes l = lanes_of(C, dtype);
+  const Lanes l = lanes_of(C, dtype, BLOCK);
   int64_t tiles, chunk;
   cut_rows(R, &tiles, &chunk);
   a->R = R; a->C = C; a->chunk = chunk; a->tiles = (int)tiles;
@@ -421,8 +372,6 @@ int launch_backward(const Args& a, bool vec, bool sums, hipStream_t s) {
   else hipLaunchKernelGGL((bnorm_kernel<E, 1>), dim3(sweep_blocks(a)), dim3(BLOCK), 0, s, a);
   return (int)hipGetLastError();
 }
-
-unsigned wide_bit(const void* p, unsigned bit) { return p != nullptr && !misaligned(p, 16) ? bit : 0u; }
 
 __global__ void fill_kernel(float* p, int n, float v) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -468,12 +417,8 @@ int gd3d_sparse_bn_forward(const void* features, const int32_t* coors, const voi
     }
     return (int)hipGetLastError();
   }
-  const bool vec = lanes_of(C, dtype).vec > 1;
-  switch (dtype) {
-    case 0: return launch_forward<F32>(a, vec, s);
-    case GD3D_DTYPE_F16: return launch_forward<F16>(a, vec, s);
-    default: return launch_forward<BF16>(a, vec, s);
-  }
+  const bool vec = lanes_of(C, dtype, BLOCK).vec > 1;
+  return with_elem(dtype, [&](auto e) { return launch_forward<decltype(e)>(a, vec, s); });
 }
 
 int gd3d_sparse_bn_backward(const void* grad_out, const void* features, const void* out, const int32_t* coors, const float* weight,
@@ -501,12 +446,8 @@ int gd3d_sparse_bn_backward(const void* grad_out, const void* features, const vo
     if (grad_bias != nullptr) hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, grad_bias, (int)C, 0.0f);
     return (int)hipGetLastError();
   }
-  const bool vec = lanes_of(C, dtype).vec > 1, sums = training || grad_weight != nullptr || grad_bias != nullptr;
-  switch (dtype) {
-    case 0: return launch_backward<F32>(a, vec, sums, s);
-    case GD3D_DTYPE_F16: return launch_backward<F16>(a, vec, sums, s);
-    default: return launch_backward<BF16>(a, vec, sums, s);
-  }
+  const bool vec = lanes_of(C, dtype, BLOCK).vec > 1, sums = training || grad_weight != nullptr || grad_bias != nullptr;
+  return with_elem(dtype, [&](auto e) { return launch_backward<decltype(e)>(a, vec, sums, s); });
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // sparse_bn_common.h — what csrc/sparse_bn.hip and csrc/sparse_bn_cpu.cpp share of the live-row batch normalisation (include/gd3d.h,
 // gd3d_sparse_bn_*): which rows are live (csrc/sparse_conv_common.h's rule), how R rows are cut into tiles, how the
-// lanes of a workgroup are laid over rows and channels, the workspace layout and the argument checks.  The cut and the lane layout
+// lanes of a workgroup are laid over rows and channels (csrc/sparse_elem.h), the workspace layout and the argument checks.  The cut and the lane layout
 // depend on (R, C) and the element size alone: nothing a row holds can change the order of a sum.
 #pragma once
 #include <stddef.h>
@@ -26,20 +26,7 @@ inline void cut_rows(int64_t R, int64_t* tiles, int64_t* chunk) {
   *tiles = R > 0 ? (R + c - 1) / c : 0;
 }
 
-// the lane layout: a lane owns `vec` adjacent channels (16 bytes where the row pitch allows it, else one), `groups` lanes cover a row,
-// `rows` rows are covered by one workgroup at a time
-struct Lanes {
-  int vec, groups, rows;
-};
-
-inline Lanes lanes_of(int32_t C, int32_t dtype) {
-  const int wide = dtype == 0 ? 4 : 8;
-  Lanes l;
-  l.vec = C % wide == 0 ? wide : 1;
-  l.groups = C / l.vec;
-  l.rows = BLOCK / l.groups;
-  return l;
-}
+// the lane layout of every kernel here: sparse_elem::lanes_of(C, dtype, BLOCK)
 
 // the workspace, in 4-byte words: the tiles' live-row counts, three (tiles, C) planes of partials, the merged (2, C) plane, the count
 struct Space {
@@ -58,16 +45,12 @@ SC_HD Space space_of(int32_t C) {
   return s;
 }
 
-inline size_t elem_size(int32_t dtype) { return dtype == 0 ? 4 : 2; }
-
 // GD3D_E_* or 0: the scalar arguments of every entry
 inline int check_dims(int64_t R, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W, int32_t act, int32_t dtype) {
   if (R < 0 || C < 1 || B < 0 || D < 1 || H < 1 || W < 1) return GD3D_E_BADARG;
-  if ((act != GD3D_ACT_NONE && act != GD3D_ACT_RELU) || (dtype != 0 && dtype != GD3D_DTYPE_F16 && dtype != GD3D_DTYPE_BF16)) return GD3D_E_BADARG;
+  if (!sparse_conv::act_ok(act) || !sparse_elem::dtype_ok(dtype)) return GD3D_E_BADARG;
   if (C > MAX_C || R > 0x7fffffffLL) return GD3D_E_TOOLARGE;
   return 0;
 }
-
-inline bool misaligned(const void* p, size_t to) { return ((uintptr_t)p & (to - 1)) != 0; }
 
 }  // namespace sparse_bn

@@ -3,7 +3,6 @@
 // rounding to nearest even); the sums are taken per tile of csrc/sparse_bn_common.h's cut in fp64 — two passes, the mean and then the
 // centred squares — and rounded to fp32 once: another order than the device's, the values agree to the tests' bound, not to the bit.
 #include <cmath>
-#include <cstring>
 #include <new>
 #include <vector>
 
@@ -11,45 +10,16 @@
 #include "sparse_bn_common.h"
 
 using namespace sparse_bn;
+using namespace sparse_elem;
 
 namespace {
 
-inline float widen_bf16(uint16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-inline uint16_t narrow_bf16(float f) {   // round to nearest even; inf stays inf, a NaN stays a (quiet) NaN
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-inline float widen_f16(uint16_t h) {
-  _Float16 v;
-  std::memcpy(&v, &h, 2);
-  return (float)v;
-}
-
-inline uint16_t narrow_f16(float f) {
-  const _Float16 v = (_Float16)f;
-  uint16_t h;
-  std::memcpy(&h, &v, 2);
-  return h;
-}
-
 inline float get(const void* p, int64_t i, int32_t dtype) {
-  if (dtype == 0) return ((const float*)p)[i];
-  const uint16_t h = ((const uint16_t*)p)[i];
-  return dtype == GD3D_DTYPE_F16 ? widen_f16(h) : widen_bf16(h);
+  return with_elem(dtype, [&](auto e) { return decltype(e)::widen(((const typename decltype(e)::T*)p)[i]); });
 }
 
 inline void put(void* p, int64_t i, int32_t dtype, float v) {
-  if (dtype == 0) ((float*)p)[i] = v;
-  else ((uint16_t*)p)[i] = dtype == GD3D_DTYPE_F16 ? narrow_f16(v) : narrow_bf16(v);
+  with_elem(dtype, [&](auto e) { ((typename decltype(e)::T*)p)[i] = decltype(e)::narrow(v); });
 }
 
 struct Dims {

@@ -1,6 +1,6 @@
 // sparse_conv_16.hip — the fp16 / bf16 forms of the sparse 3D convolution (include/gd3d.h, gd3d_sparse_conv_*_16)
 // for gfx950: the forward and input-gradient implicit GEMM on v_mfma_f32_16x16x32_{f16,bf16}.  The tables are those of
-// csrc/sparse_conv.hip's index build, the element types those of csrc/sparse_conv_elem16.h; the weight gradient on 16-bit operands is
+// csrc/sparse_conv.hip's index build, the element types those of csrc/sparse_elem.h; the weight gradient on 16-bit operands is
 // csrc/sparse_conv_wgrad.hip's, dense() for 2-byte elements csrc/sparse_dense.hip's.
 //   gemm_kernel   output stationary.  A workgroup of 4 waves owns ROWS = 128 rows x TN = 16, 32 or 64 output channels (the smallest tile
 //                 that holds Cout); a wave owns RT = 2 tiles of 16 rows.  The reduction axis is the concatenation (offset j, channel c),
@@ -24,11 +24,11 @@
 
 #include "../../include/gd3d.h"
 #include "sparse_conv_common.h"
-#include "sparse_conv_elem16.h"
 
 namespace sparse_conv16 {
 
 using namespace sparse_conv;
+using namespace sparse_elem;
 
 constexpr int BLOCK = 256;
 constexpr int WAVES = BLOCK / 64;

@@ -12,49 +12,25 @@ using namespace sparse_conv;
 
 namespace {
 
-inline float widen_bf16(uint16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-inline uint16_t narrow_bf16(float f) {   // round to nearest even; inf stays inf, a NaN stays a (quiet) NaN
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-inline float widen_f16(uint16_t h) {
-  _Float16 v;
-  std::memcpy(&v, &h, 2);
-  return (float)v;
-}
-
-inline uint16_t narrow_f16(float f) {
-  const _Float16 v = (_Float16)f;
-  uint16_t h;
-  std::memcpy(&h, &v, 2);
-  return h;
-}
+using sparse_elem::BF16;
+using sparse_elem::F16;
 
 std::vector<float> widen(const void* p, int64_t n, int32_t dtype) {
   std::vector<float> out((size_t)(p == nullptr || n < 0 ? 0 : n));
   const uint16_t* s = (const uint16_t*)p;
   if (dtype == GD3D_DTYPE_F16)
-    for (size_t i = 0; i < out.size(); ++i) out[i] = widen_f16(s[i]);
+    for (size_t i = 0; i < out.size(); ++i) out[i] = F16::widen(s[i]);
   else
-    for (size_t i = 0; i < out.size(); ++i) out[i] = widen_bf16(s[i]);
+    for (size_t i = 0; i < out.size(); ++i) out[i] = BF16::widen(s[i]);
   return out;
 }
 
 void narrow(const std::vector<float>& v, int32_t dtype, void* p) {
   uint16_t* d = (uint16_t*)p;
   if (dtype == GD3D_DTYPE_F16)
-    for (size_t i = 0; i < v.size(); ++i) d[i] = narrow_f16(v[i]);
+    for (size_t i = 0; i < v.size(); ++i) d[i] = F16::narrow(v[i]);
   else
-    for (size_t i = 0; i < v.size(); ++i) d[i] = narrow_bf16(v[i]);
+    for (size_t i = 0; i < v.size(); ++i) d[i] = BF16::narrow(v[i]);
 }
 
 }  // namespace
@@ -123,7 +99,7 @@ int gd3d_sparse_conv_backward_weight_16_cpu(const void* features, const void* gr
   if (rc != 0) return rc;
   if (!elem_ok(2, dtype) || N < 0 || R < 0 || grad_weight == nullptr) return GD3D_E_BADARG;
   if (N > 0x7fffffffLL || R > 0x7fffffffLL || R * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
-  if (odd_ptr(features) || odd_ptr(grad_out)) return GD3D_E_BADARG;
+  if (misaligned(features, 2) || misaligned(grad_out, 2)) return GD3D_E_BADARG;
   try {
     const bool empty = R == 0 || N == 0;
     const std::vector<float> x = widen(features, empty ? 0 : N * Cin, dtype), gy = widen(grad_out, empty ? 0 : R * Cout, dtype);
@@ -140,12 +116,12 @@ int gd3d_sparse_to_dense_16_cpu(const void* features, const int32_t* coors, int6
   const int rc = dense_geo(N, C, B, D, H, W, &g);
   if (rc != 0) return rc;
   if (B == 0) return 0;
-  if (dense == nullptr || odd_ptr(dense)) return GD3D_E_BADARG;
+  if (dense == nullptr || misaligned(dense, 2)) return GD3D_E_BADARG;
   const long long plane = (long long)D * H * W;
   uint16_t* d = (uint16_t*)dense;
   std::memset(d, 0, sizeof(uint16_t) * (size_t)g.in_sent * (size_t)C);
   if (N == 0) return 0;
-  if (features == nullptr || coors == nullptr || odd_ptr(features)) return GD3D_E_BADARG;
+  if (features == nullptr || coors == nullptr || misaligned(features, 2)) return GD3D_E_BADARG;
   const uint16_t* f = (const uint16_t*)features;
   for (int64_t i = 0; i < N; ++i) {
     const int32_t* c = coors + i * 4;
@@ -163,7 +139,7 @@ int gd3d_sparse_to_dense_backward_16_cpu(const void* grad_dense, const int32_t* 
   if (rc != 0) return rc;
   if (N == 0) return 0;
   if (coors == nullptr || grad_features == nullptr || (B > 0 && grad_dense == nullptr)) return GD3D_E_BADARG;
-  if (odd_ptr(grad_dense) || odd_ptr(grad_features)) return GD3D_E_BADARG;
+  if (misaligned(grad_dense, 2) || misaligned(grad_features, 2)) return GD3D_E_BADARG;
   const long long plane = (long long)D * H * W;
   const uint16_t* s = (const uint16_t*)grad_dense;
   uint16_t* gx = (uint16_t*)grad_features;

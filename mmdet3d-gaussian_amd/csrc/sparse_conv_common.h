@@ -8,14 +8,11 @@
 #include <stdint.h>
 
 #include "../../include/gd3d.h"
-
-#if defined(__HIPCC__)
-#define SC_HD __host__ __device__ __forceinline__
-#else
-#define SC_HD inline
-#endif
+#include "sparse_elem.h"
 
 namespace sparse_conv {
+
+using sparse_elem::misaligned;
 
 constexpr int MAX_K = 27;     // offsets of one kernel
 constexpr int MAX_C = 256;    // channels, either side
@@ -167,10 +164,10 @@ inline int dense_geo(int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int3
 // ---- the argument checks of the value entries, device and `_cpu` alike -----------------------------------------------------------------
 // One order everywhere, so that every entry returns the same code for the same arguments: the channels, GD3D_E_BADARG for the scalars,
 // GD3D_E_TOOLARGE, the empty call (0 with *run = false: nothing to compute), null pointers, odd pointers (16-bit forms), the overlap.
-// elem: the operands' element size, 4 (dtype is not looked at) or 2 (dtype one of GD3D_DTYPE_F16 / BF16, operands 2-byte aligned).
+// elem: the operands' element size, 4 (the fp32 entries, which hand in dtype 0) or 2 (dtype one of GD3D_DTYPE_F16 / BF16, operands
+// 2-byte aligned).
 
-inline bool odd_ptr(const void* p) { return ((uintptr_t)p & 1u) != 0; }
-inline bool elem_ok(size_t elem, int32_t dtype) { return elem == 4 || dtype == GD3D_DTYPE_F16 || dtype == GD3D_DTYPE_BF16; }
+inline bool elem_ok(size_t elem, int32_t dtype) { return sparse_elem::dtype_ok(dtype) && sparse_elem::elem_size(dtype) == elem; }
 inline bool act_ok(int32_t act) { return act == GD3D_ACT_NONE || act == GD3D_ACT_RELU; }
 
 // The GEMM-shaped calls: `rows` output rows of Cout channels gather from `n_src` source rows through `table` — (R, N) in the forward
@@ -184,7 +181,7 @@ inline int check_gemm_call(size_t elem, int32_t dtype, int64_t rows, int64_t n_s
   if (rows > 0x7fffffffLL || n_src > 0x7fffffffLL || rows * K > 0x7fffffffLL) return GD3D_E_TOOLARGE;
   if (rows == 0) return 0;
   if (weight == nullptr || table == nullptr || out == nullptr || (n_src > 0 && src == nullptr)) return GD3D_E_BADARG;
-  if (elem == 2 && (odd_ptr(src) || odd_ptr(weight) || odd_ptr(residual) || odd_ptr(out))) return GD3D_E_BADARG;
+  if (elem == 2 && (misaligned(src, 2) || misaligned(weight, 2) || misaligned(residual, 2) || misaligned(out, 2))) return GD3D_E_BADARG;
   if (residual != nullptr && ranges_overlap(residual, out, elem * (size_t)rows * (size_t)Cout)) return GD3D_E_BADARG;
   *run = true;
   return 0;
@@ -201,7 +198,7 @@ inline int check_wgrad_call(size_t elem, int32_t dtype, int64_t N, int64_t R, in
   if (R == 0 || N == 0) return 0;
   if (features == nullptr || grad_out == nullptr || nbr == nullptr) return GD3D_E_BADARG;
   if (need_work && (workspace == nullptr || ((uintptr_t)workspace & 255) != 0)) return GD3D_E_BADARG;
-  if (elem == 2 && (odd_ptr(features) || odd_ptr(grad_out))) return GD3D_E_BADARG;
+  if (elem == 2 && (misaligned(features, 2) || misaligned(grad_out, 2))) return GD3D_E_BADARG;
   *run = true;
   return 0;
 }

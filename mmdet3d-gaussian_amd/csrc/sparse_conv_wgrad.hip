@@ -1,6 +1,6 @@
 // sparse_conv_wgrad.hip — the weight and bias gradient of the sparse 3D convolution (include/gd3d.h, gd3d_sparse_conv_backward_weight,
 // gd3d_sparse_conv_backward_weight_16) for gfx950, ONE source for fp32, fp16 and bf16 operands: an element policy
-// E gives the storage type and `widen`, the identity for fp32 and exact for the 16-bit types (csrc/sparse_conv_elem16.h), so the three
+// E gives the storage type and `widen`, the identity for fp32 and exact for the 16-bit types (csrc/sparse_elem.h), so the three
 // forms run the same fp32 sequence and the 16-bit entries equal the fp32 entry on the widened operands bit for bit.  fp32 out.
 //   wgrad_kernel  per (row chunk, offset, tile of W[j] of 16, 32 or 64 channels a side): the rows of the chunk in steps of WG_ROWS,
 //                 the gathered X rows and the gY rows staged in LDS as fp32, partial sums into the workspace.  No atomics.
@@ -14,19 +14,10 @@
 #include "../../include/gd3d.h"
 #include "gd3d_fill.h"
 #include "sparse_conv_common.h"
-#include "sparse_conv_elem16.h"
 
 namespace sparse_conv {
 
-using sparse_conv16::BF16;
-using sparse_conv16::F16;
-
 constexpr int BLOCK = 256;
-
-struct F32 {
-  typedef float T;
-  static __device__ __forceinline__ float widen(float x) { return x; }
-};
 
 struct WgradArgs {
   const void *X, *gY;       // (n_src, Cin) and (rows, Cout) of E::T
@@ -185,7 +176,7 @@ static int run_wgrad(WgradArgs& a, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-// elem 4: fp32 operands, dtype not looked at; elem 2: dtype GD3D_DTYPE_F16 / GD3D_DTYPE_BF16
+// elem 4: fp32 operands, dtype 0; elem 2: dtype GD3D_DTYPE_F16 / GD3D_DTYPE_BF16
 static int backward_weight(size_t elem, int32_t dtype, const void* features, const void* grad_out, const int32_t* nbr, const int64_t* num,
                            int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, void* workspace, float* grad_weight, float* grad_bias,
                            hipStream_t s) {
@@ -205,8 +196,7 @@ static int backward_weight(size_t elem, int32_t dtype, const void* features, con
   a.part_w = (float*)workspace;
   a.part_b = (float*)((char*)workspace + up256(sizeof(float) * (size_t)a.parts * (size_t)kcc));
   a.gW = grad_weight; a.gb = grad_bias;
-  if (elem == 4) return run_wgrad<F32>(a, s);
-  return dtype == GD3D_DTYPE_F16 ? run_wgrad<F16>(a, s) : run_wgrad<BF16>(a, s);
+  return sparse_elem::with_elem(dtype, [&](auto e) { return run_wgrad<decltype(e)>(a, s); });
 }
 
 }  // namespace sparse_conv

@@ -57,7 +57,7 @@ static int fill_zero16(uint16_t* p, size_t n, hipStream_t s) {
 
 // a 2-byte element at an odd address; 4-byte elements are taken as they come
 template <class T>
-static bool misplaced(const void* p) { return sizeof(T) == 2 && odd_ptr(p); }
+static bool misplaced(const void* p) { return sizeof(T) == 2 && misaligned(p, 2); }
 
 template <class T>
 static int to_dense(const void* features, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W, void* dense,

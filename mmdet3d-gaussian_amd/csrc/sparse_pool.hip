@@ -15,58 +15,9 @@
 #include "sparse_pool_common.h"
 
 using namespace sparse_pool;
+using namespace sparse_elem;
 
 namespace {
-
-struct F32 {
-  typedef float T;
-  static constexpr int WIDE = 4;
-  static __device__ __forceinline__ float widen(float x) { return x; }
-  static __device__ __forceinline__ float narrow(float x) { return x; }
-};
-struct F16 {
-  typedef uint16_t T;
-  static constexpr int WIDE = 8;
-  static __device__ __forceinline__ float widen(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-  static __device__ __forceinline__ uint16_t narrow(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }
-};
-struct BF16 {
-  typedef uint16_t T;
-  static constexpr int WIDE = 8;
-  static __device__ __forceinline__ float widen(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
-  static __device__ __forceinline__ uint16_t narrow(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-};
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-  T v[V];
-};
-
-// V adjacent elements at p[at] as they are stored: one 16-byte load where `wide`, V element loads otherwise (V == 1: the element)
-template <typename T, int V>
-__device__ __forceinline__ void load(const T* p, long long at, bool wide, T* out) {
-  if (V > 1 && wide) {
-    const Pack<T, V> k = *reinterpret_cast<const Pack<T, V>*>(p + at);
-#pragma unroll
-    for (int v = 0; v < V; ++v) out[v] = k.v[v];
-  } else {
-#pragma unroll
-    for (int v = 0; v < V; ++v) out[v] = p[at + v];
-  }
-}
-
-template <typename T, int V>
-__device__ __forceinline__ void store(T* p, long long at, bool wide, const T* in) {
-  if (V > 1 && wide) {
-    Pack<T, V> k;
-#pragma unroll
-    for (int v = 0; v < V; ++v) k.v[v] = in[v];
-    *reinterpret_cast<Pack<T, V>*>(p + at) = k;
-  } else {
-#pragma unroll
-    for (int v = 0; v < V; ++v) p[at + v] = in[v];
-  }
-}
 
 struct Args {
   const void *x, *y, *gy;      // features (N, C); the pooled output (R, C) and its gradient (the backward only)
@@ -146,8 +97,6 @@ __global__ __launch_bounds__(BLOCK) void unpool_kernel(Args a) {
   }
 }
 
-unsigned wide_bit(const void* p, unsigned bit) { return p != nullptr && !misaligned(p, 16) ? bit : 0u; }
-
 template <typename E>
 int launch(const Args& a, bool vec, bool forward, hipStream_t s) {
   constexpr int V = E::WIDE;
@@ -164,14 +113,10 @@ int launch(const Args& a, bool vec, bool forward, hipStream_t s) {
 }
 
 int dispatch(Args& a, int32_t C, int32_t dtype, bool forward, void* stream) {
-  const Lanes l = lanes_of(C, dtype);
+  const Lanes l = lanes_of(C, dtype, BLOCK);
   a.C = C; a.groups = l.groups; a.lane_rows = l.rows;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case 0: return launch<F32>(a, l.vec > 1, forward, s);
-    case GD3D_DTYPE_F16: return launch<F16>(a, l.vec > 1, forward, s);
-    default: return launch<BF16>(a, l.vec > 1, forward, s);
-  }
+  return with_elem(dtype, [&](auto e) { return launch<decltype(e)>(a, l.vec > 1, forward, s); });
 }
 
 }  // namespace

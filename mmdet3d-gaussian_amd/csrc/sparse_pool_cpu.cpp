@@ -1,57 +1,13 @@
 // sparse_pool_cpu.cpp — the `_cpu` twins of csrc/sparse_pool.hip (include/gd3d.h, gd3d_sparse_max_pool_*) on the thread
 // team of csrc/host_threads.h.  The same walk per element: the maximum kept as the element it was read as, a candidate winning when it
 // is greater or a NaN; the gradient summed in ascending offset order in fp32 and rounded to nearest even once.  The same bits as the device.
-#include <cstring>
-
 #include "host_threads.h"
 #include "sparse_pool_common.h"
 
 using namespace sparse_pool;
+using namespace sparse_elem;
 
 namespace {
-
-inline float widen_bf16(uint16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-inline uint16_t narrow_bf16(float f) {   // round to nearest even; inf stays inf, a NaN stays a (quiet) NaN
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-inline float widen_f16(uint16_t h) {
-  _Float16 v;
-  std::memcpy(&v, &h, 2);
-  return (float)v;
-}
-
-inline uint16_t narrow_f16(float f) {
-  const _Float16 v = (_Float16)f;
-  uint16_t h;
-  std::memcpy(&h, &v, 2);
-  return h;
-}
-
-struct F32 {
-  typedef float T;
-  static float widen(float x) { return x; }
-  static float narrow(float x) { return x; }
-};
-struct F16 {
-  typedef uint16_t T;
-  static float widen(uint16_t h) { return widen_f16(h); }
-  static uint16_t narrow(float x) { return narrow_f16(x); }
-};
-struct BF16 {
-  typedef uint16_t T;
-  static float widen(uint16_t h) { return widen_bf16(h); }
-  static uint16_t narrow(float x) { return narrow_bf16(x); }
-};
 
 int team_for(int64_t units, int64_t min_per_thread) {
   const int t = gd3d_host::team_size(0, units, min_per_thread, 2 * min_per_thread);
@@ -116,13 +72,7 @@ int gd3d_sparse_max_pool_forward_cpu(const void* features, const int32_t* nbr, c
   const size_t es = elem_size(dtype);
   if (misaligned(features, es) || misaligned(out, es) || misaligned(nbr, 4) || misaligned(num, 8)) return GD3D_E_BADARG;
   const long long limit = row_limit((const long long*)num, R);
-  bool ok;
-  switch (dtype) {
-    case 0: ok = pool<F32>(features, nbr, limit, N, R, K, C, out); break;
-    case GD3D_DTYPE_F16: ok = pool<F16>(features, nbr, limit, N, R, K, C, out); break;
-    default: ok = pool<BF16>(features, nbr, limit, N, R, K, C, out); break;
-  }
-  return ok ? 0 : GD3D_E_HOST;
+  return with_elem(dtype, [&](auto e) { return pool<decltype(e)>(features, nbr, limit, N, R, K, C, out); }) ? 0 : GD3D_E_HOST;
 }
 
 int gd3d_sparse_max_pool_backward_cpu(const void* grad_out, const void* features, const void* out, const int32_t* nbr_t, int64_t N,
@@ -134,13 +84,7 @@ int gd3d_sparse_max_pool_backward_cpu(const void* grad_out, const void* features
   const size_t es = elem_size(dtype);
   if (misaligned(grad_out, es) || misaligned(features, es) || misaligned(out, es) || misaligned(grad_features, es) || misaligned(nbr_t, 4))
     return GD3D_E_BADARG;
-  bool ok;
-  switch (dtype) {
-    case 0: ok = unpool<F32>(grad_out, features, out, nbr_t, N, R, K, C, grad_features); break;
-    case GD3D_DTYPE_F16: ok = unpool<F16>(grad_out, features, out, nbr_t, N, R, K, C, grad_features); break;
-    default: ok = unpool<BF16>(grad_out, features, out, nbr_t, N, R, K, C, grad_features); break;
-  }
-  return ok ? 0 : GD3D_E_HOST;
+  return with_elem(dtype, [&](auto e) { return unpool<decltype(e)>(grad_out, features, out, nbr_t, N, R, K, C, grad_features); }) ? 0 : GD3D_E_HOST;
 }
 
 }  // extern "C"

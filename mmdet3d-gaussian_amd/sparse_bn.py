@@ -6,31 +6,16 @@ values into its running buffers and turns the zero rows into `shift`.  `sparse_b
 liveness is read from `coors` on the device, by `sparse_conv_index`'s rule, and no count is read back — adds a basic block's residual,
 applies the ReLU, and writes exact zeros to the dead rows: training and eval, forward and backward, fp32 / fp16 / bf16, deterministic,
 without atomics, capturable.  `SparseBatchNorm1d` is the module (the parameters, buffers and `state_dict` keys of `nn.BatchNorm1d`);
-`convert_sparse_batchnorm` / `SparseEncoder.convert_norm()` put it into an encoder, opt-in; `fuse_sparse_conv_bn` folds it as it folds
-a `BatchNorm1d`.
+`convert_sparse_batchnorm` / `SparseEncoder.convert_norm()` (sparse_encoder.py) put it into an encoder, opt-in; `fuse_sparse_conv_bn`
+folds it as it folds a `BatchNorm1d`.
 """
-from collections import OrderedDict
-
 import torch
 from torch import nn
 
 from . import _host, _lib
-from .sparse_conv import (_ACT_CODES, _DTYPE_CODES, MAX_CHANNELS, SparseBasicBlock, SparseConvTensor, SparseModule, SparseSequential, _coors_i32,
-                          _triple)
+from .sparse_tensor import ACT_CODES, DTYPE_CODES, MAX_CHANNELS, SparseConvTensor, SparseModule, as_dtype, check_activation, coors_i32, kernel_dtype, triple
 
 _workspace_bytes = _host.memo(lambda r, c: _lib.load().gd3d_sparse_bn_workspace_bytes(r, c))
-
-
-def _kernel_dtype(t):
-    """the dtype the kernels run `t` in: its own where that is fp32, fp16 or bf16, else fp32 (evaluated there and cast back)"""
-    return t.dtype if t.dtype in _DTYPE_CODES else torch.float32
-
-
-def _as(t, dtype):
-    """t as a contiguous tensor of `dtype`; t itself when it already is"""
-    if t.dtype != dtype:
-        t = t.to(dtype)
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def _workspace(R, C, dev):
@@ -43,9 +28,9 @@ class _SparseBatchNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, weight, bias, residual, coors, running_mean, running_var, num_batches_tracked, shape, B, training, momentum, eps,
                 activation):
-        dtype = _kernel_dtype(features)
-        x = _as(features, dtype)
-        res = None if residual is None else _as(residual, dtype)
+        dtype = kernel_dtype(features)
+        x = as_dtype(features, dtype)
+        res = None if residual is None else as_dtype(residual, dtype)
         w = None if weight is None else _host.f32c(weight)
         b = None if bias is None else _host.f32c(bias)
         (R, C), dev = x.shape, x.device
@@ -60,7 +45,7 @@ class _SparseBatchNorm(torch.autograd.Function):
                    (_host.ptr_or_null(x), _host.ptr_or_null(coors), _host.ptr_or_null(res), ptr(w), ptr(b),
                     ptr(running_mean) if update or not batch_stats else None, ptr(running_var) if update or not batch_stats else None,
                     ptr(num_batches_tracked) if update else None, R, C, B, *shape, int(batch_stats), float(momentum), float(eps),
-                    _ACT_CODES[activation], _DTYPE_CODES.get(dtype, 0), ptr(work), _host.ptr_or_null(out),
+                    ACT_CODES[activation], DTYPE_CODES.get(dtype, 0), ptr(work), _host.ptr_or_null(out),
                     stats.data_ptr() if batch_stats else None, stats.data_ptr() + 4 * C if batch_stats else None))
         ctx.save_for_backward(x, w, stats if batch_stats else running_mean, None if batch_stats else running_var, out if activation == 'relu' else None, coors)
         ctx.work = work
@@ -74,7 +59,7 @@ class _SparseBatchNorm(torch.autograd.Function):
         x, w, mean, var, out, coors = ctx.saved_tensors
         shape, B, batch_stats, eps, activation, dtype, x_dtype, w_dtype, b_dtype, r_dtype = ctx.state
         (R, C), dev = x.shape, x.device
-        gy = _as(grad_out, dtype)
+        gy = as_dtype(grad_out, dtype)
         gx = torch.empty((R, C), dtype=dtype, device=dev)
         gres = torch.empty((R, C), dtype=dtype, device=dev) if r_dtype is not None and ctx.needs_input_grad[3] else None
         need_w, need_b = w_dtype is not None and ctx.needs_input_grad[1], b_dtype is not None and ctx.needs_input_grad[2]
@@ -84,7 +69,7 @@ class _SparseBatchNorm(torch.autograd.Function):
         ptr, ptr0 = _host.ptr, _host.ptr_or_null
         _host.call('gd3d_sparse_bn_backward', dev,
                    (ptr0(gy), ptr0(x), ptr0(out), ptr0(coors), ptr(w), mean.data_ptr(), mean.data_ptr() + 4 * C if batch_stats else var.data_ptr(), R, C, B,
-                    *shape, int(batch_stats), float(eps), _ACT_CODES[activation], _DTYPE_CODES.get(dtype, 0), ptr(work), ptr0(gx), ptr0(gres), ptr(gw), ptr(gb)))
+                    *shape, int(batch_stats), float(eps), ACT_CODES[activation], DTYPE_CODES.get(dtype, 0), ptr(work), ptr0(gx), ptr0(gres), ptr(gw), ptr(gb)))
         return (gx.to(x_dtype) if ctx.needs_input_grad[0] else None, None if gw is None else gw.to(w_dtype), None if gb is None else gb.to(b_dtype),
                 None if gres is None else gres.to(r_dtype), None, None, None, None, None, None, None, None, None, None)
 
@@ -129,17 +114,16 @@ def sparse_batch_norm(features, coors, spatial_shape, batch_size, weight, bias, 
         raise RuntimeError(f'sparse_batch_norm: 1 .. {MAX_CHANNELS} channels are supported, got {C}')
     if not isinstance(coors, torch.Tensor) or coors.dim() != 2 or coors.size(0) != R:
         raise RuntimeError(f'shape mismatch: sparse_batch_norm: coors must be an ({R}, 4) tensor [b, z, y, x], got {tuple(getattr(coors, "shape", ()))}')
-    c = _coors_i32(coors, 'sparse_batch_norm')
+    c = coors_i32(coors, 'sparse_batch_norm')
     if c.device != features.device:
         raise RuntimeError(f'sparse_batch_norm: coors is on {c.device}, features on {features.device}')
-    shape, B = _triple(spatial_shape, 'spatial_shape'), int(batch_size)
+    shape, B = triple(spatial_shape, 'spatial_shape'), int(batch_size)
     if B < 0 or min(shape) < 1:
         raise RuntimeError(f'sparse_batch_norm: needs batch_size >= 0 and a positive spatial_shape, got {B}, {shape}')
     if momentum is None:
         raise RuntimeError('sparse_batch_norm: momentum=None (a cumulative moving average) is not supported: the update is written on the device '
                            'with a fixed momentum')
-    if activation not in _ACT_CODES:
-        raise RuntimeError(f"sparse_batch_norm: activation must be None or 'relu', got {activation!r}")
+    check_activation(activation, 'sparse_batch_norm')
     _check_channel_vector(weight, C, 'weight', features)
     _check_channel_vector(bias, C, 'bias', features)
     if (running_mean is None) != (running_var is None):
@@ -166,8 +150,7 @@ class SparseBatchNorm1d(nn.BatchNorm1d, SparseModule):
     them) added before the activation — the identity of a basic block."""
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, device=None, dtype=None, *, activation=None):
-        if activation not in _ACT_CODES:
-            raise RuntimeError(f"SparseBatchNorm1d: activation must be None or 'relu', got {activation!r}")
+        check_activation(activation, 'SparseBatchNorm1d')
         super().__init__(num_features, eps, momentum, affine, track_running_stats, device=device, dtype=dtype)
         self.activation = activation
 
@@ -186,62 +169,11 @@ class SparseBatchNorm1d(nn.BatchNorm1d, SparseModule):
         return new
 
     def forward(self, x, residual=None):
-        if not isinstance(x, SparseConvTensor):
-            raise RuntimeError(f'{type(self).__name__} takes a SparseConvTensor, got {type(x).__name__}')
+        SparseConvTensor.expect(x, type(self).__name__)
         features = sparse_batch_norm(x.features, x.indices, x.spatial_shape, x.batch_size, self.weight, self.bias, self.running_mean, self.running_var,
                                      self.num_batches_tracked, training=self.training, momentum=self.momentum, eps=self.eps,
                                      residual=getattr(residual, 'features', residual), activation=self.activation)
-        out = SparseConvTensor(features, x.indices, x.spatial_shape, x.batch_size, x.grid)
-        out.indice_dict = x.indice_dict
-        return out
+        return x.derive(features)
 
     def extra_repr(self):
         return super().extra_repr() + f', activation={self.activation!r}'
-
-
-class SparseNormBasicBlock(SparseBasicBlock):
-    """A `SparseBasicBlock` whose norms are `SparseBatchNorm1d`: norm1 carries the first ReLU, norm2 takes the identity as `residual` and
-    carries the final ReLU — two convolutions and two norm calls.  Built by `convert_sparse_batchnorm`, which re-classes a block in place."""
-
-    def forward(self, x):
-        identity = x.features
-        out = self.norm1(self.conv1(x))
-        out = self.conv2(out)
-        if self.downsample is not None:
-            identity = self.downsample(x)
-        return self.norm2(out, residual=identity)
-
-
-def _convert_sequential(seq):
-    """in place: a BatchNorm1d directly followed by an nn.ReLU becomes one SparseBatchNorm1d('relu') under the norm's name, a lone
-    BatchNorm1d one without activation"""
-    items, converted, i = list(seq._modules.items()), OrderedDict(), 0
-    while i < len(items):
-        name, module = items[i]
-        i += 1
-        if type(module) is nn.BatchNorm1d:
-            act = None
-            if i < len(items) and isinstance(items[i][1], nn.ReLU):
-                act, i = 'relu', i + 1
-            module = SparseBatchNorm1d.from_batchnorm(module, act)
-        converted[name] = module
-    seq._modules = converted
-
-
-def convert_sparse_batchnorm(module):
-    """Opt-in, in place, returns the module: inside every `SparseSequential` a `BatchNorm1d` (directly followed by an `nn.ReLU` or not)
-    becomes a `SparseBatchNorm1d`; every `SparseBasicBlock` becomes a `SparseNormBasicBlock`.  Parameters and buffers are shared with the
-    modules they came from: `state_dict` keys and optimizer references stay valid.  Training in the static form (`max_out`,
-    `hard_voxelize(static=True)`) NEEDS the converted norm; `.eval()` and `fuse_sparse_conv_bn` work on the result as before."""
-    for name, child in list(module.named_children()):
-        module._modules[name] = convert_sparse_batchnorm(child)
-    if isinstance(module, SparseBasicBlock) and not isinstance(module, SparseNormBasicBlock):
-        for name in ('norm1', 'norm2'):
-            if type(getattr(module, name)) is not nn.BatchNorm1d:
-                raise RuntimeError(f'convert_sparse_batchnorm: {name} of a SparseBasicBlock must be a BatchNorm1d, got {type(getattr(module, name)).__name__}')
-        module.norm1 = SparseBatchNorm1d.from_batchnorm(module.norm1, 'relu')
-        module.norm2 = SparseBatchNorm1d.from_batchnorm(module.norm2, 'relu')
-        module.__class__ = SparseNormBasicBlock
-    if isinstance(module, SparseSequential):
-        _convert_sequential(module)
-    return module

@@ -11,29 +11,19 @@ import math
 import torch
 
 from . import _host
-from .sparse_conv import (_DTYPE_CODES, MAX_CHANNELS, MAX_OFFSETS, SparseConvIndex, SparseConvTensor, SparseModule, _triple, sparse_conv_index)
-
-
-def _kernel_dtype(t):
-    """the dtype the kernels run `t` in: its own where that is fp32, fp16 or bf16, else fp32 (evaluated there and cast back)"""
-    return t.dtype if t.dtype in _DTYPE_CODES else torch.float32
-
-
-def _as(t, dtype):
-    if t.dtype != dtype:
-        t = t.to(dtype)
-    return t if t.is_contiguous() else t.contiguous()
+from .sparse_conv import SparseConvIndex, sparse_conv_index
+from .sparse_tensor import DTYPE_CODES, MAX_CHANNELS, MAX_OFFSETS, SparseConvTensor, SparseModule, as_dtype, kernel_dtype, triple
 
 
 class _SparseMaxPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, nbr, nbr_t, num):
-        dtype = _kernel_dtype(features)
-        x = _as(features, dtype)
+        dtype = kernel_dtype(features)
+        x = as_dtype(features, dtype)
         (N, C), (R, K), dev = x.shape, nbr.shape, x.device
         out = torch.empty((R, C), dtype=dtype, device=dev)
         ptr = _host.ptr_or_null
-        _host.call('gd3d_sparse_max_pool_forward', dev, (ptr(x), ptr(nbr), ptr(num), N, R, K, C, _DTYPE_CODES.get(dtype, 0), ptr(out)))
+        _host.call('gd3d_sparse_max_pool_forward', dev, (ptr(x), ptr(nbr), ptr(num), N, R, K, C, DTYPE_CODES.get(dtype, 0), ptr(out)))
         ctx.save_for_backward(x, out, nbr_t)
         ctx.state = (features.dtype, dtype)
         return out if dtype == features.dtype else out.to(features.dtype)
@@ -44,10 +34,10 @@ class _SparseMaxPool(torch.autograd.Function):
         x, out, nbr_t = ctx.saved_tensors
         x_dtype, dtype = ctx.state
         (N, C), R, K, dev = x.shape, out.size(0), nbr_t.size(1), x.device
-        gy = _as(grad_out, dtype)
+        gy = as_dtype(grad_out, dtype)
         gx = torch.empty((N, C), dtype=dtype, device=dev)
         ptr = _host.ptr_or_null
-        _host.call('gd3d_sparse_max_pool_backward', dev, (ptr(gy), ptr(x), ptr(out), ptr(nbr_t), N, R, K, C, _DTYPE_CODES.get(dtype, 0), ptr(gx)))
+        _host.call('gd3d_sparse_max_pool_backward', dev, (ptr(gy), ptr(x), ptr(out), ptr(nbr_t), N, R, K, C, DTYPE_CODES.get(dtype, 0), ptr(gx)))
         return gx.to(x_dtype), None, None, None
 
 
@@ -84,21 +74,18 @@ class SparseMaxPool3d(SparseModule):
 
     def __init__(self, kernel_size, stride=1, padding=0, dilation=1, *, max_out=None):
         super().__init__()
-        if _triple(dilation, 'dilation') != (1, 1, 1):
+        if triple(dilation, 'dilation') != (1, 1, 1):
             raise RuntimeError(f'SparseMaxPool3d: dilation must be 1, got {dilation}')
-        self.kernel_size, self.stride, self.padding = _triple(kernel_size, 'kernel_size'), _triple(stride, 'stride'), _triple(padding, 'padding')
+        self.kernel_size, self.stride, self.padding = triple(kernel_size, 'kernel_size'), triple(stride, 'stride'), triple(padding, 'padding')
         self.dilation = (1, 1, 1)
         self.max_out = max_out
         if math.prod(self.kernel_size) > MAX_OFFSETS or min(self.kernel_size) < 1:
             raise RuntimeError(f'SparseMaxPool3d: kernel_size {self.kernel_size} must hold 1 .. {MAX_OFFSETS} offsets')
 
     def forward(self, x):
-        if not isinstance(x, SparseConvTensor):
-            raise RuntimeError(f'SparseMaxPool3d takes a SparseConvTensor, got {type(x).__name__}')
+        SparseConvTensor.expect(x, 'SparseMaxPool3d')
         index = sparse_conv_index(x.indices, x.spatial_shape, x.batch_size, self.kernel_size, self.stride, self.padding, False, self.max_out)
-        out = SparseConvTensor(sparse_max_pool(x.features, index), index.out_coors, index.out_shape, x.batch_size, x.grid)
-        out.indice_dict = x.indice_dict
-        return out
+        return x.derive(sparse_max_pool(x.features, index), index.out_coors, index.out_shape)
 
     def extra_repr(self):
         return f'kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}' + ('' if self.max_out is None else f', max_out={self.max_out}')

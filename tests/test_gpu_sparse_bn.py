@@ -10,8 +10,8 @@ import torch
 import mmdet3d_gaussian_amd as amd
 import sparse_bn_ref as bref
 import sparse_conv_ref as ref
-from mmdet3d_gaussian_amd import _lib
 from sparse_bn_ref import KINDS
+from sparse_twins import refuse_twins
 from test_cpu_sparse_bn import (CHANNELS, LAYOUTS, MODES, ROW_CASES, check_case, check_converted_encoder, check_guards, check_ill_conditioned, check_nonfinite,
                                 check_static_against_exact, layout, operands, rows_layout, run_ours)
 from test_cpu_sparse_conv_fused import randomise_batchnorms
@@ -71,15 +71,7 @@ def test_converted_encoder_trains_next_to_the_unconverted_one(block_type, monkey
 
 def test_device_tensors_never_reach_a_twin(monkeypatch):
     """a `_cpu` twin called with the address of device memory would fault the process: the twins are replaced by functions that raise"""
-    lib = _lib.load()
-
-    def refuse(name):
-        def twin(*args):
-            raise AssertionError(f'{name} was called for tensors on the device')
-        return twin
-    for name in _lib.SYMBOLS:
-        if 'sparse_bn' in name and name.endswith('_cpu'):
-            monkeypatch.setattr(lib, name, refuse(name))
+    refuse_twins(monkeypatch, lambda name: 'sparse_bn' in name and name.endswith('_cpu'))
     coors, shape, B = layout('subm_inactive_block')
     live = bref.live_rows(coors, shape, B)
     with pytest.raises(AssertionError, match='_cpu was called'):          # the replacement is in place: CPU tensors do reach it

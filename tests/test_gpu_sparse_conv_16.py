@@ -13,6 +13,7 @@ import sparse_conv_16_cases as c16
 import sparse_conv_ref as ref
 from mmdet3d_gaussian_amd import _lib
 from mmdet3d_gaussian_amd.sparse_conv import _backward_entries
+from sparse_twins import refuse_twins
 from test_cpu_sparse_conv import ENC_B, ENC_SHAPES, SWEEPS, build_encoder, check_nonfinite_containment, encoder_inputs, run_index
 from test_cpu_sparse_conv_16 import KINDS, check_dense_16, check_modules_16, check_range_16, check_values_16, convs_of, run_values_16
 
@@ -301,15 +302,7 @@ def test_mlvl_sparse_encoder_in_bf16_follows_the_per_layer_fp64_oracle():
 def test_device_tensors_never_reach_a_twin(monkeypatch):
     """a `_cpu` twin called with the address of device memory would fault the process: every 16-bit twin is replaced by a function that
     raises, and the whole 16-bit surface runs on cuda:0"""
-    lib = _lib.load()
-
-    def refuse(name):
-        def twin(*args):
-            raise AssertionError(f'{name} was called for tensors on the device')
-        return twin
-    for name in _lib.SYMBOLS:
-        if name.endswith('_16_cpu'):
-            monkeypatch.setattr(lib, name, refuse(name))
+    refuse_twins(monkeypatch, lambda name: name.endswith('_16_cpu'))
     with pytest.raises(AssertionError, match='_16_cpu was called'):      # the replacement is in place: CPU tensors do reach it
         run_values_16('subm_rows_1', 'cpu', 'bf16')
     check_values_16('subm_9x12x10_c4_16', DEV, 'fp16')

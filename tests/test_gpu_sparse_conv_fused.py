@@ -9,7 +9,7 @@ import torch
 
 import mmdet3d_gaussian_amd as amd
 import sparse_conv_ref as ref
-from mmdet3d_gaussian_amd import _lib
+from sparse_twins import refuse_twins
 from test_cpu_sparse_conv_fused import (DEAD_CASES, FUSED_CASES, KINDS, check_bit_identity, check_dead_rows, check_fused_encoder, check_fused_values,
                                         check_gradients, check_guards, check_nonfinite, randomise_batchnorms, run_fused)
 
@@ -61,15 +61,7 @@ def test_fused_encoder_follows_the_unfused_modules_layer_by_layer(block_type, ki
 
 def test_device_tensors_never_reach_a_twin(monkeypatch):
     """a `_cpu` twin called with the address of device memory would fault the process: the fused twins are replaced by functions that raise"""
-    lib = _lib.load()
-
-    def refuse(name):
-        def twin(*args):
-            raise AssertionError(f'{name} was called for tensors on the device')
-        return twin
-    for name in _lib.SYMBOLS:
-        if 'forward_fused' in name and name.endswith('_cpu'):
-            monkeypatch.setattr(lib, name, refuse(name))
+    refuse_twins(monkeypatch, lambda name: 'forward_fused' in name and name.endswith('_cpu'))
     with pytest.raises(AssertionError, match='_cpu was called'):          # the replacement is in place: CPU tensors do reach it
         run_fused('subm_9x12x10_c4_16', 'cpu', 'bf16', True, True, 'relu')
     for kind in KINDS:

@@ -11,7 +11,7 @@ import sparse_conv_ref as ref
 import sparse_decoder_ref as dref
 import test_cpu_sparse_inverse as inv
 import test_cpu_sparse_pool as pool
-from mmdet3d_gaussian_amd import _lib
+from sparse_twins import refuse_twins
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -129,15 +129,7 @@ def test_pool_device_equals_the_twin_and_itself_bit_for_bit(C, kind):
 
 def test_device_tensors_never_reach_a_twin(monkeypatch):
     """a `_cpu` twin called with the address of device memory would fault the process: the twins are replaced by functions that raise"""
-    lib = _lib.load()
-
-    def refuse(name):
-        def twin(*args):
-            raise AssertionError(f'{name} was called for tensors on the device')
-        return twin
-    for name in _lib.SYMBOLS:
-        if 'sparse_max_pool' in name and name.endswith('_cpu'):
-            monkeypatch.setattr(lib, name, refuse(name))
+    refuse_twins(monkeypatch, lambda name: 'sparse_max_pool' in name and name.endswith('_cpu'))
     coors, idx, _ = pool.case_of('k2s2')
     X, gY = pool.draws((len(coors), 8), 'fp32', 1), pool.draws((len(idx['nbr']), 8), 'fp32', 2)
     with pytest.raises(AssertionError, match='_cpu was called'):

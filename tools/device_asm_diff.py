@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Do two source trees compile to the same gfx950 kernels?   No GPU needed.
 
-    python tools/device_asm_diff.py OLD_TREE NEW_TREE [--units gd3d_] [--jobs 8] [--keep DIR]
+    python tools/device_asm_diff.py OLD_TREE NEW_TREE [--units gd3d_] [--jobs 8] [--keep DIR] [--rename REGEX=REPL ...]
 
 Compiles every HIP translation unit that each tree's mmdet3d-gaussian_amd/build.py lists (its SOURCES and EXTRA_SOURCES,
 with that tree's own flags; --units keeps the file names that start with the prefix) to device-only assembly and compares
@@ -11,6 +11,9 @@ normalisation is the function's index inside local labels (.LBB<i>_<k>, .Lfunc_e
 function's position in its file (and with its digits, the padding in front of a comment).
 Prints the kernels that are only in one tree, the ones that differ (with a unified diff), and exits 1 if any body or
 resource figure differs; kernels present on one side only are listed and do not fail the run.
+--rename REGEX=REPL (repeatable) is re.sub(REGEX, REPL) over OLD's assembly text before anything is read from it, for a kernel whose
+mangled name changed because a template argument moved to another namespace: the renamed kernels then pair up and are compared as
+the others are.  A substitution and nothing more.
 """
 import argparse
 import concurrent.futures
@@ -45,11 +48,14 @@ def compile_tree(tree, out, prefix, jobs):
         return list(pool.map(one, cmds))
 
 
-def kernels(paths):
+def kernels(paths, renames=()):
     """kernel name -> (normalised body lines, descriptor lines)"""
     out = {}
     for p in paths:
-        lines = open(p).read().split('\n')
+        text = open(p).read()
+        for pattern, repl in renames:
+            text = re.sub(pattern, repl, text)
+        lines = text.split('\n')
         names = [ln.split()[1] for ln in lines if ln.strip().startswith('.amdhsa_kernel ')]
         for name in names:
             start = next(i for i, ln in enumerate(lines) if ln.startswith(name + ':'))
@@ -71,6 +77,7 @@ def main():
     ap.add_argument('--units', default='', help='only translation units whose file name starts with this')
     ap.add_argument('--jobs', type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument('--keep', help='write the assembly to DIR/old and DIR/new instead of a temporary directory')
+    ap.add_argument('--rename', action='append', default=[], metavar='REGEX=REPL', help="re.sub over OLD's assembly before it is read")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         root = a.keep or tmp
@@ -78,7 +85,8 @@ def main():
         for tag, tree in (('old', a.old), ('new', a.new)):
             d = os.path.join(root, tag)
             os.makedirs(d, exist_ok=True)
-            sides.append(kernels(compile_tree(os.path.abspath(tree), d, a.units, a.jobs)))
+            renames = [r.split('=', 1) for r in a.rename] if tag == 'old' else ()
+            sides.append(kernels(compile_tree(os.path.abspath(tree), d, a.units, a.jobs), renames))
     old, new = sides
     for tag, names in (('only in OLD', sorted(set(old) - set(new))), ('only in NEW', sorted(set(new) - set(old)))):
         print(f'{tag}: {len(names)}')
