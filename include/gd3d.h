@@ -1492,6 +1492,63 @@ int gd3d_sparse_max_pool_forward_cpu(const void* features, const int32_t* nbr, c
 int gd3d_sparse_max_pool_backward_cpu(const void* grad_out, const void* features, const void* out, const int32_t* nbr_t, int64_t N,
                                       int64_t R, int32_t K, int32_t C, int32_t dtype, void* grad_features);
 
+/* ------------------------------------------------------------------------------------
+ * PV-RCNN's RPN proposal stage (an addition inside ABI 6): `rpn_head.get_bboxes(*rpn_outs, img_metas, proposal_cfg)` of
+ * PVRCNN.forward_train / simple_test (models/detectors/pv_rcnn.py:115-125, :143-146), where rpn_head is mmdet3d's PartA2RPNHead
+ * (get_bboxes_single + class_agnostic_nms; third party, absent, RESTATED from the published 0.x text, parity unpinned), for a
+ * whole batch as a fill, nine launches and the batched NMS — no host read, static shapes, the same under graph capture and replay,
+ * independent of the workgroup schedule.  Every multiply, add, subtract, divide and root below is ONE correctly rounded fp32
+ * operation, never contracted; exp is the library's fixed sequence, the same on both targets.
+ *   fx_expf (csrc/fx_exp.h): k = trunc(x * (1 / ln 2) +- 0.5), r = (x - k * LN2_HI) - k * LN2_LO, c = r - r^2 (P1 + r^2 P2),
+ *   1 + (hi - (lo - r c / (2 - c))), scaled by 2^k on the bit pattern.  NaN -> NaN; x > 88.7228317 (0x42b17217) -> +inf; a result
+ *   below the normal range (x < -87.3365402, 0xc2aeac4f) -> +0 EXACTLY, never a subnormal.  Against fp64 exp, correctly rounded,
+ *   on 2^20 uniform arguments of the finite-result range, every multiple of ln 2 / 2 there +- 4 neighbours and the 4096 values
+ *   either side of 0: at most 0.90 ulp (measured 0.880; the host libm's expf on the same sample: 0.502).
+ *   sigmoid(x) = 1 / (1 + fx_expf(-x)).
+ *
+ * One level, sigmoid classification, box code size 7.  cls_score (B, A*C, H, W), bbox_pred (B, A*7, H, W), dir_cls_pred
+ * (B, A*2, H, W) fp32 contiguous NCHW; anchors (N, 7), N = H*W*A, anchor n = (h*W + w)*A + a; the channel of class c is a*C + c
+ * (likewise a*7 + k and a*2 + d).  cap = min(nms_pre, N) (nms_pre <= 0: N), M = min(nms_post, max_num).  Per sample:
+ *   1. per anchor: best = the maximum of its C logits, label = the LOWEST class attaining it, dir = 1 iff dir_pred[1] >
+ *      dir_pred[0].  An anchor with a NaN class logit is never a candidate.
+ *   2. the candidates: the cap anchors (all, where fewer are without NaN) with the largest best, in descending order, equal
+ *      logits (-0 == +0) by ASCENDING anchor index — a per-sample radix select on order-preserving 32-bit keys of the LOGIT, the
+ *      boundary key's holders taken by ascending index, the survivors ordered by counting.  (The reference ranks the sigmoid
+ *      VALUES with an unspecified tie order: the two orders differ only among logits whose sigmoid rounds to the same fp32.)
+ *   3. per candidate: score = sigmoid(best); the box is DeltaXYZWLHRBBoxCoder.decode: za = az + ah / 2, diagonal =
+ *      sqrt(al * al + aw * aw), x = t0 * diagonal + ax, y = t1 * diagonal + ay, z = t2 * ah + za, l = fx_expf(t4) * al,
+ *      w = fx_expf(t3) * aw, h = fx_expf(t5) * ah, r = t6 + ar, z = z - h / 2, box = [x, y, z, w, l, h, r]; the NMS box is
+ *      xywhr2xyxyr of [x, y, w, l, r]: [x - w / 2, y - l / 2, x + w / 2, y + l / 2, r].
+ *   4. the candidates with score > score_thr, STRICTLY, take part in the NMS: their number cnt is counted on the device and the
+ *      first cnt candidates of the order are taken (the passing candidates are a prefix of the order wherever the sigmoid's
+ *      rounding is monotone).  use_rotate_nms != 0: rnms_batched mode 0 (rotated BEV IoU), else mode 1 (axis-aligned), at
+ *      nms_thr, greedy in the selection order.
+ *   5. the first min(num_keep, M) kept candidates are the sample's rows (the reference's "sort by score and cut to max_num" is
+ *      the identity on a list that is already non-increasing); num_keep == -1 (the scan gave up) gives batch_cnt -1 and no row.
+ *   6. on the kept rows: yaw = (v - floor(v / pi + dir_limit_offset) * pi) + dir_offset + pi * dir, v = yaw - dir_offset, pi the
+ *      fp32 value; cls_preds[c] = sigmoid(logit_c) — the sigmoid scores in EVERY case.
+ * Outputs, EVERY element written by every call, the samples packed back to back: boxes_3d (B*M, 7), scores_3d (B*M), labels_3d
+ * (B*M) int64, cls_preds (B*M, C), rois (B*M, 8) = [batch id, box], batch_cnt (B) int32; rows past the counts' sum: batch id -1,
+ * label -1, zeros (gd3d_roi_assign_sample's convention).  Optional (NULL: not written): cand_inds (B, cap) int64 the candidates'
+ * anchor indices in the selection order, -1 past them; cand_cnt (B) int32 = cnt.
+ * workspace: gd3d_rpn_proposal_workspace_bytes(B, A, C, H, W, nms_pre) bytes, from shapes alone (0: the shapes are refused).
+ * B, A, C, H, W, nms_post or max_num < 1, a NaN parameter, a NULL operand, a short workspace: GD3D_E_BADARG.  C > 16, B > 1024,
+ * N >= 2^30, cap > 16384: GD3D_E_TOOLARGE.
+ * `_cpu` twin (csrc/rpn_proposal_cpu.cpp): the same contract on HOST memory on the calling thread, a stable sort and
+ *   rnms_bev_cpu / rnms_normal_bev_cpu; every output BIT-IDENTICAL to the kernels'; workspace is ignored.
+ * ---------------------------------------------------------------------------------- */
+size_t gd3d_rpn_proposal_workspace_bytes(int32_t B, int32_t A, int32_t C, int32_t H, int32_t W, int32_t nms_pre);
+int gd3d_rpn_proposals(const float* cls_score, const float* bbox_pred, const float* dir_cls_pred, const float* anchors, int32_t B,
+                       int32_t A, int32_t C, int32_t H, int32_t W, int32_t nms_pre, int32_t nms_post, int32_t max_num, float nms_thr,
+                       float score_thr, int32_t use_rotate_nms, float dir_offset, float dir_limit_offset, float* boxes_3d,
+                       float* scores_3d, int64_t* labels_3d, float* cls_preds, float* rois, int32_t* batch_cnt, int64_t* cand_inds,
+                       int32_t* cand_cnt, void* workspace, size_t workspace_bytes, void* stream);
+int gd3d_rpn_proposals_cpu(const float* cls_score, const float* bbox_pred, const float* dir_cls_pred, const float* anchors, int32_t B,
+                           int32_t A, int32_t C, int32_t H, int32_t W, int32_t nms_pre, int32_t nms_post, int32_t max_num,
+                           float nms_thr, float score_thr, int32_t use_rotate_nms, float dir_offset, float dir_limit_offset,
+                           float* boxes_3d, float* scores_3d, int64_t* labels_3d, float* cls_preds, float* rois, int32_t* batch_cnt,
+                           int64_t* cand_inds, int32_t* cand_cnt, void* workspace, size_t workspace_bytes);
+
 /* Library identification: returns GD3D_ABI_VERSION; *arch (if non-NULL) receives a static
  * string naming the code-object target, e.g. "gfx950". */
 int gd3d_abi_version(const char** arch);

@@ -80,6 +80,7 @@ from .voxelize import HardSimpleVFE, Voxelization, dynamic_voxelize, hard_voxeli
 from .pillar_feat import PillarFeatureDecorator, PointVoxelStatsCalculator, pillar_decorate, point_voxel_stats
 from .view_net import PointPillarsScatter, multi_view_voxelize, pillar_scatter, to_cylindrical, to_spherical, view_sample
 from .simota import Point3DRangeGenerator, SimOTABEVAssigner, simota_assign
+from .rpn_proposal import PartA2RPNHeadProposals, rpn_proposals
 from .sparse_tensor import SparseConvTensor, SparseModule, SparseSequential, ToDense, sparse_to_dense
 from .sparse_conv import (FusedSparseConv, SparseConv3d, SparseConvIndex, SparseInverseConv3d, SubMConv3d, sparse_conv, sparse_conv_index,
                           sparse_conv_index_inverse, sparse_inverse_conv)
@@ -116,4 +117,5 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'sparse_to_dense', 'SparseConvIndex', 'SparseConvTensor', 'SparseModule', 'SubMConv3d', 'SparseConv3d', 'SparseSequential', 'SparseBasicBlock',
            'make_sparse_convmodule', 'SparseEncoder', 'MlvlSparseEncoder', 'fuse_sparse_conv_bn', 'FusedSparseConv', 'FusedSparseBasicBlock', 'sparse_batch_norm',
            'SparseBatchNorm1d', 'SparseNormBasicBlock', 'convert_sparse_batchnorm', 'sparse_conv_index_inverse', 'sparse_inverse_conv', 'SparseInverseConv3d',
-           'make_sparse_inverse_convmodule', 'sparse_max_pool', 'SparseMaxPool3d', 'ToDense', 'SparseUNet', 'extras']
+           'make_sparse_inverse_convmodule', 'sparse_max_pool', 'SparseMaxPool3d', 'ToDense', 'SparseUNet', 'rpn_proposals', 'PartA2RPNHeadProposals',
+           'extras']

@@ -356,6 +356,12 @@ SYMBOLS = {
     'gd3d_sparse_max_pool_backward': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
     'gd3d_sparse_max_pool_forward_cpu': (_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     'gd3d_sparse_max_pool_backward_cpu': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    # PV-RCNN's RPN proposal stage (csrc/rpn_proposal.hip)
+    'gd3d_rpn_proposal_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    'gd3d_rpn_proposals': (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _f32, _f32, _vp, _vp,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'gd3d_rpn_proposals_cpu': (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _f32, _f32, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 
