@@ -28,7 +28,8 @@ SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'gd3d_center_head.hip': ['-fno-hip-fp32-correctly-rounded-divide-sqrt', '-ffp-contract=fast'],
     'rbox.hip': ['-ffp-contract=off'],
     'voxel_scatter.hip': [],
-    'voxel_index.hip': [],                     # rocPRIM radix sort + scan between hand-written kernels
+    'device_sort.hip': [],                     # the one unit that includes rocPRIM: the radix sorts and scans of the three units below (integer code)
+    'voxel_index.hip': [],                     # device_sort.h's radix sort + scan between hand-written kernels
     'eval_match.hip': ['-ffp-contract=off'],
     'coders.hip': ['-ffp-contract=off'],      # same rounding sequence as the torch elementwise ops it replaces
     'vsa.hip': ['-ffp-contract=off'],         # ball-query membership and FPS arg-max decisions replay bit for bit in vsa_cpu.cpp
@@ -37,11 +38,11 @@ SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'roi_sample.hip': ['-ffp-contract=off'],  # the 3D IoU, hence every assignment and draw, replays bit for bit in roi_sample_cpu.cpp
     'seg_head.hip': ['-ffp-contract=off'],    # n_pos, the winner columns and the backward's row sums replay bit for bit in seg_head_cpu.cpp
     'vsa_bev.hip': ['-ffp-contract=off'],     # pixel coordinates, weights, interpolated values and voxel centres replay bit for bit in vsa_bev_cpu.cpp
-    'hard_voxel.hip': ['-ffp-contract=off'],  # a point's cell and the voxel mean replay bit for bit in hard_voxel_cpu.cpp; rocPRIM sort + scans as voxel_index.hip
+    'hard_voxel.hip': ['-ffp-contract=off'],  # a point's cell and the voxel mean replay bit for bit in hard_voxel_cpu.cpp; sort + scans from device_sort.h
     'pillar_feat.hip': ['-ffp-contract=off'],  # the voxel table, the centres, the offsets and the distance replay bit for bit in pillar_feat_cpu.cpp
     'view_net.hip': ['-ffp-contract=off'],     # the view transforms, the cells, the canvas and the sampled features replay bit for bit in view_net_cpu.cpp
     'simota.hip': ['-ffp-contract=off'],       # memberships, the IoU, the costs on fx_logf, both selections and every match replay bit for bit in simota_cpu.cpp
-    'sparse_conv.hip': ['-ffp-contract=off'],  # every table of the index build replays bit for bit in sparse_conv_cpu.cpp; explicit fmaf for the values; rocPRIM sort + scan
+    'sparse_conv.hip': ['-ffp-contract=off'],  # every table of the index build replays bit for bit in sparse_conv_cpu.cpp; explicit fmaf for the values; sorts + scan from device_sort.h
     'sparse_conv_16.hip': ['-ffp-contract=off'],  # the fp16 / bf16 forms on v_mfma_f32_16x16x32: the epilogues' fp32 sequences stay as written
     'sparse_conv_wgrad.hip': ['-ffp-contract=off'],  # the weight and bias gradient, one source for fp32 / fp16 / bf16: explicit fmaf in a fixed order
     'sparse_dense.hip': ['-ffp-contract=off'],     # dense() and its backward for 4- and 2-byte elements: copies only, flagged as the rest of the sparse conv

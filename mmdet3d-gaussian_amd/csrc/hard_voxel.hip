@@ -5,7 +5,7 @@
 // nothing back:
 //   key_kernel      one int64 key per point, b * G + (z * Gy + y) * Gx + x, or B * G for a dropped point
 //   radix sort      (key, point id) pairs, stable, over the key bits in use only: ascending point id inside a cell is the slot
-//                   order.  rocPRIM's device radix sort, as in voxel_index.hip.
+//                   order.  rocPRIM's device radix sort and scans, through csrc/device_sort.h.
 //   head_kernel     run heads of the sorted keys; marks, in POINT order, the first point of every cell
 //   two scans       max-scan of the head positions (every sorted point learns where its cell starts, hence its slot and its
 //                   cell's first point) and plus-scan, in point order, of the first-point marks (a cell's rank of appearance)
@@ -20,51 +20,45 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include "../../include/gd3d.h"
+#include "device_sort.h"
 #include "gd3d_fill.h"
+#include "gd3d_workspace.h"
 #include "hard_voxel_common.h"
 
 namespace hard_voxel {
 
-
-struct Layout {   // carve of the caller's workspace (all offsets multiples of 256 bytes)
-  size_t key_in, key_out, val_in, order, head_pos, seg, first, cum, cum_base, row_base, vstart, sort_tmp, scan_tmp, total;
-  size_t sort_bytes, scan_bytes;
+// The caller's workspace (256-byte aligned), carved: every buffer once.  At address 0 it is the size function.
+struct Work {
+  long long *key_in, *key_out;
+  int *val_in, *order, *head_pos, *seg, *first, *cum, *cum_base, *row_base, *vstart;
+  char *sort_tmp, *scan_tmp;
+  size_t sort_bytes = 0, scan_bytes = 0, bytes = 0;   // scan_bytes: the larger of the two scans'
+  hipError_t err;
+  Work(void* workspace, int64_t n, int64_t rows) {
+    size_t plus = 0;
+    err = gd3d::sort_pairs_temp_bytes((size_t)n, sort_bytes);
+    if (err == hipSuccess) err = gd3d::inclusive_max_temp_bytes((size_t)n, scan_bytes);
+    if (err == hipSuccess) err = gd3d::inclusive_sum_temp_bytes((size_t)n, plus);
+    if (err != hipSuccess) return;
+    scan_bytes = scan_bytes > plus ? scan_bytes : plus;
+    gd3d::Carver c(workspace, gd3d::Carver::CALLER_ALIGNED);
+    key_in = c.take<long long>((size_t)n);
+    key_out = c.take<long long>((size_t)n);
+    val_in = c.take<int>((size_t)n);
+    order = c.take<int>((size_t)n);
+    head_pos = c.take<int>((size_t)n);
+    seg = c.take<int>((size_t)n);
+    first = c.take<int>((size_t)n);
+    cum = c.take<int>((size_t)n);
+    cum_base = c.take<int>(MAX_B);
+    row_base = c.take<int>(MAX_B);
+    vstart = c.take<int>((size_t)rows);
+    sort_tmp = c.take<char>(sort_bytes);
+    scan_tmp = c.take<char>(scan_bytes);
+    bytes = c.bytes();
+  }
 };
-
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static hipError_t layout(int64_t n, int64_t rows, Layout& L) {
-  L.sort_bytes = 0;
-  hipError_t e = rocprim::radix_sort_pairs(nullptr, L.sort_bytes, (const long long*)nullptr, (long long*)nullptr, (const int*)nullptr,
-                                           (int*)nullptr, (size_t)n, 0, 64, (hipStream_t)0);
-  if (e != hipSuccess) return e;
-  size_t a = 0, b = 0;
-  e = rocprim::inclusive_scan(nullptr, a, (const int*)nullptr, (int*)nullptr, (size_t)n, rocprim::maximum<int>(), (hipStream_t)0);
-  if (e != hipSuccess) return e;
-  e = rocprim::inclusive_scan(nullptr, b, (const int*)nullptr, (int*)nullptr, (size_t)n, rocprim::plus<int>(), (hipStream_t)0);
-  if (e != hipSuccess) return e;
-  L.scan_bytes = a > b ? a : b;
-  size_t o = 0;
-  L.key_in = o; o += up256(sizeof(long long) * (size_t)n);
-  L.key_out = o; o += up256(sizeof(long long) * (size_t)n);
-  L.val_in = o; o += up256(sizeof(int) * (size_t)n);
-  L.order = o; o += up256(sizeof(int) * (size_t)n);
-  L.head_pos = o; o += up256(sizeof(int) * (size_t)n);
-  L.seg = o; o += up256(sizeof(int) * (size_t)n);
-  L.first = o; o += up256(sizeof(int) * (size_t)n);
-  L.cum = o; o += up256(sizeof(int) * (size_t)n);
-  L.cum_base = o; o += up256(sizeof(int) * MAX_B);
-  L.row_base = o; o += up256(sizeof(int) * MAX_B);
-  L.vstart = o; o += up256(sizeof(int) * (size_t)rows);
-  L.sort_tmp = o; o += up256(L.sort_bytes);
-  L.scan_tmp = o; o += up256(L.scan_bytes);
-  L.total = o;
-  return hipSuccess;
-}
 
 __global__ __launch_bounds__(BLOCK) void key_kernel(const float* __restrict__ points, long long n, long long stride,
                                                     const int32_t* __restrict__ cnt, int B, const Geometry g,
@@ -234,12 +228,6 @@ __global__ __launch_bounds__(BLOCK) void dynamic_kernel(const float* __restrict_
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 static unsigned blocks_of(long long threads) { return (unsigned)((threads + BLOCK - 1) / BLOCK); }   // threads <= 2^31 * 2^6
 
-static int key_bits(long long sentinel) {   // the bits of the largest key
-  int bits = 1;
-  while (bits < 63 && (sentinel >> bits) != 0) ++bits;
-  return bits;
-}
-
 static int launch_mean(const MeanArgs& a, hipStream_t s) {
   const bool vec = a.F == 4 && a.stride % 4 == 0 && aligned16(a.src) && aligned16(a.mean);
   if (vec) hipLaunchKernelGGL(mean_kernel<true>, dim3(blocks_of(a.rows)), dim3(BLOCK), 0, s, a);
@@ -255,9 +243,8 @@ extern "C" {
 
 size_t gd3d_hard_voxelize_workspace_bytes(int64_t N, int32_t B, int32_t max_voxels) {
   if (N <= 0 || N > 0x7fffffffLL || B <= 0 || max_voxels < 1) return 256;
-  Layout L;
-  if (layout(N, row_bound(N, B, max_voxels), L) != hipSuccess) return 0;
-  return L.total;
+  const Work w(nullptr, N, row_bound(N, B, max_voxels));
+  return w.err == hipSuccess ? w.bytes : 0;
 }
 
 int gd3d_hard_voxelize(const float* points, int64_t N, int64_t row_stride, int32_t C, const int32_t* points_batch_cnt, int32_t B,
@@ -281,21 +268,8 @@ int gd3d_hard_voxelize(const float* points, int64_t N, int64_t row_stride, int32
   }
   if (points == nullptr || workspace == nullptr || coors == nullptr || num_points == nullptr) return GD3D_E_BADARG;
   if (((uintptr_t)workspace & 255) != 0) return GD3D_E_BADARG;
-  Layout L;
-  hipError_t he = layout(N, rows, L);
-  if (he != hipSuccess) return (int)he;
-  char* w = (char*)workspace;
-  long long* key_in = (long long*)(w + L.key_in);
-  long long* key_out = (long long*)(w + L.key_out);
-  int* val_in = (int*)(w + L.val_in);
-  int* order = (int*)(w + L.order);
-  int* head_pos = (int*)(w + L.head_pos);
-  int* seg = (int*)(w + L.seg);
-  int* first = (int*)(w + L.first);
-  int* cum = (int*)(w + L.cum);
-  int* cum_base = (int*)(w + L.cum_base);
-  int* row_base = (int*)(w + L.row_base);
-  int* vstart = (int*)(w + L.vstart);
+  const Work w(workspace, N, rows);
+  if (w.err != hipSuccess) return (int)w.err;
   // padding slots, and the rows past the total: coors -1, num_points 0, zero features (the mean kernel writes its own zeros)
   if (voxels != nullptr) {
     e = gd3d::fill_words(voxels, sizeof(float) * (size_t)rows * (size_t)max_num_points * (size_t)C, 0u, s);
@@ -308,32 +282,29 @@ int gd3d_hard_voxelize(const float* points, int64_t N, int64_t row_stride, int32
   const long long sentinel = (long long)B * g.G;
   const unsigned blocks = blocks_of(N);
   hipLaunchKernelGGL(key_kernel, dim3(blocks), dim3(BLOCK), 0, s, points, (long long)N, (long long)row_stride, points_batch_cnt, (int)B,
-                     g, key_in, val_in);
-  size_t sb = L.sort_bytes;
-  he = rocprim::radix_sort_pairs((void*)(w + L.sort_tmp), sb, (const long long*)key_in, key_out, (const int*)val_in, order, (size_t)N, 0,
-                                 (unsigned)key_bits(sentinel), s);
+                     g, w.key_in, w.val_in);
+  hipError_t he = gd3d::sort_pairs(w.sort_tmp, w.sort_bytes, w.key_in, w.key_out, w.val_in, w.order, (size_t)N,
+                                   (unsigned)gd3d::key_bits(sentinel), s);
   if (he != hipSuccess) return (int)he;
-  hipLaunchKernelGGL(head_kernel, dim3(blocks), dim3(BLOCK), 0, s, (const long long*)key_out, (const int*)order, (long long)N, sentinel,
-                     head_pos, first);
-  size_t cb = L.scan_bytes;
-  he = rocprim::inclusive_scan((void*)(w + L.scan_tmp), cb, (const int*)head_pos, seg, (size_t)N, rocprim::maximum<int>(), s);
+  hipLaunchKernelGGL(head_kernel, dim3(blocks), dim3(BLOCK), 0, s, (const long long*)w.key_out, (const int*)w.order, (long long)N, sentinel,
+                     w.head_pos, w.first);
+  he = gd3d::inclusive_max(w.scan_tmp, w.scan_bytes, w.head_pos, w.seg, (size_t)N, s);
   if (he != hipSuccess) return (int)he;
-  cb = L.scan_bytes;
-  he = rocprim::inclusive_scan((void*)(w + L.scan_tmp), cb, (const int*)first, cum, (size_t)N, rocprim::plus<int>(), s);
+  he = gd3d::inclusive_sum(w.scan_tmp, w.scan_bytes, w.first, w.cum, (size_t)N, s);
   if (he != hipSuccess) return (int)he;
-  hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(BLOCK), 0, s, points_batch_cnt, (int)B, (long long)N, (const int*)cum,
-                     (const long long*)key_out, sentinel, (int)max_voxels, cum_base, row_base, voxel_batch_cnt, (long long*)num);
+  hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(BLOCK), 0, s, points_batch_cnt, (int)B, (long long)N, (const int*)w.cum,
+                     (const long long*)w.key_out, sentinel, (int)max_voxels, w.cum_base, w.row_base, voxel_batch_cnt, (long long*)num);
   ScatterArgs a;
   a.points = points; a.n = N; a.stride = row_stride; a.C = C; a.P = max_num_points; a.max_voxels = max_voxels;
   a.G = g.G; a.gx = g.gx; a.gy = g.gy; a.sentinel = sentinel;
-  a.skey = key_out; a.order = order; a.seg = seg; a.cum = cum; a.cum_base = cum_base; a.row_base = row_base;
-  a.voxels = voxels; a.coors = coors; a.num_points = num_points; a.vstart = vstart;
+  a.skey = w.key_out; a.order = w.order; a.seg = w.seg; a.cum = w.cum; a.cum_base = w.cum_base; a.row_base = w.row_base;
+  a.voxels = voxels; a.coors = coors; a.num_points = num_points; a.vstart = w.vstart;
   const bool vec = C == 4 && row_stride % 4 == 0 && aligned16(points) && aligned16(voxels);
   if (vec) hipLaunchKernelGGL(scatter_kernel<true>, dim3(blocks), dim3(BLOCK), 0, s, a);
   else hipLaunchKernelGGL(scatter_kernel<false>, dim3(blocks), dim3(BLOCK), 0, s, a);
   if (mean != nullptr) {
     MeanArgs m;
-    m.src = points; m.stride = row_stride; m.order = order; m.vstart = vstart; m.num_points = num_points; m.num = (const long long*)num;
+    m.src = points; m.stride = row_stride; m.order = w.order; m.vstart = w.vstart; m.num_points = num_points; m.num = (const long long*)num;
     m.rows = rows; m.P = max_num_points; m.F = num_features; m.mean = mean;
     return launch_mean(m, s);
   }

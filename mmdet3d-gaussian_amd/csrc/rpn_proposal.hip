@@ -33,39 +33,6 @@ namespace rpn_proposal {
 
 static_assert(WG == BINS && WG == 4 * 64 && RANK_I == 64, "a thread per bin; four waves share a tile; a lane per ranked survivor");
 
-struct Args {
-  const float* cls;        // (B, A*C, H, W)
-  const float* bbox;       // (B, A*7, H, W)
-  const float* dirp;       // (B, A*2, H, W)
-  const float* anchors;    // (N, 7)
-  Params p;
-  int nblk;
-  int* hist;
-  int* nsurv;
-  int* cnt;
-  unsigned* keys;
-  int* tiecnt;
-  unsigned long long* surv;
-  int* sel;
-  float* box7;
-  float* bev5;
-  float* score;
-  int* label;
-  int* dir;
-  long long* order;
-  float* thresh;
-  const long long* keep;
-  const long long* num_keep;
-  float* boxes_3d;
-  float* scores_3d;
-  long long* labels_3d;
-  float* cls_preds;
-  float* rois;
-  int* batch_cnt;
-  long long* cand_inds;    // nullable
-  int* cand_cnt;           // nullable
-};
-
 // histogram add with two rounds of peer aggregation (trained maps put most anchors into a handful of exponent bins, and 64 lanes
 // adding to one LDS word are served one after the other); every lane of the wave calls it
 __device__ __forceinline__ void hist_add(int* hist, int bin, bool valid) {
@@ -421,9 +388,9 @@ using namespace rpn_proposal;
 extern "C" {
 
 size_t gd3d_rpn_proposal_workspace_bytes(int32_t B, int32_t A, int32_t C, int32_t H, int32_t W, int32_t nms_pre) {
-  Params p;
-  if (check_args(B, A, C, H, W, nms_pre, 1, 1, 0.0f, 0.0f, 1, 0.0f, 0.0f, p) != 0) return 0;
-  return make_layout(p.B, p.N, p.cap, rnms_batched_workspace_bytes(p.B, p.cap)).bytes;
+  Args a;
+  if (check_args(B, A, C, H, W, nms_pre, 1, 1, 0.0f, 0.0f, 1, 0.0f, 0.0f, a.p) != 0) return 0;
+  return carve(a, nullptr, rnms_batched_workspace_bytes(a.p.B, a.p.cap)).bytes;
 }
 
 int gd3d_rpn_proposals(const float* cls_score, const float* bbox_pred, const float* dir_cls_pred, const float* anchors, int32_t B,
@@ -438,31 +405,13 @@ int gd3d_rpn_proposals(const float* cls_score, const float* bbox_pred, const flo
       scores_3d == nullptr || labels_3d == nullptr || cls_preds == nullptr || rois == nullptr || batch_cnt == nullptr ||
       workspace == nullptr)
     return GD3D_E_BADARG;
-  const Layout l = make_layout(a.p.B, a.p.N, a.p.cap, rnms_batched_workspace_bytes(a.p.B, a.p.cap));
-  if (workspace_bytes < l.bytes) return GD3D_E_BADARG;
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  const Carved w = carve(a, workspace, rnms_batched_workspace_bytes(a.p.B, a.p.cap));
+  if (workspace_bytes < w.bytes) return GD3D_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
   a.cls = cls_score;
   a.bbox = bbox_pred;
   a.dirp = dir_cls_pred;
   a.anchors = anchors;
-  a.nblk = l.nblk;
-  a.hist = (int*)(w + l.hist);
-  a.nsurv = (int*)(w + l.nsurv);
-  a.cnt = (int*)(w + l.cnt);
-  a.keys = (unsigned*)(w + l.keys);
-  a.tiecnt = (int*)(w + l.tiecnt);
-  a.surv = (unsigned long long*)(w + l.surv);
-  a.sel = (int*)(w + l.sel);
-  a.box7 = (float*)(w + l.box7);
-  a.bev5 = (float*)(w + l.bev5);
-  a.score = (float*)(w + l.score);
-  a.label = (int*)(w + l.label);
-  a.dir = (int*)(w + l.dir);
-  a.order = (long long*)(w + l.order);
-  a.thresh = (float*)(w + l.thresh);
-  a.keep = (const long long*)(w + l.keep);
-  a.num_keep = (const long long*)(w + l.num_keep);
   a.boxes_3d = boxes_3d;
   a.scores_3d = scores_3d;
   a.labels_3d = (long long*)labels_3d;
@@ -471,9 +420,9 @@ int gd3d_rpn_proposals(const float* cls_score, const float* bbox_pred, const flo
   a.batch_cnt = batch_cnt;
   a.cand_inds = (long long*)cand_inds;
   a.cand_cnt = cand_cnt;
-  rc = gd3d::fill_words(w + l.zero, l.zero_bytes, 0u, s);
+  rc = gd3d::fill_words(a.hist, w.zero_bytes, 0u, s);
   if (rc != 0) return rc;
-  const dim3 wg(WG), ranks((unsigned)((a.p.cap + RANK_I - 1) / RANK_I), (unsigned)B), cells((unsigned)((a.p.HW + WG - 1) / WG), (unsigned)B), spans((unsigned)l.nblk, (unsigned)B),
+  const dim3 wg(WG), ranks((unsigned)((a.p.cap + RANK_I - 1) / RANK_I), (unsigned)B), cells((unsigned)((a.p.HW + WG - 1) / WG), (unsigned)B), spans((unsigned)a.nblk, (unsigned)B),
       cands((unsigned)((a.p.cap + WG - 1) / WG), (unsigned)B);
   hipLaunchKernelGGL(key_kernel, cells, wg, 0, s, a);
   for (int level = 1; level < LEVELS; ++level) hipLaunchKernelGGL(hist_kernel, spans, wg, 0, s, a, level);
@@ -483,8 +432,8 @@ int gd3d_rpn_proposals(const float* cls_score, const float* bbox_pred, const flo
   hipLaunchKernelGGL(gather_kernel, cands, wg, 0, s, a);
   rc = (int)hipGetLastError();
   if (rc != 0) return rc;
-  rc = rnms_batched(a.p.rotate ? 0 : 1, a.bev5, (const int64_t*)a.order, a.cnt, B, a.p.cap, a.thresh, (int64_t*)(w + l.keep),
-                    (int64_t*)(w + l.num_keep), w + l.nms, stream);
+  rc = rnms_batched(a.p.rotate ? 0 : 1, a.bev5, (const int64_t*)a.order, a.cnt, B, a.p.cap, a.thresh, (int64_t*)a.keep,
+                    (int64_t*)a.num_keep, w.nms, stream);
   if (rc != 0) return rc;
   hipLaunchKernelGGL(finish_kernel, dim3((unsigned)B), wg, 0, s, a);
   return (int)hipGetLastError();

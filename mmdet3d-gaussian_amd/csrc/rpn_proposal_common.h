@@ -2,10 +2,11 @@
 // every value and decision of the RPN proposal stage (mmdet3d's PartA2RPNHead.get_bboxes_single + class_agnostic_nms, restated in
 // include/gd3d.h) that is not a loop over anchors, each as ONE fixed sequence of fp32 operations: the per-anchor reduction and
 // its order key, the sigmoid on fx_expf (csrc/fx_exp.h), the DeltaXYZWLHR decode with the NMS box, the direction fix, the
-// argument checks and the workspace layout.  Both units are compiled with -ffp-contract=off, so every output is the same bits on
-// the device and on the host.
+// argument checks, the launches' arguments and the carve of the workspace.  Both units are compiled with -ffp-contract=off, so
+// every output is the same bits on the device and on the host.
 #pragma once
 #include "fx_exp.h"
+#include "gd3d_workspace.h"
 
 #include <stddef.h>
 #include <stdint.h>
@@ -27,47 +28,76 @@ struct Params {
   float nms_thr, score_thr, dir_offset, dir_limit_offset;
 };
 
-// ---- workspace: sized from shapes alone ------------------------------------------------------------------------------------------
-struct Layout {
-  size_t zero, zero_bytes;   // the block one fill clears:
-  size_t hist;               //   int32 [B][LEVELS][BINS]  keys per digit under the prefix the levels above resolved
-  size_t nsurv;              //   int32 [B]                survivors above the boundary key appended so far
-  size_t cnt;                //   int32 [B]                candidates with score > score_thr
-  size_t keys;               // uint32 [B][N]              order keys, 0 for an anchor that is no candidate
-  size_t tiecnt;             // int32 [B][nblk]            keys equal to the boundary key in each span
-  size_t surv;               // uint64 [B][cap]            (key, ~index) of the survivors, in no order
-  size_t sel;                // int32 [B][cap]             their anchor indices in the selection order
-  size_t box7, bev5, score, label, dir;   // per candidate, in the selection order
-  size_t order, thresh, keep, num_keep, nms;   // the operands of rnms_batched
-  size_t bytes;
-  int nblk;
+// ---- the launches' arguments and the workspace, sized from shapes alone --------------------------------------------------------
+struct Args {
+  const float* cls;        // (B, A*C, H, W)
+  const float* bbox;       // (B, A*7, H, W)
+  const float* dirp;       // (B, A*2, H, W)
+  const float* anchors;    // (N, 7)
+  Params p;
+  int nblk;                // spans of SPAN keys in a sample
+  // the workspace (carve):
+  int* hist;               // [B][LEVELS][BINS]  keys per digit under the prefix the levels above resolved
+  int* nsurv;              // [B]                survivors above the boundary key appended so far
+  int* cnt;                // [B]                candidates with score > score_thr
+  unsigned* keys;          // [B][N]             order keys, 0 for an anchor that is no candidate
+  int* tiecnt;             // [B][nblk]          keys equal to the boundary key in each span
+  unsigned long long* surv;   // [B][cap]        (key, ~index) of the survivors, in no order
+  int* sel;                // [B][cap]           their anchor indices in the selection order
+  float* box7;             // per candidate, in the selection order: box7 .. dir
+  float* bev5;
+  float* score;
+  int* label;
+  int* dir;
+  long long* order;        // the operands of rnms_batched: order, cnt, thresh, keep, num_keep
+  float* thresh;
+  const long long* keep;
+  const long long* num_keep;
+  float* boxes_3d;
+  float* scores_3d;
+  long long* labels_3d;
+  float* cls_preds;
+  float* rois;
+  int* batch_cnt;
+  long long* cand_inds;    // nullable
+  int* cand_cnt;           // nullable
 };
-inline size_t round256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline Layout make_layout(int64_t B, int64_t N, int64_t cap, size_t nms_bytes) {
-  Layout l;
-  size_t o = 0;
-  l.nblk = (int)((N + SPAN - 1) / SPAN);
-  l.zero = o;
-  l.hist = o; o += round256((size_t)B * LEVELS * BINS * 4);
-  l.nsurv = o; o += round256((size_t)B * 4);
-  l.cnt = o; o += round256((size_t)B * 4);
-  l.zero_bytes = o - l.zero;
-  l.keys = o; o += round256((size_t)B * (size_t)N * 4);
-  l.tiecnt = o; o += round256((size_t)B * (size_t)l.nblk * 4);
-  l.surv = o; o += round256((size_t)B * (size_t)cap * 8);
-  l.sel = o; o += round256((size_t)B * (size_t)cap * 4);
-  l.box7 = o; o += round256((size_t)B * (size_t)cap * 28);
-  l.bev5 = o; o += round256((size_t)B * (size_t)cap * 20);
-  l.score = o; o += round256((size_t)B * (size_t)cap * 4);
-  l.label = o; o += round256((size_t)B * (size_t)cap * 4);
-  l.dir = o; o += round256((size_t)B * (size_t)cap * 4);
-  l.order = o; o += round256((size_t)B * (size_t)cap * 8);
-  l.thresh = o; o += round256((size_t)B * 4);
-  l.keep = o; o += round256((size_t)B * (size_t)cap * 8);
-  l.num_keep = o; o += round256((size_t)B * 8);
-  l.nms = o; o += round256(nms_bytes);
-  l.bytes = o + 256;
-  return l;
+
+// What of the workspace is no kernel argument: the block one fill clears (hist, nsurv, cnt: contiguous and first), the workspace of
+// rnms_batched, the size the entry asks of its caller.
+struct Carved {
+  size_t zero_bytes;
+  void* nms;
+  size_t bytes;
+};
+
+// The workspace of a.p (B, N, cap) cut into a's buffers, every buffer once; the base is rounded up to 256 bytes here.  At address 0
+// it is the size function.
+inline Carved carve(Args& a, void* workspace, size_t nms_bytes) {
+  const size_t B = (size_t)a.p.B, N = (size_t)a.p.N, cap = (size_t)a.p.cap;
+  gd3d::Carver c(workspace, gd3d::Carver::SELF_ALIGNING);
+  Carved r;
+  a.nblk = (int)((N + SPAN - 1) / SPAN);
+  a.hist = c.take<int>(B * LEVELS * BINS);
+  a.nsurv = c.take<int>(B);
+  a.cnt = c.take<int>(B);
+  a.keys = c.take<unsigned>(B * N);
+  r.zero_bytes = (size_t)((uintptr_t)a.keys - (uintptr_t)a.hist);
+  a.tiecnt = c.take<int>(B * (size_t)a.nblk);
+  a.surv = c.take<unsigned long long>(B * cap);
+  a.sel = c.take<int>(B * cap);
+  a.box7 = c.take<float>(B * cap * 7);
+  a.bev5 = c.take<float>(B * cap * 5);
+  a.score = c.take<float>(B * cap);
+  a.label = c.take<int>(B * cap);
+  a.dir = c.take<int>(B * cap);
+  a.order = c.take<long long>(B * cap);
+  a.thresh = c.take<float>(B);
+  a.keep = c.take<long long>(B * cap);
+  a.num_keep = c.take<long long>(B);
+  r.nms = c.take<char>(nms_bytes);
+  r.bytes = c.bytes();
+  return r;
 }
 
 // the entry points' argument checks (csrc/rpn_proposal_cpu.cpp): one text for the launches and for the twin

@@ -25,33 +25,6 @@
 
 namespace simota {
 
-struct Args {
-  const float* scores;        // (P, C)
-  const float* boxes;         // (P, 7)
-  const float* priors;        // (prior_rows, stride)
-  long long prior_rows, prior_stride;
-  int shared;
-  const int32_t* pcnt;        // (B)
-  long long P;
-  const float* gt;            // (G, 7)
-  const int64_t* glabel;      // (G)
-  const int32_t* gcnt;        // (B)
-  long long G;
-  int B, G_cap;
-  Params prm;
-  int64_t* gt_inds;           // (P)
-  int64_t* labels;            // (P)
-  float* max_overlaps;        // (P)
-  int32_t* pos_cnt;           // (B)
-  int64_t* pos_inds;          // (B, G_cap * K)
-  int64_t* pos_gt_inds;       // (B, G_cap * K)
-  int32_t* cand_cnt;          // workspace, csrc/simota_common.h: Layout
-  int32_t* cand;
-  int32_t* match_prior;
-  float* match_iou;
-  int32_t* conflict;
-};
-
 __device__ __forceinline__ void load7(const float* p, float (&r)[7]) {
 #pragma unroll
   for (int k = 0; k < 7; ++k) r[k] = p[k];
@@ -435,9 +408,7 @@ int gd3d_simota_assign(const float* pred_scores, const float* decoded_bboxes, co
   if (G > 0 && (gt_bboxes == nullptr || gt_labels == nullptr)) return GD3D_E_BADARG;
   const long long L = (long long)G_cap * candidate_topk;
   if (L > 0 && (pos_inds == nullptr || pos_gt_inds == nullptr)) return GD3D_E_BADARG;
-  const Layout lay = make_layout(P, B, G_cap, candidate_topk);
-  if (workspace_bytes < lay.bytes) return GD3D_E_BADARG;
-  unsigned char* ws = reinterpret_cast<unsigned char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  if (workspace_bytes < carve(a, workspace, P, B, G_cap, candidate_topk)) return GD3D_E_BADARG;
   const int res_list = resolve_list_bytes((int)L);
   const int res_ctl = res_list > RES_MIN_LDS - 64 ? res_list : RES_MIN_LDS - 64;
   const int res_lds = res_ctl + 64;
@@ -456,11 +427,6 @@ int gd3d_simota_assign(const float* pred_scores, const float* decoded_bboxes, co
   a.shared = shared_priors; a.pcnt = prior_batch_cnt; a.P = P; a.gt = gt_bboxes; a.glabel = gt_labels; a.gcnt = gt_batch_cnt;
   a.G = G; a.B = B; a.G_cap = G_cap; a.gt_inds = gt_inds; a.labels = labels; a.max_overlaps = max_overlaps; a.pos_cnt = pos_cnt;
   a.pos_inds = pos_inds; a.pos_gt_inds = pos_gt_inds;
-  a.cand_cnt = reinterpret_cast<int32_t*>(ws + lay.cand_cnt);
-  a.cand = reinterpret_cast<int32_t*>(ws + lay.cand);
-  a.match_prior = reinterpret_cast<int32_t*>(ws + lay.match_prior);
-  a.match_iou = reinterpret_cast<float*>(ws + lay.match_iou);
-  a.conflict = reinterpret_cast<int32_t*>(ws + lay.conflict);
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(a.cand_cnt, 0, (size_t)B * 4, st);
   if (e != hipSuccess) return (int)e;

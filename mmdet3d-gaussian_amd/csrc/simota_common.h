@@ -6,6 +6,7 @@
 // units are compiled with -ffp-contract=off, so every decision is the same on the device and on the host.
 #pragma once
 #include "fx_log.h"
+#include "gd3d_workspace.h"
 #include "roi_sample_common.h"
 
 #include <stddef.h>
@@ -39,27 +40,46 @@ struct Params {
   float radius, iou_w, cls_w, match_init;
 };
 
-// ---- workspace: sized from shapes alone (csrc/simota_cpu.cpp: gd3d_simota_workspace_bytes) -----------------------------------
-struct Layout {
-  size_t cand_cnt;      // int32 [B]              candidates of a sample
-  size_t cand;          // int32 [P]              their prior indices within the sample, in the sample's own rows, in no order
-  size_t match_prior;   // int32 [B * G_cap * K]  the priors gt g took, -1 beyond its k
-  size_t match_iou;     // float [B * G_cap * K]  their IoU with g
-  size_t conflict;      // int32 [B * G_cap * K]  (prior, rank) of the priors more than one gt took
-  size_t bytes;
+// ---- the launches' arguments and the workspace, sized from shapes alone (csrc/simota_cpu.cpp: gd3d_simota_workspace_bytes) --------
+struct Args {
+  const float* scores;        // (P, C)
+  const float* boxes;         // (P, 7)
+  const float* priors;        // (prior_rows, stride)
+  long long prior_rows, prior_stride;
+  int shared;
+  const int32_t* pcnt;        // (B)
+  long long P;
+  const float* gt;            // (G, 7)
+  const int64_t* glabel;      // (G)
+  const int32_t* gcnt;        // (B)
+  long long G;
+  int B, G_cap;
+  Params prm;
+  int64_t* gt_inds;           // (P)
+  int64_t* labels;            // (P)
+  float* max_overlaps;        // (P)
+  int32_t* pos_cnt;           // (B)
+  int64_t* pos_inds;          // (B, G_cap * K)
+  int64_t* pos_gt_inds;       // (B, G_cap * K)
+  // the workspace (carve):
+  int32_t* cand_cnt;          // [B]              candidates of a sample
+  int32_t* cand;              // [P]              their prior indices within the sample, in the sample's own rows, in no order
+  int32_t* match_prior;       // [B * G_cap * K]  the priors gt g took, -1 beyond its k
+  float* match_iou;           // [B * G_cap * K]  their IoU with g
+  int32_t* conflict;          // [B * G_cap * K]  (prior, rank) of the priors more than one gt took
 };
-inline size_t round256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline Layout make_layout(int64_t P, int32_t B, int32_t G_cap, int32_t K) {
-  Layout l;
+
+// The workspace cut into a's buffers, every buffer once; the base is rounded up to 256 bytes here.  Returns the size the entry asks
+// of its caller: at address 0 it is the size function.
+inline size_t carve(Args& a, void* workspace, int64_t P, int32_t B, int32_t G_cap, int32_t K) {
   const size_t m = (size_t)B * (size_t)G_cap * (size_t)K;
-  size_t o = 0;
-  l.cand_cnt = o; o += round256((size_t)B * 4);
-  l.cand = o; o += round256((size_t)P * 4);
-  l.match_prior = o; o += round256(m * 4);
-  l.match_iou = o; o += round256(m * 4);
-  l.conflict = o; o += round256(m * 4);
-  l.bytes = o + 256;
-  return l;
+  gd3d::Carver c(workspace, gd3d::Carver::SELF_ALIGNING);
+  a.cand_cnt = c.take<int32_t>((size_t)B);
+  a.cand = c.take<int32_t>((size_t)P);
+  a.match_prior = c.take<int32_t>(m);
+  a.match_iou = c.take<float>(m);
+  a.conflict = c.take<int32_t>(m);
+  return c.bytes();
 }
 
 // the entry points' argument checks (csrc/simota_cpu.cpp): one text for the launch and for the twin

@@ -39,7 +39,8 @@ extern "C" {
 
 size_t gd3d_simota_workspace_bytes(int64_t P, int32_t B, int32_t G_cap, int32_t candidate_topk) {
   if (P < 0 || B < 0 || G_cap < 0 || candidate_topk < 0) return 0;
-  return make_layout(P, B, G_cap, candidate_topk).bytes;
+  Args a;
+  return carve(a, nullptr, P, B, G_cap, candidate_topk);
 }
 
 int gd3d_simota_assign_cpu(const float* pred_scores, const float* decoded_bboxes, const float* priors, int64_t prior_rows,

@@ -4,7 +4,7 @@
 // Every call is one stream-ordered run of launches that reads nothing back.
 //   index build   key_kernel     one int64 key per input row, ((b * D + z) * H + y) * W + x, or the sentinel B*D*H*W for an inactive row
 //                 radix sort     (key, row) pairs, stable: a look-up by lower bound finds the LOWEST row of a duplicated cell.  rocPRIM's
-//                                device radix sort, as in hard_voxel.hip.
+//                                device radix sort and scan, through csrc/device_sort.h.
 //                 submanifold    subm_kernel: a thread per (row, offset) looks its neighbour's coordinate up
 //                 regular        cand_kernel (the output cell of every (row, offset) pair, or the sentinel), a radix sort of those
 //                                keys, head flags, a plus-scan and a compaction give the unique output keys in ascending order;
@@ -20,11 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include "../../include/gd3d.h"
+#include "device_sort.h"
 #include "gd3d_fill.h"
+#include "gd3d_workspace.h"
 #include "sparse_conv_common.h"
 
 namespace sparse_conv {
@@ -34,43 +33,37 @@ constexpr int BLOCK = 256;
 static unsigned blocks_of(long long threads) { return (unsigned)((threads + BLOCK - 1) / BLOCK); }
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-static int key_bits(long long sentinel) {   // the bits of the largest key
-  int bits = 1;
-  while (bits < 63 && (sentinel >> bits) != 0) ++bits;
-  return bits;
-}
-
-struct Layout {   // carve of the caller's workspace (all offsets multiples of 256 bytes)
-  size_t key_in, skey, val_in, srow, cand, scand, flag, pos, sort_tmp, total;
-  size_t sort_bytes;
-};
-
-static hipError_t layout(int64_t n, int64_t m, bool subm, Layout& L) {   // m = n * K
-  size_t a = 0, b = 0, c = 0;
-  hipError_t e = rocprim::radix_sort_pairs(nullptr, a, (const long long*)nullptr, (long long*)nullptr, (const int*)nullptr,
-                                           (int*)nullptr, (size_t)n, 0, 64, (hipStream_t)0);
-  if (e != hipSuccess) return e;
-  if (!subm) {
-    e = rocprim::radix_sort_keys(nullptr, b, (const long long*)nullptr, (long long*)nullptr, (size_t)m, 0, 64, (hipStream_t)0);
-    if (e != hipSuccess) return e;
-    e = rocprim::exclusive_scan(nullptr, c, (const int*)nullptr, (int*)nullptr, 0, (size_t)m, rocprim::plus<int>(), (hipStream_t)0);
-    if (e != hipSuccess) return e;
+// The caller's workspace (256-byte aligned) of the index build, carved: every buffer once.  At address 0 it is the size function.
+struct Work {
+  long long *key_in, *skey;
+  int *val_in, *srow;
+  long long *cand, *scand, *ukey;   // the regular form's, m = n * K entries each (none in the submanifold form)
+  int *flag, *pos;
+  char* sort_tmp;                   // of both sorts and the scan, one after the other
+  size_t sort_bytes = 0, bytes = 0;
+  hipError_t err;
+  Work(void* workspace, int64_t n, int64_t m, bool subm) {
+    size_t keys = 0, scan = 0;
+    err = gd3d::sort_pairs_temp_bytes((size_t)n, sort_bytes);
+    if (err == hipSuccess && !subm) err = gd3d::sort_keys_temp_bytes((size_t)m, keys);
+    if (err == hipSuccess && !subm) err = gd3d::exclusive_sum_temp_bytes((size_t)m, scan);
+    if (err != hipSuccess) return;
+    sort_bytes = sort_bytes > keys ? sort_bytes : keys;
+    sort_bytes = sort_bytes > scan ? sort_bytes : scan;
+    const size_t mm = subm ? 0 : (size_t)m;
+    gd3d::Carver c(workspace, gd3d::Carver::CALLER_ALIGNED);
+    key_in = c.take<long long>((size_t)n);
+    skey = c.take<long long>((size_t)n);
+    val_in = c.take<int>((size_t)n);
+    srow = c.take<int>((size_t)n);
+    ukey = cand = c.take<long long>(mm);   // the candidates are sorted out of `cand`: it is free again when the unique keys are written
+    scand = c.take<long long>(mm);
+    flag = c.take<int>(mm);
+    pos = c.take<int>(mm);
+    sort_tmp = c.take<char>(sort_bytes);
+    bytes = c.bytes();
   }
-  L.sort_bytes = a > b ? (a > c ? a : c) : (b > c ? b : c);
-  size_t o = 0;
-  L.key_in = o; o += up256(sizeof(long long) * (size_t)n);
-  L.skey = o; o += up256(sizeof(long long) * (size_t)n);
-  L.val_in = o; o += up256(sizeof(int) * (size_t)n);
-  L.srow = o; o += up256(sizeof(int) * (size_t)n);
-  const size_t mm = subm ? 0 : (size_t)m;
-  L.cand = o; o += up256(sizeof(long long) * mm);
-  L.scand = o; o += up256(sizeof(long long) * mm);
-  L.flag = o; o += up256(sizeof(int) * mm);
-  L.pos = o; o += up256(sizeof(int) * mm);
-  L.sort_tmp = o; o += up256(L.sort_bytes);
-  L.total = o;
-  return hipSuccess;
-}
+};
 
 __global__ __launch_bounds__(BLOCK) void key_kernel(const int32_t* __restrict__ coors, long long n, const Geo g,
                                                     long long* __restrict__ keys, int* __restrict__ vals) {
@@ -372,9 +365,8 @@ extern "C" {
 
 size_t gd3d_sparse_conv_index_workspace_bytes(int64_t N, int32_t K, int32_t subm) {
   if (N <= 0 || K < 1 || K > MAX_K || N * K > 0x7fffffffLL) return 256;
-  Layout L;
-  if (layout(N, N * K, subm != 0, L) != hipSuccess) return 0;
-  return L.total;
+  const Work w(nullptr, N, N * K, subm != 0);
+  return w.err == hipSuccess ? w.bytes : 0;
 }
 
 int gd3d_sparse_conv_index(const int32_t* coors, int64_t N, int32_t B, const int32_t* spatial_shape, const int32_t* kernel_size,
@@ -401,48 +393,34 @@ int gd3d_sparse_conv_index(const int32_t* coors, int64_t N, int32_t B, const int
   if (coors == nullptr || workspace == nullptr || ((uintptr_t)workspace & 255) != 0) return GD3D_E_BADARG;
   if (!subm && nbr_t == nullptr) return GD3D_E_BADARG;
   const long long M = (long long)N * g.K;
-  Layout L;
-  hipError_t he = layout(N, M, subm != 0, L);
-  if (he != hipSuccess) return (int)he;
-  char* w = (char*)workspace;
-  long long* key_in = (long long*)(w + L.key_in);
-  long long* skey = (long long*)(w + L.skey);
-  int* val_in = (int*)(w + L.val_in);
-  int* srow = (int*)(w + L.srow);
-  hipLaunchKernelGGL(key_kernel, dim3(blocks_of(N)), dim3(BLOCK), 0, s, coors, (long long)N, g, key_in, val_in);
-  size_t sb = L.sort_bytes;
-  he = rocprim::radix_sort_pairs((void*)(w + L.sort_tmp), sb, (const long long*)key_in, skey, (const int*)val_in, srow, (size_t)N, 0,
-                                 (unsigned)key_bits(g.in_sent), s);
+  const Work w(workspace, N, M, subm != 0);
+  if (w.err != hipSuccess) return (int)w.err;
+  hipLaunchKernelGGL(key_kernel, dim3(blocks_of(N)), dim3(BLOCK), 0, s, coors, (long long)N, g, w.key_in, w.val_in);
+  hipError_t he = gd3d::sort_pairs(w.sort_tmp, w.sort_bytes, w.key_in, w.skey, w.val_in, w.srow, (size_t)N, (unsigned)gd3d::key_bits(g.in_sent), s);
   if (he != hipSuccess) return (int)he;
   if (subm) {
-    hipLaunchKernelGGL(subm_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, coors, (long long)N, g, (const long long*)skey,
-                       (const int*)srow, out_coors, nbr);
+    hipLaunchKernelGGL(subm_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, coors, (long long)N, g, (const long long*)w.skey,
+                       (const int*)w.srow, out_coors, nbr);
     // the sorted keys below the sentinel are the active rows: a sample's count is a difference of two lower bounds
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(BLOCK), 0, s, (const long long*)skey, (long long)N, (const int*)nullptr,
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(BLOCK), 0, s, (const long long*)w.skey, (long long)N, (const int*)nullptr,
                        (const int*)nullptr, 0LL, 0LL, g.in_sent, (int)B, 1, (long long*)num, out_batch_cnt);
     return (int)hipGetLastError();
   }
-  long long* cand = (long long*)(w + L.cand);
-  long long* scand = (long long*)(w + L.scand);
-  int* flag = (int*)(w + L.flag);
-  int* pos = (int*)(w + L.pos);
-  hipLaunchKernelGGL(cand_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, coors, (long long)N, g, cand);
-  sb = L.sort_bytes;
-  he = rocprim::radix_sort_keys((void*)(w + L.sort_tmp), sb, (const long long*)cand, scand, (size_t)M, 0, (unsigned)key_bits(g.out_sent), s);
+  hipLaunchKernelGGL(cand_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, coors, (long long)N, g, w.cand);
+  he = gd3d::sort_keys(w.sort_tmp, w.sort_bytes, w.cand, w.scand, (size_t)M, (unsigned)gd3d::key_bits(g.out_sent), s);
   if (he != hipSuccess) return (int)he;
-  hipLaunchKernelGGL(head_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, (const long long*)scand, M, g.out_sent, flag);
-  sb = L.sort_bytes;
-  he = rocprim::exclusive_scan((void*)(w + L.sort_tmp), sb, (const int*)flag, pos, 0, (size_t)M, rocprim::plus<int>(), s);
+  hipLaunchKernelGGL(head_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, (const long long*)w.scand, M, g.out_sent, w.flag);
+  he = gd3d::exclusive_sum(w.sort_tmp, w.sort_bytes, w.flag, w.pos, (size_t)M, s);
   if (he != hipSuccess) return (int)he;
-  long long* ukey = cand;                                        // the candidates are sorted out of this buffer: it is free again
-  hipLaunchKernelGGL(compact_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, (const long long*)scand, (const int*)flag, (const int*)pos, M, ukey);
-  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(BLOCK), 0, s, (const long long*)ukey, 0LL, (const int*)flag, (const int*)pos, M,
+  hipLaunchKernelGGL(compact_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, (const long long*)w.scand, (const int*)w.flag, (const int*)w.pos, M,
+                     w.ukey);
+  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(BLOCK), 0, s, (const long long*)w.ukey, 0LL, (const int*)w.flag, (const int*)w.pos, M,
                      (long long)max_out, g.out_sent, (int)B, 0, (long long*)num, out_batch_cnt);
   if (R > 0)
-    hipLaunchKernelGGL(out_kernel, dim3(blocks_of(R * g.K)), dim3(BLOCK), 0, s, (const long long*)ukey, (const long long*)num, (long long)R,
-                       (long long)N, g, (const long long*)skey, (const int*)srow, out_coors, nbr);
-  hipLaunchKernelGGL(nbrt_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, coors, (long long)N, g, (const long long*)skey, (const int*)srow,
-                     (const long long*)ukey, (const long long*)num, nbr_t);
+    hipLaunchKernelGGL(out_kernel, dim3(blocks_of(R * g.K)), dim3(BLOCK), 0, s, (const long long*)w.ukey, (const long long*)num, (long long)R,
+                       (long long)N, g, (const long long*)w.skey, (const int*)w.srow, out_coors, nbr);
+  hipLaunchKernelGGL(nbrt_kernel, dim3(blocks_of(M)), dim3(BLOCK), 0, s, coors, (long long)N, g, (const long long*)w.skey, (const int*)w.srow,
+                     (const long long*)w.ukey, (const long long*)num, nbr_t);
   return (int)hipGetLastError();
 }
 

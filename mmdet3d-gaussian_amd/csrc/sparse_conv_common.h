@@ -148,7 +148,6 @@ SC_HD long long row_limit(const long long* num, long long rows) {
 }
 
 inline int tile_of(int channels) { return channels <= 16 ? 16 : (channels <= 32 ? 32 : 64); }   // the smallest channel tile that holds them, at most 64
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // the geometry of dense(): a 1x1x1 layer over (B, D, H, W) with C channels
 inline int dense_geo(int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W, Geo* g) {

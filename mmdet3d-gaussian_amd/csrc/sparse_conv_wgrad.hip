@@ -13,6 +13,7 @@
 
 #include "../../include/gd3d.h"
 #include "gd3d_fill.h"
+#include "gd3d_workspace.h"
 #include "sparse_conv_common.h"
 
 namespace sparse_conv {
@@ -28,6 +29,14 @@ struct WgradArgs {
   float *part_w, *part_b;   // (parts, K, Cin, Cout) and (parts, Cout)
   float *gW, *gb;           // gb nullable
 };
+
+// part_w and part_b out of the caller's workspace (256-byte aligned), for the a.parts and a.Cout set.  At address 0 it is the size function.
+static size_t carve(WgradArgs& a, void* workspace, int64_t kcc) {
+  gd3d::Carver c(workspace, gd3d::Carver::CALLER_ALIGNED);
+  a.part_w = c.take<float>((size_t)a.parts * (size_t)kcc);
+  a.part_b = c.take<float>((size_t)a.parts * (size_t)a.Cout);
+  return c.bytes();
+}
 
 // grid (parts, K, tiles of TI x TO of W[j]): the partial sum of chunk p.  TI, TO in {16, 32, 64}: the smallest tiles that hold Cin and
 // Cout; a thread owns TI / 16 x TO / 16 elements.
@@ -193,8 +202,7 @@ static int backward_weight(size_t elem, int32_t dtype, const void* features, con
   a.X = features; a.gY = grad_out; a.nbr = nbr; a.num = (const long long*)num; a.n_src = N; a.rows = R;
   weight_parts(R, kcc, (int64_t*)&a.parts, (int64_t*)&a.chunk);
   a.K = K; a.Cin = Cin; a.Cout = Cout; a.tiles_co = 1;
-  a.part_w = (float*)workspace;
-  a.part_b = (float*)((char*)workspace + up256(sizeof(float) * (size_t)a.parts * (size_t)kcc));
+  carve(a, workspace, kcc);
   a.gW = grad_weight; a.gb = grad_bias;
   return sparse_elem::with_elem(dtype, [&](auto e) { return run_wgrad<decltype(e)>(a, s); });
 }
@@ -207,9 +215,11 @@ extern "C" {
 
 size_t gd3d_sparse_conv_backward_weight_workspace_bytes(int64_t R, int32_t K, int32_t Cin, int32_t Cout) {
   if (R <= 0 || check_channels(K, Cin, Cout) != 0) return 256;
-  int64_t parts, chunk;
-  weight_parts(R, (int64_t)K * Cin * Cout, &parts, &chunk);
-  return up256(sizeof(float) * (size_t)parts * (size_t)K * Cin * Cout) + up256(sizeof(float) * (size_t)parts * Cout);
+  const int64_t kcc = (int64_t)K * Cin * Cout;
+  WgradArgs a;
+  a.Cout = Cout;
+  weight_parts(R, kcc, (int64_t*)&a.parts, (int64_t*)&a.chunk);
+  return carve(a, nullptr, kcc);
 }
 
 int gd3d_sparse_conv_backward_weight(const float* features, const float* grad_out, const int32_t* nbr, const int64_t* num, int64_t N,

@@ -9,7 +9,7 @@
 //   radix sort     (key, point id) pairs, stable: ascending keys = lexicographically sorted unique rows = the reference's
 //                  unique_dim order, samples in batch order; ascending point id inside a voxel = the grouping the atomic-free
 //                  reduce / backward kernels of voxel_scatter.hip walk.  The sort is rocPRIM's device radix sort (the one
-//                  library primitive on this path; torch.sort runs the same one).
+//                  library primitive on this path; torch.sort runs the same one), reached through csrc/device_sort.h.
 //   head / scan / finish kernels: run heads -> voxel ids (inclusive scan), point -> voxel map, segment starts, counts,
 //                  decoded voxel coordinates, and the two numbers the host needs to size its views: voxels and dropped points.
 // Outputs are caller-allocated at their upper bounds (a voxel per point); nothing is read back inside the call.
@@ -17,44 +17,39 @@
 #include <stdint.h>
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include "../../include/gd3d.h"
+#include "device_sort.h"
+#include "gd3d_workspace.h"
 
 namespace voxidx {
 
 constexpr int MAX_DIM = 8;
 constexpr int T = 256;
 
-struct Layout {   // carve of the caller's workspace (all offsets multiples of 256 bytes)
-  size_t ext, key_in, key_out, val_in, heads, vids, sort_tmp, scan_tmp, total;
-  size_t sort_bytes, scan_bytes;
+// The caller's workspace (256-byte aligned), carved: every buffer once.  At address 0 it is the size function.
+struct Work {
+  int* ext;
+  long long *key_in, *key_out;
+  int *val_in, *heads, *vids;
+  char *sort_tmp, *scan_tmp;
+  size_t sort_bytes = 0, scan_bytes = 0, bytes = 0;
+  hipError_t err;
+  Work(void* workspace, int64_t n) {
+    err = gd3d::sort_pairs_temp_bytes((size_t)n, sort_bytes);
+    if (err == hipSuccess) err = gd3d::inclusive_sum_temp_bytes((size_t)n, scan_bytes);
+    if (err != hipSuccess) return;
+    gd3d::Carver c(workspace, gd3d::Carver::CALLER_ALIGNED);
+    ext = c.take<int>(MAX_DIM);
+    key_in = c.take<long long>((size_t)n);
+    key_out = c.take<long long>((size_t)n);
+    val_in = c.take<int>((size_t)n);
+    heads = c.take<int>((size_t)n);
+    vids = c.take<int>((size_t)n);
+    sort_tmp = c.take<char>(sort_bytes);
+    scan_tmp = c.take<char>(scan_bytes);
+    bytes = c.bytes();
+  }
 };
-
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static hipError_t layout(int64_t n, Layout& L) {
-  L.sort_bytes = 0;
-  L.scan_bytes = 0;
-  hipError_t e = rocprim::radix_sort_pairs(nullptr, L.sort_bytes, (const long long*)nullptr, (long long*)nullptr,
-                                           (const int*)nullptr, (int*)nullptr, (size_t)n, 0, 64, (hipStream_t)0);
-  if (e != hipSuccess) return e;
-  e = rocprim::inclusive_scan(nullptr, L.scan_bytes, (const int*)nullptr, (int*)nullptr, (size_t)n, rocprim::plus<int>(),
-                              (hipStream_t)0);
-  if (e != hipSuccess) return e;
-  size_t o = 0;
-  L.ext = o; o += up256(sizeof(int) * MAX_DIM);
-  L.key_in = o; o += up256(sizeof(long long) * (size_t)n);
-  L.key_out = o; o += up256(sizeof(long long) * (size_t)n);
-  L.val_in = o; o += up256(sizeof(int) * (size_t)n);
-  L.heads = o; o += up256(sizeof(int) * (size_t)n);
-  L.vids = o; o += up256(sizeof(int) * (size_t)n);
-  L.sort_tmp = o; o += up256(L.sort_bytes);
-  L.scan_tmp = o; o += up256(L.scan_bytes);
-  L.total = o;
-  return hipSuccess;
-}
 
 __global__ __launch_bounds__(T) void extent_kernel(const int* __restrict__ coors, long long n, int ndim, int* __restrict__ ext) {
   __shared__ int smax[MAX_DIM];
@@ -176,9 +171,8 @@ extern "C" {
 
 size_t vox_index_workspace_bytes(int64_t n, int32_t ndim) {
   if (n <= 0 || ndim <= 0 || ndim > MAX_DIM) return 256;
-  Layout L;
-  if (layout(n, L) != hipSuccess) return 0;
-  return L.total;
+  const Work w(nullptr, n);
+  return w.err == hipSuccess ? w.bytes : 0;
 }
 
 int vox_index_build(const int32_t* coors, int64_t n, int32_t ndim, void* workspace, int32_t* point2voxel_map,
@@ -191,35 +185,24 @@ int vox_index_build(const int32_t* coors, int64_t n, int32_t ndim, void* workspa
       counts == nullptr || voxel_coors == nullptr)
     return GD3D_E_BADARG;
   if (((uintptr_t)workspace & 255) != 0) return GD3D_E_BADARG;
-  Layout L;
-  hipError_t e = layout(n, L);
-  if (e != hipSuccess) return (int)e;
-  char* w = (char*)workspace;
-  int* ext = (int*)(w + L.ext);
-  long long* key_in = (long long*)(w + L.key_in);
-  long long* key_out = (long long*)(w + L.key_out);
-  int* val_in = (int*)(w + L.val_in);
-  int* heads = (int*)(w + L.heads);
-  int* vids = (int*)(w + L.vids);
-  e = hipMemsetAsync(ext, 0, sizeof(int) * MAX_DIM, s);
+  const Work w(workspace, n);
+  if (w.err != hipSuccess) return (int)w.err;
+  hipError_t e = hipMemsetAsync(w.ext, 0, sizeof(int) * MAX_DIM, s);
   if (e != hipSuccess) return (int)e;
   e = hipMemsetAsync(num, 0, 2 * sizeof(int64_t), s);
   if (e != hipSuccess) return (int)e;
   const unsigned blocks = (unsigned)((n + T - 1) / T);
   const unsigned rblocks = blocks < 1024u ? blocks : 1024u;
-  hipLaunchKernelGGL(extent_kernel, dim3(rblocks), dim3(T), 0, s, (const int*)coors, (long long)n, (int)ndim, ext);
-  hipLaunchKernelGGL(key_kernel, dim3(blocks), dim3(T), 0, s, (const int*)coors, (long long)n, (int)ndim, (const int*)ext, key_in,
-                     val_in);
-  size_t sb = L.sort_bytes;
-  e = rocprim::radix_sort_pairs((void*)(w + L.sort_tmp), sb, (const long long*)key_in, key_out, (const int*)val_in, (int*)order,
-                                (size_t)n, 0, 64, s);
+  hipLaunchKernelGGL(extent_kernel, dim3(rblocks), dim3(T), 0, s, (const int*)coors, (long long)n, (int)ndim, w.ext);
+  hipLaunchKernelGGL(key_kernel, dim3(blocks), dim3(T), 0, s, (const int*)coors, (long long)n, (int)ndim, (const int*)w.ext, w.key_in,
+                     w.val_in);
+  e = gd3d::sort_pairs(w.sort_tmp, w.sort_bytes, w.key_in, w.key_out, w.val_in, (int*)order, (size_t)n, 64, s);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(head_kernel, dim3(blocks), dim3(T), 0, s, (const long long*)key_out, (long long)n, heads);
-  size_t cb = L.scan_bytes;
-  e = rocprim::inclusive_scan((void*)(w + L.scan_tmp), cb, (const int*)heads, vids, (size_t)n, rocprim::plus<int>(), s);
+  hipLaunchKernelGGL(head_kernel, dim3(blocks), dim3(T), 0, s, (const long long*)w.key_out, (long long)n, w.heads);
+  e = gd3d::inclusive_sum(w.scan_tmp, w.scan_bytes, w.heads, w.vids, (size_t)n, s);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(finish_kernel, dim3(blocks), dim3(T), 0, s, (const long long*)key_out, (const int*)order, (const int*)heads,
-                     (const int*)vids, (long long)n, (int)ndim, (const int*)ext, (int*)point2voxel_map, (int*)seg,
+  hipLaunchKernelGGL(finish_kernel, dim3(blocks), dim3(T), 0, s, (const long long*)w.key_out, (const int*)order, (const int*)w.heads,
+                     (const int*)w.vids, (long long)n, (int)ndim, (const int*)w.ext, (int*)point2voxel_map, (int*)seg,
                      (int*)voxel_coors, (long long*)num);
   hipLaunchKernelGGL(counts_kernel, dim3(blocks), dim3(T), 0, s, (const int*)seg, (const long long*)num, (long long)n, (int*)counts);
   return (int)hipGetLastError();

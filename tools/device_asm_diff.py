@@ -10,7 +10,9 @@ the trees kernel by kernel, whichever translation unit a kernel is in: the funct
 normalisation is the function's index inside local labels (.LBB<i>_<k>, .Lfunc_end<i>, .LJTI<i>_<k>), which depends on the
 function's position in its file (and with its digits, the padding in front of a comment).
 Prints the kernels that are only in one tree, the ones that differ (with a unified diff), and exits 1 if any body or
-resource figure differs; kernels present on one side only are listed and do not fail the run.
+resource figure differs; kernels present on one side only are listed and do not fail the run.  A kernel that several units of one
+tree define (a library template instantiated in each) counts once when its copies are the same; one whose copies differ is listed
+with its units under a heading of its own, and its first copy is the one compared.
 --rename REGEX=REPL (repeatable) is re.sub(REGEX, REPL) over OLD's assembly text before anything is read from it, for a kernel whose
 mangled name changed because a template argument moved to another namespace: the renamed kernels then pair up and are compared as
 the others are.  A substitution and nothing more.
@@ -49,8 +51,9 @@ def compile_tree(tree, out, prefix, jobs):
 
 
 def kernels(paths, renames=()):
-    """kernel name -> (normalised body lines, descriptor lines)"""
-    out = {}
+    """kernel name -> (normalised body lines, descriptor lines), and name -> [units] for every name that is defined more than
+    once: with the same body and figures in every copy it counts once; with copies that differ, the first one read is compared"""
+    out, units, differ = {}, {}, set()
     for p in paths:
         text = open(p).read()
         for pattern, repl in renames:
@@ -64,10 +67,12 @@ def kernels(paths, renames=()):
             d1 = end + 1
             while lines[d1].lstrip().startswith(('.size', '.set', ';', '.section\t.AMDGPU.csdata')):
                 d1 += 1
-            assert name not in out, f'{name} is defined twice'
             norm = [PAD.sub(' ;', LOCAL.sub(lambda m: m.group(1), ln)) for ln in lines[start:d1]]
-            out[name] = (norm[:end - start], norm[end - start:])
-    return out
+            copy = (norm[:end - start], norm[end - start:])
+            units.setdefault(name, []).append(os.path.basename(p)[:-2])
+            if out.setdefault(name, copy) != copy:
+                differ.add(name)
+    return out, {n: (u, n in differ) for n, u in units.items() if len(u) > 1}
 
 
 def main():
@@ -87,7 +92,12 @@ def main():
             os.makedirs(d, exist_ok=True)
             renames = [r.split('=', 1) for r in a.rename] if tag == 'old' else ()
             sides.append(kernels(compile_tree(os.path.abspath(tree), d, a.units, a.jobs), renames))
-    old, new = sides
+    (old, old_dup), (new, new_dup) = sides
+    for tag, dup in (('OLD', old_dup), ('NEW', new_dup)):
+        bad_dup = sorted(n for n, (_, d) in dup.items() if d)
+        print(f'defined in more than one unit in {tag}: {len(dup) - len(bad_dup)} with identical copies, {len(bad_dup)} with DIFFERING COPIES')
+        for n in bad_dup:
+            print('   ', n, 'in', ', '.join(dup[n][0]))
     for tag, names in (('only in OLD', sorted(set(old) - set(new))), ('only in NEW', sorted(set(new) - set(old)))):
         print(f'{tag}: {len(names)}')
         for n in names:
