@@ -713,6 +713,81 @@ int gd3d_vsa_fps_stacked_cpu(const float* xyz, const int32_t* xyz_batch_cnt, int
                              int64_t* out, int32_t nthreads);
 
 /* ------------------------------------------------------------------------------------
+ * Voxel query and the fused voxel query-and-group (an addition inside ABI 6; csrc/voxel_query.hip): a query looks
+ * only at the cells of a window around its own cell instead of at every point of its sample.  Restated from the reference's
+ * ops/vsa/src/voxel_query_gpu.cu:10-89 (voxel_query_kernel_stack; wrapper voxel_query.cpp:28-44), which ships without a Python
+ * caller; the published op of that name is what Voxel R-CNN and PV-RCNN++ pool their RoI grids with.
+ *
+ * xyz (N,3) fp32: one point per row of coors (N,4) [b, z, y, x] on a grid (B, Z, Y, X) (every side <= 2^24, N <= 2^31 - 1);
+ * new_xyz (M,3) fp32 the queries; new_coords (M,4) int32 [b, z, y, x] a query's cell on the same grid (any int32 value).
+ * max_range: 3 HOST values (rz, ry, rx), each in [0, 16] (GD3D_E_TOOLARGE above).  1 <= nsample <= 1024 (GD3D_E_TOOLARGE above).
+ *
+ * Query m: radius2 = radius * radius (fp32).  The window is walked with dz slowest and dx fastest, each ascending from -r to +r.  A
+ * cell outside [0,Z) x [0,Y) x [0,X) is skipped.  The cell's row i is looked up; no row: the cell is skipped, and so is a looked-up
+ * row outside [0, N) (a caller's table may hold anything).
+ *   d2 = (nx-x)*(nx-x) + (ny-y)*(ny-y) + (nz-z)*(nz-z)   fp32, left to right, no fma contraction (the ball query's expression)
+ * The row is a member iff d2 <= radius2 — INCLUSIVE, where the ball query is strict; a NaN distance is no member (the reference's
+ * `dist2 > radius2` rejection lets NaN in).  The first nsample members in window order fill idx[m,:] with GLOBAL rows of xyz (the ball
+ * query's idx is local to the sample), the slots past the member count repeat the first member, cnt[m] = min(members, nsample).  An
+ * empty query gives idx[m,:] = 0 and empty_mask[m] = 1 (the reference writes -1 into slot 0 and leaves the rest untouched).  A query
+ * whose b is outside [0, B) is empty.  idx (M,nsample) int32; cnt (M) int32 and empty_mask (M) bytes are nullable.
+ *
+ * Two look-up forms; exactly one is handed in (table != NULL selects the table, skey / srow must then be NULL):
+ *   sorted keys : skey (N) int64 ascending with srow (N) int32, as gd3d_vsa_voxel_index writes them.  key = ((b*Z + z)*Y + y)*X + x;
+ *                 a row of coors with any coordinate outside the grid (the -1 tail of the static forms) gets the key B*Z*Y*X, sorts
+ *                 last and is never found.  The sort is stable: of several rows in one cell the LOWEST is the cell's row.
+ *   dense table : table (B,Z,Y,X) int32, the row of each cell or -1, as gd3d_vsa_voxel_table writes it (fill with -1, then the
+ *                 lowest row of every cell): the reference's form, for callers who hold one; indexed in 64 bits.
+ * gd3d_vsa_voxel_index: coors int32 (coors_is_int64 == 0) or int64; workspace: gd3d_vsa_voxel_index_workspace_bytes(N) bytes, 256-byte
+ * aligned, no initialisation.  No host read: every call here is stream-ordered and can be captured.
+ *
+ * gd3d_vsa_voxel_coords: new_coords[m] = [b, z, y, x] of new_xyz[m] (x, y, z).  b comes from new_xyz_batch_cnt (B) (counts clamped to
+ * the rows left, as everywhere in the stacked ops); a row past the counts' sum gets b = -1.  Per axis, in fp32:
+ *   c = floor((p - lo) / cell)   one subtraction, one correctly rounded division, one floor (gd3d_hard_voxelize's sequence)
+ * cell_size, range_min: 3 HOST values each, (x, y, z); cell_size > 0.  An axis for which -2^30 <= c < 2^30 does not hold (NaN, +-inf,
+ * 1e30) gives b = -1 and the coordinate 0.  Cells outside the grid are NOT clamped: their window may still reach in.
+ *
+ * gd3d_vsa_voxel_query_and_group: the query, then out (M, (use_xyz ? 3 : 0) + C, nsample) = [grouped xyz minus the query centre
+ * (use_xyz), grouped features (N,C)], every channel of an empty query zero: gd3d_vsa_query_and_group's block.  Its backward wrt
+ * features is gd3d_vsa_query_and_group_backward called with B = 1 and the counts {N} and {M}: global rows are then local rows.
+ * ---------------------------------------------------------------------------------- */
+size_t gd3d_vsa_voxel_index_workspace_bytes(int64_t N);
+int gd3d_vsa_voxel_index(const void* coors, int32_t coors_is_int64, int64_t N, int32_t B, int32_t Z, int32_t Y, int32_t X,
+                         void* workspace, int64_t* skey, int32_t* srow, void* stream);
+int gd3d_vsa_voxel_table(const void* coors, int32_t coors_is_int64, int64_t N, int32_t B, int32_t Z, int32_t Y, int32_t X,
+                         int32_t* table, void* stream);
+int gd3d_vsa_voxel_coords(const float* new_xyz, const int32_t* new_xyz_batch_cnt, int32_t B, int64_t M, const float* cell_size,
+                          const float* range_min, int32_t* new_coords, void* stream);
+int gd3d_vsa_voxel_query(const float* xyz, const float* new_xyz, const int32_t* new_coords, const int64_t* skey,
+                         const int32_t* srow, const int32_t* table, int32_t B, int32_t Z, int32_t Y, int32_t X, int64_t N,
+                         int64_t M, const int32_t* max_range, float radius, int32_t nsample, int32_t* idx, int32_t* cnt,
+                         uint8_t* empty_mask, void* stream);
+int gd3d_vsa_voxel_query_and_group(const float* xyz, const float* new_xyz, const int32_t* new_coords, const int64_t* skey,
+                                   const int32_t* srow, const int32_t* table, const float* features, int32_t B, int32_t Z,
+                                   int32_t Y, int32_t X, int64_t N, int64_t M, int32_t C, const int32_t* max_range,
+                                   float radius, int32_t nsample, int32_t use_xyz, float* out, int32_t* idx, int32_t* cnt,
+                                   uint8_t* empty_mask, void* stream);
+
+/* `_cpu` twins (csrc/voxel_query_cpu.cpp): the same contracts on HOST memory, plain loops over the window in the stated order with
+ * the same fp32 sequences, so every output is BIT-IDENTICAL to the kernels'.  The index twin ignores `workspace`.  nthreads <= 0:
+ * std::thread::hardware_concurrency(). */
+int gd3d_vsa_voxel_index_cpu(const void* coors, int32_t coors_is_int64, int64_t N, int32_t B, int32_t Z, int32_t Y, int32_t X,
+                             void* workspace, int64_t* skey, int32_t* srow);
+int gd3d_vsa_voxel_table_cpu(const void* coors, int32_t coors_is_int64, int64_t N, int32_t B, int32_t Z, int32_t Y, int32_t X,
+                             int32_t* table);
+int gd3d_vsa_voxel_coords_cpu(const float* new_xyz, const int32_t* new_xyz_batch_cnt, int32_t B, int64_t M,
+                              const float* cell_size, const float* range_min, int32_t* new_coords);
+int gd3d_vsa_voxel_query_cpu(const float* xyz, const float* new_xyz, const int32_t* new_coords, const int64_t* skey,
+                             const int32_t* srow, const int32_t* table, int32_t B, int32_t Z, int32_t Y, int32_t X, int64_t N,
+                             int64_t M, const int32_t* max_range, float radius, int32_t nsample, int32_t* idx, int32_t* cnt,
+                             uint8_t* empty_mask, int32_t nthreads);
+int gd3d_vsa_voxel_query_and_group_cpu(const float* xyz, const float* new_xyz, const int32_t* new_coords, const int64_t* skey,
+                                       const int32_t* srow, const int32_t* table, const float* features, int32_t B, int32_t Z,
+                                       int32_t Y, int32_t X, int64_t N, int64_t M, int32_t C, const int32_t* max_range,
+                                       float radius, int32_t nsample, int32_t use_xyz, float* out, int32_t* idx,
+                                       int32_t* cnt, uint8_t* empty_mask, int32_t nthreads);
+
+/* ------------------------------------------------------------------------------------
  * Point-in-rotated-box ops (an addition inside ABI 6): mmdet3d 1.0's roiaware_pool3d `points_in_boxes_part` and
  * `points_in_boxes_all` (third party, CUDA only), PointwiseMaskHead.get_targets
  * (models/roi_heads/mask_heads/pointwise_mask_head.py:62-92) for a whole batch in one launch, and the dense RoI grid points of

@@ -76,6 +76,7 @@ from .pvrcnn_train import pvrcnn_head_get_targets, pvrcnn_head_loss
 from .pvrcnn_sample import bbox_overlaps_3d, pvrcnn_assign_and_sample
 from .pvrcnn_seg import keypoint_reweight, pvrcnn_seg_loss
 from .vsa_bev import bev_interpolate, sample_keypoints, voxel_centers
+from .voxel_query import (VoxelQueryAndGroup, VoxelQueryIndex, voxel_point_indices, voxel_query, voxel_query_coords, voxel_query_index)
 from .voxelize import HardSimpleVFE, Voxelization, dynamic_voxelize, hard_voxelize, pvrcnn_voxelize, voxel_mean
 from .pillar_feat import PillarFeatureDecorator, PointVoxelStatsCalculator, pillar_decorate, point_voxel_stats
 from .view_net import PointPillarsScatter, multi_view_voxelize, pillar_scatter, to_cylindrical, to_spherical, view_sample
@@ -118,4 +119,4 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'make_sparse_convmodule', 'SparseEncoder', 'MlvlSparseEncoder', 'fuse_sparse_conv_bn', 'FusedSparseConv', 'FusedSparseBasicBlock', 'sparse_batch_norm',
            'SparseBatchNorm1d', 'SparseNormBasicBlock', 'convert_sparse_batchnorm', 'sparse_conv_index_inverse', 'sparse_inverse_conv', 'SparseInverseConv3d',
            'make_sparse_inverse_convmodule', 'sparse_max_pool', 'SparseMaxPool3d', 'ToDense', 'SparseUNet', 'rpn_proposals', 'PartA2RPNHeadProposals',
-           'extras']
+           'extras', 'voxel_query_index', 'voxel_point_indices', 'voxel_query_coords', 'voxel_query', 'VoxelQueryIndex', 'VoxelQueryAndGroup']

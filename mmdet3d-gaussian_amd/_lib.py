@@ -362,6 +362,22 @@ SYMBOLS = {
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'gd3d_rpn_proposals_cpu': (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _f32, _f32, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    # voxel query over a sorted voxel index or a dense table (csrc/voxel_query.hip)
+    'gd3d_vsa_voxel_index_workspace_bytes': (_sz, [_i64]),
+    'gd3d_vsa_voxel_index': (_int, [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'gd3d_vsa_voxel_table': (_int, [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'gd3d_vsa_voxel_coords': (_int, [_vp, _vp, _i32, _i64, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp, _vp]),
+    'gd3d_vsa_voxel_query': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, ctypes.POINTER(_i32), _f32, _i32, _vp, _vp,
+                                    _vp, _vp]),
+    'gd3d_vsa_voxel_query_and_group': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i32, ctypes.POINTER(_i32),
+                                              _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'gd3d_vsa_voxel_index_cpu': (_int, [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'gd3d_vsa_voxel_table_cpu': (_int, [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp]),
+    'gd3d_vsa_voxel_coords_cpu': (_int, [_vp, _vp, _i32, _i64, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp]),
+    'gd3d_vsa_voxel_query_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, ctypes.POINTER(_i32), _f32, _i32, _vp,
+                                        _vp, _vp, _i32]),
+    'gd3d_vsa_voxel_query_and_group_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i32,
+                                                  ctypes.POINTER(_i32), _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i32]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 

@@ -48,6 +48,7 @@ SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'sparse_dense.hip': ['-ffp-contract=off'],     # dense() and its backward for 4- and 2-byte elements: copies only, flagged as the rest of the sparse conv
     'sparse_bn.hip': ['-ffp-contract=off'],    # live-row BatchNorm: every multiply-add is an explicit fmaf, the order of every sum is fixed
     'sparse_pool.hip': ['-ffp-contract=off'],  # sparse max pooling: copies and plain fp32 adds in a fixed order replay bit for bit in sparse_pool_cpu.cpp
+    'voxel_query.hip': ['-ffp-contract=off'],   # memberships, slots, keys and query cells replay bit for bit in voxel_query_cpu.cpp; sort from device_sort.h, gather from vsa_gather.h
     'rpn_proposal.hip': ['-ffp-contract=off'],  # the order keys, the sigmoid and the decode on fx_expf, the threshold and the direction fix replay bit for bit in rpn_proposal_cpu.cpp
 }
 # The frozen round-3 extras OUTSIDE §8 (DESIGN_EXTRAS.md; include/gd3d_extras.h): a library of their own since round 6,
@@ -86,6 +87,7 @@ HOST_SOURCES = {
     'sparse_conv_16_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],  # widen, sparse_conv_cpu.cpp's loops, one rounding; _Float16 through F16C
     'sparse_bn_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],      # sparse_bn.hip's element sequences, the sums in fp64 per tile
     'sparse_pool_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],    # same for sparse_pool.hip: every output bit-identical
+    'voxel_query_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],    # same for voxel_query.hip: every output bit-identical
     'rpn_proposal_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],   # same for rpn_proposal.hip: every output bit-identical
 }
 HOST_COMMON = ['-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
