@@ -38,8 +38,10 @@ def build(force=False):
     if force or stale:
         subprocess.run(['make', '-C', HERE, '_build/libgd3d_oracle.so'] + (['-B'] if force else []),
                        check=True, capture_output=True)
-    if os.path.isdir('/root/reference') and (force or not ref_eval_path()):
-        subprocess.run(['make', '-C', HERE, 'ref'], check=True, capture_output=True)
+    if os.path.isdir('/root/reference'):
+        for target, path in (('ref_eval', ref_eval_path), ('ref_vsa', ref_vsa_path), ('ref_vox', ref_vox_path)):
+            if force or not path():
+                subprocess.run(['make', '-C', HERE, target], check=True, capture_output=True)
 
 
 _lib = None
@@ -300,6 +302,18 @@ def match_coco(cost_mat, cost_thrs, is_ignore, is_crowd):
 
 def ref_eval_path():
     hits = glob.glob(os.path.join(HERE, '_ref', 'ref_eval*.so'))
+    return hits[0] if hits else None
+
+
+def ref_vsa_path():
+    """oracle/_ref/ref_vsa.so: the reference's ball query, grouping, FPS and voxel query kernels (ref_vsa_bind.hip); None if absent."""
+    path = os.path.join(HERE, '_ref', 'ref_vsa.so')
+    return path if os.path.isfile(path) else None
+
+
+def ref_vox_path():
+    """oracle/_ref/ref_vox*.so: the reference's dynamic scatter as a torch extension (build_ref_vox.py); None if absent."""
+    hits = sorted(glob.glob(os.path.join(HERE, '_ref', 'ref_vox*.so')))
     return hits[0] if hits else None
 
 

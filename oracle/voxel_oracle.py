@@ -4,8 +4,10 @@ numpy restatement of the reference's dynamic point-to-voxel scatter ops (SURVEY.
   scatter_index  — /root/reference/mmdet3d_gaussian/ops/voxel/src/scatter_points_cuda.cu:221-251
   scatter_reduce — feats_reduce_kernel :80-104 (+ the mean division :212-213)
   backward       — :106-179 (sum/mean trace-back; max: the SMALLEST point index equal to the reduced value, atomicMin)
-PARITY UNPINNED: the reference implements these ops in CUDA only ("do not support cpu yet", voxelization.h:46,59,78),
-so nothing can be executed here to produce golden vectors; this file restates the kernels' documented semantics.
+PINNED ON THE DEVICE: the reference implements these ops in CUDA only ("do not support cpu yet", voxelization.h:46,59,78), so
+nothing can be executed on a CPU to produce golden vectors; its kernels are compiled for the GPU instead (oracle/build_ref_vox.py
+-> oracle/_ref/ref_vox.so) and tests/test_gpu_ref_kernels.py holds this file to them: the index with at::unique_dim's order, sum /
+mean / max and all three backwards bit for bit on exact inputs, sums within the fp32 rounding bound on random ones.
 Sum/mean in the reference accumulate with float atomics in arbitrary order; here in ascending point order (fp64 is used
 by the tests as the arbiter)."""
 import numpy as np

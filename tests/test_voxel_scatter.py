@@ -1,5 +1,6 @@
-"""§8f-4 dynamic scatter-reduce: oracle self-checks on CPU; GPU kernels vs the oracle (parity unpinned: the reference
-op is CUDA-only; see oracle/voxel_oracle.py)."""
+"""§8f-4 dynamic scatter-reduce: oracle self-checks on CPU; GPU kernels vs the oracle.  The oracle itself is pinned to the
+reference's own kernels (scatter_points_cuda.cu compiled for the device, oracle/_ref/ref_vox.so) by
+tests/test_gpu_ref_kernels.py; see oracle/voxel_oracle.py."""
 import numpy as np
 import pytest
 import torch

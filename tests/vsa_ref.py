@@ -103,10 +103,10 @@ def query_and_group(radius, nsample, xyz, xyz_cnt, new_xyz, new_cnt, features=No
     return out, idx, cnt, mask
 
 
-def fps(xyz, npoint):
+def fps(xyz, npoint, trace=None):
     """one sample (n, 3) -> (npoint,) int64: pick 0 is index 0, then the arg max of the running min of the squared distances to
     all earlier picks, the lowest index on exactly equal distances (np.argmax returns the first); n < npoint: the n picks
-    cyclically; n == 0: zeros"""
+    cyclically; n == 0: zeros.  `trace(p, t)` is called with the running minima from which pick p is about to be taken."""
     xyz = _f32(xyz).reshape(-1, 3)
     n = xyz.shape[0]
     out = np.zeros((npoint,), np.int64)
@@ -127,6 +127,8 @@ def fps(xyz, npoint):
         np.add(dx, dy, out=dx)
         np.add(dx, dz, out=dx)                                      # (dx * dx + dy * dy) + dz * dz
         np.copyto(t, dx, where=dx < t)                              # d < t ? d : t
+        if trace is not None:
+            trace(p, t)
         old = int(np.argmax(t))
         out[p] = old
     for j in range(picks, npoint):
