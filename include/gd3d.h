@@ -576,6 +576,55 @@ int eval_match_coco_cpu(const float* cost, const float* cost_thrs, const uint8_t
                         int32_t nthreads);
 
 /* ------------------------------------------------------------------------------------
+ * Flexible mAP: the records of a matcher result and the AP of every (group, threshold) over all records (an addition inside
+ * ABI 6; csrc/eval_ap.hip).  Replaces, above eval_match_coco, what
+ * /root/reference/mmdet3d_gaussian/core/evaluation/mean_ap_flexible.py does per frame (:98-126) and per dataset (:130-148, with
+ * mmdet's average_precision(mode='area')).  A group is one (class, breakdown) pair; a record is one detection of one group.
+ *
+ * eval_tp_records: matched (T, D) int32 as eval_match_coco wrote it, or NULL: no match at all (the empty branch, :98-104);
+ *   det_flag (D) and gt_flag (G >= 0) bytes: the detection / the gt lies in the breakdown; score (D) fp32; 1 <= T <= 32.
+ *   Writes D rows of four columns, each pointer at the row where the caller's block starts:
+ *     group = `group`, score = a copy, and with m = matched[t, d] (a value outside [-1, G) counts as -1; nothing is read out of range)
+ *     bit t of tp_bits  = m > -1,
+ *     bit t of msk_bits = (det_flag[d] && m == -1) || (m > -1 && gt_flag[m]).
+ *   One launch.
+ *
+ * eval_ap_accumulate: n records (n <= 2^31 - 1) in four columns, num_gt (K) int64, 1 <= K <= 2^20, 1 <= T <= 32
+ *   -> num_det (K, T) int64, recall (K, T) fp64, ap (K, T) fp64.
+ *   Rank order inside a group: descending score; equal scores (-0 == +0) in ascending row index; NaN scores first, among
+ *   themselves in ascending row index.  (numpy's reversed argsort with the ties made definite.)
+ *   A row whose group is outside [0, K) counts for nothing: that is how a static record buffer is padded.
+ *   For group g and threshold t take the rows of g whose msk bit t is set, in rank order, numbered j = 1..D:
+ *     h_j = the row's tp bit t (a tp bit on a row whose msk bit is clear is ignored);   c_j = h_1 + ... + h_j;
+ *     p_j = c_j / j, ONE IEEE fp64 division of the two integers;                        e_j = max over i >= j of p_i;
+ *     den = num_gt[g] > 0 ? (double)num_gt[g] : 1e-7      (the reference's max(num_gt, 1e-7));
+ *     num_det = D;   recall = D ? (double)c_D / den : 0;   ap = S / den,
+ *   where S is the sum of e_j over the rows with h_j, taken EXACTLY and rounded to fp64 once, to nearest even: every such e_j is a
+ *   fp64 in [2^-31, 1], a whole number of 2^-84, so the sum is an integer below 2^116 of those units; it is added in integers (the
+ *   order is immaterial) and only the total is rounded.  ap therefore carries two roundings, whatever n is.
+ *   No read-back, no float atomic, static shapes, capturable on one stream.  workspace: eval_ap_workspace_bytes(n, K, T) bytes,
+ *   256-byte aligned (the same carve at address 0; 0 for arguments out of range).
+ *   eval_ap_tile_rows(): sorted rows per workgroup of the scan kernels; eval_ap_scan_chunk_tiles(): tiles per iteration of the
+ *   carry scans between tiles (a loop: no capacity, another trip every that many tiles). */
+int eval_tp_records(const int32_t* matched, const uint8_t* det_flag, const uint8_t* gt_flag, const float* score, int32_t group,
+                    int64_t D, int64_t G, int32_t T, int32_t* out_group, float* out_score, uint32_t* out_tp_bits,
+                    uint32_t* out_msk_bits, void* stream);
+int32_t eval_ap_tile_rows(void);
+int32_t eval_ap_scan_chunk_tiles(void);
+size_t eval_ap_workspace_bytes(int64_t n, int64_t K, int32_t T);
+int eval_ap_accumulate(const int32_t* group, const float* score, const uint32_t* tp_bits, const uint32_t* msk_bits,
+                       const int64_t* num_gt, int64_t n, int64_t K, int32_t T, int64_t* num_det, double* recall, double* ap,
+                       void* workspace, void* stream);
+/* `_cpu` twins (csrc/eval_ap_cpu.cpp): the same contracts on HOST memory, plain loops over a stable sort; the same bits in all three
+ * outputs.  (group, threshold) pairs are spread over `nthreads` std::threads (<= 0: hardware concurrency). */
+int eval_tp_records_cpu(const int32_t* matched, const uint8_t* det_flag, const uint8_t* gt_flag, const float* score, int32_t group,
+                        int64_t D, int64_t G, int32_t T, int32_t* out_group, float* out_score, uint32_t* out_tp_bits,
+                        uint32_t* out_msk_bits);
+int eval_ap_accumulate_cpu(const int32_t* group, const float* score, const uint32_t* tp_bits, const uint32_t* msk_bits,
+                           const int64_t* num_gt, int64_t n, int64_t K, int32_t T, int64_t* num_det, double* recall, double* ap,
+                           int32_t nthreads);
+
+/* ------------------------------------------------------------------------------------
  * Dynamic point-to-voxel scatter-reduce.  Replaces
  * dynamic_point_to_voxel_scatter_reduce / dynamic_point_to_voxel_backward
  * (/root/reference/mmdet3d_gaussian/ops/voxel/src/voxelization.h:35-79,

@@ -67,7 +67,11 @@ from .registry import LOSSES, Registry, build_loss
 from . import sharded
 from .coders import CenterPointBBoxCoderRev, CenterPointBBoxYawCoder, DeltaXYZWLHRBBoxCoder, PointBBoxYawCoder
 from .graphed import GraphedStep
-from .evaluation import match_coco, trans_bev
+from .evaluation import ap_accumulate, match_coco, tp_records, trans_bev
+from .registry import (EVAL_AFFINITYCALS, EVAL_BREAKDOWNS, EVAL_MATCHERS, EVAL_TPMETRIC, build_eval_affinity_calculator, build_eval_breakdown,
+                       build_eval_matcher, build_eval_tp_metric)
+from .eval_map import (FlexibleStatisticsEval, LidarCenterTransBEV, LidarIOU3D, LidarIOUBEV, MatcherCoCo, NoBreakdown, RangeBreakdown,
+                       VolumeBreakdown, eval_map_flexible)
 from .scatter import Scatter, scatter_index, scatter_reduce
 from .vsa import QueryAndGroup, ball_query, furthest_point_sample, furthest_point_sample_stacked, grouping
 from .points_in_boxes import (pointwise_mask_targets, points_in_boxes_all, points_in_boxes_all_stacked, points_in_boxes_part,
@@ -119,4 +123,7 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'make_sparse_convmodule', 'SparseEncoder', 'MlvlSparseEncoder', 'fuse_sparse_conv_bn', 'FusedSparseConv', 'FusedSparseBasicBlock', 'sparse_batch_norm',
            'SparseBatchNorm1d', 'SparseNormBasicBlock', 'convert_sparse_batchnorm', 'sparse_conv_index_inverse', 'sparse_inverse_conv', 'SparseInverseConv3d',
            'make_sparse_inverse_convmodule', 'sparse_max_pool', 'SparseMaxPool3d', 'ToDense', 'SparseUNet', 'rpn_proposals', 'PartA2RPNHeadProposals',
-           'extras', 'voxel_query_index', 'voxel_point_indices', 'voxel_query_coords', 'voxel_query', 'VoxelQueryIndex', 'VoxelQueryAndGroup']
+           'extras', 'voxel_query_index', 'voxel_point_indices', 'voxel_query_coords', 'voxel_query', 'VoxelQueryIndex', 'VoxelQueryAndGroup',
+           'tp_records', 'ap_accumulate', 'FlexibleStatisticsEval', 'eval_map_flexible', 'NoBreakdown', 'RangeBreakdown', 'VolumeBreakdown',
+           'LidarIOU3D', 'LidarIOUBEV', 'LidarCenterTransBEV', 'MatcherCoCo', 'EVAL_MATCHERS', 'EVAL_AFFINITYCALS', 'EVAL_BREAKDOWNS',
+           'EVAL_TPMETRIC', 'build_eval_matcher', 'build_eval_affinity_calculator', 'build_eval_breakdown', 'build_eval_tp_metric']

@@ -378,6 +378,14 @@ SYMBOLS = {
                                         _vp, _vp, _i32]),
     'gd3d_vsa_voxel_query_and_group_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i32,
                                                   ctypes.POINTER(_i32), _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i32]),
+    # the flexible mAP's records and AP accumulation (csrc/eval_ap.hip)
+    'eval_tp_records': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'eval_tp_records_cpu': (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    'eval_ap_tile_rows': (_i32, []),
+    'eval_ap_scan_chunk_tiles': (_i32, []),
+    'eval_ap_workspace_bytes': (_sz, [_i64, _i64, _i32]),
+    'eval_ap_accumulate': (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'eval_ap_accumulate_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 

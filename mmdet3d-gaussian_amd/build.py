@@ -49,6 +49,7 @@ SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'sparse_bn.hip': ['-ffp-contract=off'],    # live-row BatchNorm: every multiply-add is an explicit fmaf, the order of every sum is fixed
     'sparse_pool.hip': ['-ffp-contract=off'],  # sparse max pooling: copies and plain fp32 adds in a fixed order replay bit for bit in sparse_pool_cpu.cpp
     'voxel_query.hip': ['-ffp-contract=off'],   # memberships, slots, keys and query cells replay bit for bit in voxel_query_cpu.cpp; sort from device_sort.h, gather from vsa_gather.h
+    'eval_ap.hip': ['-ffp-contract=off'],       # keys, counts, the fp64 precisions and the exact envelope sum replay bit for bit in eval_ap_cpu.cpp; sort from device_sort.h
     'rpn_proposal.hip': ['-ffp-contract=off'],  # the order keys, the sigmoid and the decode on fx_expf, the threshold and the direction fix replay bit for bit in rpn_proposal_cpu.cpp
 }
 # The frozen round-3 extras OUTSIDE §8 (DESIGN_EXTRAS.md; include/gd3d_extras.h): a library of their own since round 6,
@@ -89,6 +90,7 @@ HOST_SOURCES = {
     'sparse_pool_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],    # same for sparse_pool.hip: every output bit-identical
     'voxel_query_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],    # same for voxel_query.hip: every output bit-identical
     'rpn_proposal_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],   # same for rpn_proposal.hip: every output bit-identical
+    'eval_ap_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],        # same for eval_ap.hip: every output bit-identical
 }
 HOST_COMMON = ['-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 

@@ -58,6 +58,29 @@ def build_loss(cfg):
     return LOSSES.build(cfg)
 
 
+# the flexible mAP's registries and verbs (/root/reference/mmdet3d_gaussian/core/evaluation/builder.py:4-23); eval_map.py fills them
+EVAL_MATCHERS = Registry('eval_matcher')
+EVAL_AFFINITYCALS = Registry('eval_affinity_calculator')
+EVAL_BREAKDOWNS = Registry('eval_breakdowns')
+EVAL_TPMETRIC = Registry('eval_tp_metric')
+
+
+def build_eval_matcher(cfg, **default_args):
+    return EVAL_MATCHERS.build(cfg, default_args)
+
+
+def build_eval_affinity_calculator(cfg, **default_args):
+    return EVAL_AFFINITYCALS.build(cfg, default_args)
+
+
+def build_eval_breakdown(cfg, **default_args):
+    return EVAL_BREAKDOWNS.build(cfg, default_args)
+
+
+def build_eval_tp_metric(cfg, **default_args):
+    return EVAL_TPMETRIC.build(cfg, default_args)
+
+
 def register_with_mmdet(cls):
     """Also register in mmdet's LOSSES when mmdet is present (drop-in for the reference's configs)."""
     try:
