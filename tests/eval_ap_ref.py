@@ -6,7 +6,9 @@
 * `exact_accumulate`     — the same on fractions.Fraction (the fp64 quotients p_j, then everything exact), for small ones;
 * `literal_single`       — mean_ap_flexible.py:37-128 over the oracle's affinities and matcher, INCLUDING its one-tp-array-per-class
                            aliasing (:90, :115-116, :124-126: every breakdown's tuple holds the LAST breakdown's true positives);
-* `build_cases`          — the case table of the accumulate kernels, computed from the library's tile size and scan chunk;
+* `build_cases`          — the case table of the accumulate kernels, computed from the library's tile size and scan chunk: random
+                           cases of K <= 4, then cases built from lists of group sizes (`_layout_case`), whose sorted layout is
+                           known and whose conditions (which boundary falls where) are asserted when the table is built;
 * `random_dataset`       — detections and annotations in the reference's format.
 """
 from fractions import Fraction
@@ -84,13 +86,20 @@ def literal_accumulate(num_gt, score, tp, bkd_msk, num_thrs, fp64_ap=False):
 # ---- the definition, vectorised and exact ---------------------------------------------------------------------------------------------
 
 def _group_rows(case):
+    """-> (rows, first): rows = the records of groups [0, K) in sorted order (group, then rank), first (K + 1,) = where each group's
+    rows start in it.  One stable sort and one searchsorted: linear in n + K (an unoccupied group has first[k] == first[k + 1])."""
+    K = case['K']
     order = rank_order(case['score'])
-    g = case['group'][order]
-    return [order[g == k] for k in range(case['K'])]
+    g = case['group'][order].astype(np.int64)
+    live = (g >= 0) & (g < K)
+    order, g = order[live], g[live]
+    by_group = np.argsort(g, kind='stable')
+    return order[by_group], np.searchsorted(g[by_group], np.arange(K + 1))
 
 
 def vector_accumulate(case):
-    """-> num_det (K, T) int64, recall (K, T) fp64, ap (K, T) fp64 (the e_j summed by math.fsum: exact, rounded once), n_tp (K, T)"""
+    """-> num_det (K, T) int64, recall (K, T) fp64, ap (K, T) fp64 (the e_j summed by math.fsum: exact, rounded once), n_tp (K, T).
+    Unoccupied groups keep their zeros."""
     import math
     K, T = case['K'], case['T']
     num_det = np.zeros((K, T), np.int64)
@@ -98,7 +107,9 @@ def vector_accumulate(case):
     ap = np.zeros((K, T))
     n_tp = np.zeros((K, T), np.int64)
     tp, msk = unpack(case['tp'], T), unpack(case['msk'], T)
-    for k, rows in enumerate(_group_rows(case)):
+    sorted_rows, first = _group_rows(case)
+    for k in np.nonzero(first[1:] > first[:-1])[0]:
+        rows = sorted_rows[first[k]:first[k + 1]]
         den = float(case['num_gt'][k]) if case['num_gt'][k] > 0 else 1e-7
         for t in range(T):
             r = rows[msk[t, rows]]
@@ -121,7 +132,9 @@ def exact_accumulate(case):
     K, T = case['K'], case['T']
     tp, msk = unpack(case['tp'], T), unpack(case['msk'], T)
     out = [[Fraction(0)] * T for _ in range(K)]
-    for k, rows in enumerate(_group_rows(case)):
+    sorted_rows, first = _group_rows(case)
+    for k in range(K):
+        rows = sorted_rows[first[k]:first[k + 1]]
         den = Fraction(int(case['num_gt'][k])) if case['num_gt'][k] > 0 else Fraction(1e-7)
         for t in range(T):
             r = rows[msk[t, rows]]
@@ -227,6 +240,192 @@ def build_cases(R, chunk, big=True):
     cases.append(c)
     order = np.lexsort((-c['score'].astype(np.float64), c['group']))
     cases.append(_case('records_presorted', c['group'][order], c['score'][order], c['tp'][order], c['msk'][order], c['num_gt'], 2))
+    return cases + _layout_cases(R, chunk, big)       # (their own generator: the cases above keep their draws)
+
+
+# ---- cases built from a list of group sizes: the sorted layout is known, and asserted -------------------------------------------------------
+
+STRAY_GROUPS = (-1, None, 2 ** 31 - 1, -2 ** 31)     # None: K itself
+
+
+def _layout_case(name, rng, sizes, T, K=None, ids=None, strays=0, tp=None, msk=None, num_gt=None, p_msk=0.8, big=False):
+    """A case whose SORTED layout is given: group ids[i] (default i; ascending) holds sizes[i] rows, whose scores fall strictly inside
+    the group, so row j of the layout is row j after the sort; `tp` / `msk` (default: random words) are given in that layout.  `strays`
+    rows of groups {-1, K, 2^31 - 1, -2^31} are appended — they sort last — and all rows are shuffled.  case['bounds'] =
+    np.cumsum(sizes): where the groups end in the sorted rows."""
+    sizes = np.asarray(sizes, np.int64)
+    ids = np.arange(len(sizes)) if ids is None else np.asarray(ids, np.int64)
+    K = len(sizes) if K is None else K
+    assert len(ids) == len(sizes) and (np.diff(ids) > 0).all() and ids[0] >= 0 and ids[-1] < K and (sizes >= 0).all()
+    n = int(sizes.sum())
+    group = np.repeat(ids, sizes)
+    within = np.arange(n) - np.repeat(np.cumsum(sizes) - sizes, sizes)
+    score = (1.0 - (within + 0.5) / np.repeat(sizes, sizes)).astype(np.float32)
+    tp = _words(rng, n, T) if tp is None else np.asarray(tp, np.uint32)
+    msk = _words(rng, n, T, p_msk) if msk is None else np.asarray(msk, np.uint32)
+    assert len(tp) == len(msk) == n
+    if strays:
+        group = np.concatenate([group, [K if STRAY_GROUPS[i % 4] is None else STRAY_GROUPS[i % 4] for i in range(strays)]])
+        score = np.concatenate([score, rng.uniform(0, 1, strays).astype(np.float32)])
+        tp, msk = np.concatenate([tp, _words(rng, strays, T)]), np.concatenate([msk, _words(rng, strays, T, 0.9)])
+    if num_gt is None:
+        num_gt = rng.integers(0, 6, K)
+        num_gt[ids] = rng.integers(0, np.maximum(2, sizes))
+    perm = rng.permutation(n + strays)
+    c = _case(name, group[perm], score[perm], tp[perm], msk[perm], num_gt, T)
+    assert c['K'] == K
+    c['bounds'], c['sizes'], c['big'] = np.cumsum(sizes), sizes, big
+    # the layout is what the sort gives: inside a group the scores fall strictly
+    live = np.nonzero((c['group'] >= 0) & (c['group'] < K))[0]
+    back = live[np.lexsort((-c['score'][live].astype(np.float64), c['group'][live]))]
+    assert np.array_equal(c['group'][back], np.repeat(ids, sizes)) and np.array_equal(c['tp'][back], tp[:n]) and np.array_equal(c['msk'][back], msk[:n])
+    assert n == 0 or (np.diff(c['score'][back].astype(np.float64))[np.diff(c['group'][back]) == 0] < 0).all()
+    return c
+
+
+def _bit0(rng, flags, T, p=0.5):
+    """words whose bit 0 is `flags` and whose other bits are random"""
+    return (_words(rng, len(flags), T, p) & ~np.uint32(1)) | np.asarray(flags, bool).astype(np.uint32)
+
+
+def _fill(rng, rows, R):
+    """group sizes of 3 to 4 tiles that add up to `rows` (the last two: what is left, halved)"""
+    out = []
+    while rows > 8 * R:
+        out.append(int(rng.integers(3 * R, 4 * R + 1)))
+        rows -= out[-1]
+    assert rows >= 2
+    return out + [rows // 2, rows - rows // 2]
+
+
+def _has(bounds, lo, hi):
+    """a group ends at a row of [lo, hi)"""
+    return bool(((bounds >= lo) & (bounds < hi)).any())
+
+
+def _layout_cases(R, chunk, big):
+    rng = np.random.default_rng(20270)
+    W = R // 4                 # rows of a wave: thread i of a tile holds rows 4i .. 4i + 3, wave w rows W w .. W w + W - 1
+    assert R % 4 == 0 and W % 4 == 0
+    cases = []
+    # many boundaries per thread, per wave and per tile, at every alignment
+    dense = [1, 2, 3, 4, 5, 6, 7, 1, 1, 2, 2, 3, 3] * 40
+    seen_mod4 = set()
+    for shift in range(5):
+        c = _layout_case(f'segments_dense_shift{shift}', rng, [shift] + dense + [R + 3, 2, R, 1], 3, strays=37)
+        b = c['bounds']
+        lo, hi = shift, shift + sum(dense)
+        seen_mod4 |= set((b[(b > lo) & (b <= hi)] % 4).tolist())
+        sorted_groups = np.repeat(np.arange(c['K']), c['sizes'])
+        quads = sorted_groups[:len(sorted_groups) // 4 * 4].reshape(-1, 4)
+        assert ((np.diff(quads, axis=1) != 0).sum(1) >= 2).any(), 'no thread holds three groups'
+        spans = [w for w in range(hi // W) if w * W >= lo and (w + 1) * W <= hi]
+        assert len(spans) >= 4 and all(((b > w * W) & (b < (w + 1) * W)).sum() >= 8 for w in spans)
+        cases.append(c)
+    assert seen_mod4 == {0, 1, 2, 3}
+    cases.append(_layout_case('singletons', rng, [1] * (2 * R + 5), 2, strays=11))
+    c = _layout_case('wave_edge_boundaries', rng, [W, W, 2 * W, 3 * W, 1, W - 1, W // 4, 3 * W // 4, W - 1, 1, W + 1, W - 2, 1, 100], 3, strays=5)
+    b = c['bounds']
+    assert ((b % W == 0) & (b % R != 0)).sum() >= 4 and (b % W == 1).sum() >= 2 and (b % W == W - 1).sum() >= 2
+    assert {int(x) // W % 4 for x in b[(b % W == 0) & (b % R != 0)]} == {1, 2, 3}       # each of a tile's three inner wave edges
+    cases.append(c)
+    c = _layout_case('tile_edge_paths', rng, [R // 2, R - R // 2, R, 5, R - 5, R // 3, 2 * R - R // 3, 7], 3, strays=9)
+    s, e = c['bounds'] - c['sizes'], c['bounds']
+    assert s[1] % R != 0 and e[1] % R == 0 and s[1] // R == (e[1] - 1) // R                     # mid-tile to exactly the tile's end
+    assert s[2] % R == 0 and e[2] - s[2] == R and c['sizes'][1] > 0 and c['sizes'][3] > 0      # a whole tile between two others
+    assert s[3] % R == 0 and e[3] % R != 0 and s[3] // R == e[3] // R                           # a tile's first row to mid-tile
+    assert s[6] % R != 0 and e[6] % R == 0 and (e[6] - 1) // R == s[6] // R + 1                 # mid-tile to the end of the next tile
+    cases.append(c)
+    # groups longer than the 64 tiles one trip of the finish kernel's lanes covers
+    cases.append(_layout_case('group_over_64_tiles', rng, [10, 65 * R + 17, 5], 3, strays=21))
+    cases.append(_layout_case('group_over_128_tiles', rng, [3, 129 * R + 1], 3, strays=6))
+    for c in cases[-2:]:
+        assert ((c['bounds'] - 1) // R - (c['bounds'] - c['sizes']) // R).max() + 1 > (64 if '64' in c['name'] else 128)
+    # the same long group, false positives first and true positives in its last 1.5 R rows (bit 0); bit 1 adds one early true
+    # positive whose precision 1/100 lies below the last one, so its envelope value comes from 64 tiles further on
+    n0, n1, n2 = 33, 65 * R + 17, R // 2 + 3
+    late = np.arange(n1) >= n1 - R - R // 2
+    assert 1 / 100 < late.sum() / n1
+    tp = np.concatenate([_words(rng, n0, 3), late.astype(np.uint32) * np.uint32(5) | (late | (np.arange(n1) == 99)).astype(np.uint32) * np.uint32(2),
+                         (np.arange(n2) < n2 // 2).astype(np.uint32) * np.uint32(7)])
+    cases.append(_layout_case('envelope_over_64_tiles', rng, [n0, n1, n2], 3, strays=13, tp=tp, msk=np.full(n0 + n1 + n2, 7, np.uint32),
+                              num_gt=[9, n1, n2]))
+    # every row a true positive at every threshold: whole tiles of e = 1, the top limb sums 2^31 per tile
+    n0, n1 = 3 * R + 9, R // 4 + 1
+    cases.append(_layout_case('all_true_positives', rng, [n0, n1], 3, strays=7, tp=np.full(n0 + n1, 7, np.uint32), msk=np.full(n0 + n1, 7, np.uint32),
+                              num_gt=[n0, 0]))
+    n0 = 2 * R + 3
+    cases.append(_layout_case('one_true_positive_at_the_last_rank', rng, [n0], 3, strays=4, tp=(np.arange(n0) == n0 - 1).astype(np.uint32) * np.uint32(7),
+                              msk=np.full(n0, 7, np.uint32), num_gt=[7]))
+    for K in (1023, 1024, 1025):
+        cases.append(_layout_case(f'groups_{K}', rng, rng.integers(1, 6, K), 1, strays=50))
+        assert (cases[-1]['sizes'] > 0).all()
+    K = 1 << 20
+    ids = np.unique(np.concatenate([[0, 1, K // 2 - 1, K // 2, K - 2, K - 1], rng.integers(0, K, 300)]))
+    sizes = rng.integers(1, 31, len(ids))
+    sizes[-1] += 4900 - sizes.sum()
+    c = _layout_case('max_groups', rng, sizes, 1, K=K, ids=ids, strays=100, num_gt=rng.integers(1, 5, K))
+    assert len(c['score']) == 5000 and (sizes > 0).all() and (c['num_gt'] > 0).all() and len(ids) > 200
+    cases.append(c)
+    if not big:
+        return cases
+    # ---- the carry scans' second and third trips over live rows (no stray rows: the last tile is live) ----
+    E1, E2 = chunk * R, 2 * chunk * R
+    m = (E2 - R // 2) // (R + R // 2)
+    assert R // 2 + m * (R + R // 2) == E2
+    c = _layout_case('three_scan_trips_short_groups', rng, [R // 2] + [R + R // 2] * m + [7], 2, big=True)
+    n = len(c['score'])
+    assert n == E2 + 7 and (n + R - 1) // R == 2 * chunk + 1 and all(_has(c['bounds'], k * R, (k + 1) * R + 1) for k in range(2 * chunk + 1))
+    cases.append(c)
+    # a group over each chunk edge: [E - 2R - 7, E + 2R + 5), true positives in its last R rows (bit 0: the counts flow forward over
+    # the edge); bit 1 adds one early true positive of precision 1/10, below the last one (its envelope flows backward over the edge)
+    span = 4 * R + 12
+    sizes = _fill(rng, E1 - 2 * R - 7, R) + [span]
+    a1 = len(sizes) - 1
+    sizes += _fill(rng, E2 - 2 * R - 7 - sum(sizes), R) + [span]
+    a2 = len(sizes) - 1
+    sizes += [3 * R + 1]
+    nn = sum(sizes)
+    starts = np.cumsum(sizes) - np.asarray(sizes)
+    assert starts[a1] == E1 - 2 * R - 7 and starts[a2] == E2 - 2 * R - 7 and 1 / 10 < R / span
+    flags0, flags1 = rng.uniform(0, 1, nn) < 0.5, rng.uniform(0, 1, nn) < 0.5
+    mk = _words(rng, nn, 2)
+    for a in (a1, a2):
+        rows = np.arange(starts[a], starts[a] + span)
+        flags0[rows] = rows >= starts[a] + span - R
+        flags1[rows] = flags0[rows] | (rows == starts[a] + 9)
+        mk[rows] = 3
+    c = _layout_case('chunk_edge_straddled', rng, sizes, 2, tp=flags0.astype(np.uint32) | flags1.astype(np.uint32) << np.uint32(1), msk=mk, big=True)
+    assert not _has(c['bounds'], E1 - 2 * R - 6, E1 + 2 * R + 5) and not _has(c['bounds'], E2 - 2 * R - 6, E2 + 2 * R + 5)
+    assert _has(c['bounds'], E1 + 2 * R + 5, E1 + 2 * R + 6) and _has(c['bounds'], E2 + 2 * R + 5, E2 + 2 * R + 6)
+    cases.append(c)
+    # groups that end exactly on the chunk edges: the one before ends in false positives over whole tiles, the one after opens with
+    # precision 1 — counts leaking forward or the envelope leaking backward change a result
+    n_before, n_after = 3 * R + 100, R + 9
+    sizes = _fill(rng, E1 - n_before, R) + [n_before, n_after]
+    b1 = len(sizes) - 2
+    sizes += _fill(rng, E2 - n_before - sum(sizes), R) + [n_before, n_after]
+    b2 = len(sizes) - 2
+    sizes += [2 * R + 1]
+    nn = sum(sizes)
+    starts = np.cumsum(sizes) - np.asarray(sizes)
+    assert starts[b1] + n_before == E1 and starts[b2] + n_before == E2
+    flags0 = rng.uniform(0, 1, nn) < 0.5
+    mk = _words(rng, nn, 2)
+    for b_ in (b1, b2):
+        rows = np.arange(starts[b_], starts[b_] + n_before)
+        flags0[rows] = ((rows - starts[b_]) % 7 == 3) & (rows - starts[b_] < 40)
+        after = np.arange(starts[b_ + 1], starts[b_ + 1] + n_after)
+        flags0[after] = after - starts[b_ + 1] < n_after // 2
+        mk[rows] |= 1
+        mk[after] |= 1
+    c = _layout_case('chunk_edge_is_boundary', rng, sizes, 2, tp=_bit0(rng, flags0, 2), msk=mk, big=True)
+    assert _has(c['bounds'], E1, E1 + 1) and _has(c['bounds'], E2, E2 + 1) and len(c['score']) > E2 + R
+    cases.append(c)
+    c = _random_case(f'size_{chunk * R + 1}_second_scan_trip_live', rng, chunk * R + 1, 3, 2, stray=False, round_to=4)
+    c['big'] = True
+    assert ((c['group'] >= 0) & (c['group'] < 3)).all() and len(c['score']) == chunk * R + 1
+    cases.append(c)
     return cases
 
 

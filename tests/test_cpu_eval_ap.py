@@ -12,6 +12,7 @@ Bounds (derived, not measured; u = 2^-53):
 """
 import ctypes
 import os
+import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -58,6 +59,26 @@ def test_twin_equals_the_vectorised_definition(case):
     assert np.array_equal(nd, want_nd)
     assert np.array_equal(bits(rc), bits(want_rc)), np.abs(rc - want_rc).max()
     assert np.array_equal(bits(ap), bits(want_ap)), np.abs(ap - want_ap).max()
+
+
+def case_named(name, cases=CASES):
+    return next(c for c in cases if c['name'].startswith(name))
+
+
+def test_all_true_positives_and_one_true_positive_analytically():
+    """Whole tiles of e = 1: ap = recall = 1 and num_det = n to the bit; with num_gt = 0 the sum n_1 is divided by 1e-7.  One true
+    positive at the last of n ranks: the envelope is the fp64 quotient 1 / n at that row alone."""
+    case = case_named('all_true_positives')
+    n0, n1 = (int(s) for s in case['sizes'])
+    assert case['num_gt'].tolist() == [n0, 0] and n0 > 3 * R
+    nd, rc, ap = run(case)
+    assert (nd[0] == n0).all() and (rc[0] == 1.0).all() and (ap[0] == 1.0).all()
+    assert (nd[1] == n1).all() and (rc[1] == float(n1) / 1e-7).all() and (ap[1] == float(n1) / 1e-7).all()
+    case = case_named('one_true_positive_at_the_last_rank')
+    n, den = int(case['sizes'][0]), float(case['num_gt'][0])
+    assert n == 2 * R + 3 and den > 0
+    nd, rc, ap = run(case)
+    assert (nd[0] == n).all() and (rc[0] == 1.0 / den).all() and (ap[0] == (1.0 / n) / den).all()
 
 
 def _small_cases():
@@ -178,6 +199,144 @@ def test_argument_errors():
         amd.tp_records(torch.zeros((2, 5), dtype=torch.int32), torch.zeros(4, dtype=torch.bool), torch.zeros(3, dtype=torch.bool), f32(4), 0)
     with pytest.raises(RuntimeError, match='detection flags'):
         amd.tp_records(None, torch.zeros(3, dtype=torch.bool), torch.zeros(3, dtype=torch.bool), f32(4), 0, num_thrs=2)
+
+
+# ---- the shared arithmetic against Python's integers -----------------------------------------------------------------------------------------
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope='module')
+def apmath(tmp_path_factory):
+    """tests/hostmath/eval_ap_math.cpp: csrc/eval_ap_common.h compiled for the host with -ffp-contract=off, as both product units are"""
+    cxx = _lib._build.host_cxx_path()
+    if cxx is None:
+        pytest.skip('no host C++ compiler')
+    so = str(tmp_path_factory.mktemp('eval_ap_math') / 'libevalapmath.so')
+    cmd = [cxx, '-O1', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC', os.path.join(ROOT, 'tests', 'hostmath', 'eval_ap_math.cpp'), '-o', so]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lib = ctypes.CDLL(so)
+    for f in ('hostmath_limbs_of', 'hostmath_limbs_to_double', 'hostmath_score_key', 'hostmath_record_key'):
+        getattr(lib, f).restype = None
+    return lib
+
+
+def _vp(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _limbs_to_double(lib, limbs):
+    limbs = np.ascontiguousarray(limbs, np.uint64).reshape(-1, 4)
+    out = np.empty(len(limbs), np.float64)
+    lib.hostmath_limbs_to_double(_vp(limbs), ctypes.c_long(len(limbs)), _vp(out))
+    return out
+
+
+def _total(l):
+    return int(l[0]) + (int(l[1]) << 21) + (int(l[2]) << 42) + (int(l[3]) << 63)
+
+
+def _unnormalised(rng, total):
+    """four limb sums below 2^53, not normalised, whose weighted sum is `total` (< 2^116): the normal form, then units moved down"""
+    l = [total & 0x1fffff, (total >> 21) & 0x1fffff, (total >> 42) & 0x1fffff, total >> 63]
+    assert l[3] < 1 << 53
+    for k in (3, 2, 1):
+        a = min(l[k], ((1 << 53) - 1 - l[k - 1]) >> 21, int(rng.integers(0, 1 << 32)))
+        if rng.uniform() < 0.8:
+            l[k] -= a
+            l[k - 1] += a << 21
+    assert all(0 <= x < 1 << 53 for x in l) and _total(l) == total
+    return l
+
+
+def test_limbs_to_double_on_unnormalised_limb_sums_against_python_integers(apmath):
+    """What only the device's finish kernel asks of limbs_to_double: limb sums of up to 53 bits each, whose carries `l1 >> 43`,
+    `l2 >> 22`, `l3 >> 1` count.  The result must be the total of 2^-84 units rounded once, to nearest even: float(Fraction)."""
+    rng = np.random.default_rng(84)
+    rows = []
+    for _ in range(20000):                               # random limbs of random lengths
+        rows.append([int(rng.integers(0, 1 << 53)) >> int(rng.integers(0, 54)) for _ in range(4)])
+    top = (1 << 53) - 1
+    rows += [[top] * 4, [top, 0, 0, 0], [0, top, 0, 0], [0, 0, top, 0], [0, 0, 0, top], [0, top, top, 0], [top, top, 0, 1], [0, 0, 0, 0],
+             [1, 0, 0, 0], [0, 0, 0, 1], [0, 0, 0, 1 << 31], [0, 1 << 52, 1 << 52, 1 << 52]]
+    halfway = 0
+    for bits_ in range(54, 116):                         # totals of every length with the cut exactly halfway, one below and one above
+        for _ in range(40):
+            m = (1 << 52) | int(rng.integers(0, 1 << 52))          # the 53 kept bits: odd and even last bits
+            for delta in (-1, 0, 1):
+                total = (m << (bits_ - 53)) + (1 << (bits_ - 54)) + delta
+                assert total.bit_length() == bits_
+                rows.append(_unnormalised(rng, total))
+                halfway += 1
+    assert halfway >= 62 * 3 * 40 and any(r[1] >> 43 for r in rows) and any(r[2] >> 22 for r in rows)
+    got = _limbs_to_double(apmath, np.array(rows, np.uint64))
+    want = np.array([float(Fraction(_total(r), 1 << 84)) for r in rows])
+    bad = np.nonzero(bits(got) != bits(want))[0]
+    assert bad.size == 0, (rows[bad[0]], got[bad[0]], want[bad[0]])
+
+
+def test_limbs_of_represents_the_fp64_quotient_exactly(apmath):
+    rng = np.random.default_rng(85)
+    j = rng.integers(1, 1 << 31, 200000)
+    c = np.minimum(j, rng.integers(1, 1 << 31, 200000) >> rng.integers(0, 31, 200000)).clip(1)
+    e = np.concatenate([c / j, [1.0, 2.0 ** -31, 1.0 / (2 ** 31 - 1), 0.0, 1.0 / 3.0, (2.0 ** 31 - 2) / (2.0 ** 31 - 1)]])
+    assert (c >= 1).all() and (c <= j).all() and (e[:len(c)] == c.astype(np.float64) / j.astype(np.float64)).all()
+    limbs = np.empty((len(e), 4), np.uint32)
+    apmath.hostmath_limbs_of(_vp(e), ctypes.c_long(len(e)), _vp(limbs))
+    assert (limbs[:, :3] < 1 << 21).all() and (limbs[:, 3] <= 1 << 21).all()
+    assert limbs[len(c)].tolist() == [0, 0, 0, 1 << 21] and limbs[len(c) + 3].tolist() == [0, 0, 0, 0]
+    for q, l in zip(e.tolist(), limbs.tolist()):
+        num, den = q.as_integer_ratio()                  # den: a power of two, at most 2^84 for these quotients
+        assert (1 << 84) % den == 0 and _total(l) == num * ((1 << 84) // den), (q, l)
+    # and back: a single e survives the round trip
+    assert np.array_equal(bits(_limbs_to_double(apmath, limbs.astype(np.uint64))), bits(e))
+
+
+def test_record_key_order_is_the_rank_order_on_special_scores(apmath):
+    """Ascending record_key (stable) = group, then `rank_order`: NaN of either sign and any payload first, -0 == +0, denormals,
+    +-inf; groups outside [0, K) — the ends of int32 among them — sort last, as group K."""
+    rng = np.random.default_rng(86)
+    K = 5
+    special = np.array([0x7fc00000, 0xffc00000, 0x7f800001, 0xff800001, 0x7fffffff, 0xffffffff, 0x00000000, 0x80000000, 0x00000001, 0x80000001,
+                        0x007fffff, 0x807fffff, 0x00800000, 0x80800000, 0x7f800000, 0xff800000, 0x7f7fffff, 0xff7fffff, 0x3f800000, 0xbf800000,
+                        0x3f000000, 0x3f000001], np.uint32).view(np.float32)
+    n = 4000
+    score = special[rng.integers(0, len(special), n)]
+    score[::7] = rng.uniform(-2, 2, len(score[::7])).astype(np.float32)
+    group = rng.choice(np.array([0, 1, 2, 3, 4, -1, K, K + 1, 2 ** 31 - 1, -2 ** 31, -7], np.int64), n).astype(np.int32)
+    key = np.empty(n, np.uint64)
+    apmath.hostmath_record_key(_vp(group), _vp(score), ctypes.c_long(n), ctypes.c_int32(K), _vp(key))
+    word = np.empty(n, np.uint32)
+    apmath.hostmath_score_key(_vp(score), ctypes.c_long(n), _vp(word))
+    g = np.where((group >= 0) & (group < K), group, K).astype(np.int64)
+    assert np.array_equal(key >> np.uint64(32), g.astype(np.uint64)) and np.array_equal((key & np.uint64(0xffffffff)).astype(np.uint32), word)
+    with np.errstate(invalid='ignore'):                  # the signalling NaNs, widened
+        order = ref.rank_order(score)
+    want = order[np.argsort(g[order], kind='stable')]
+    assert np.array_equal(np.argsort(key, kind='stable'), want)
+    assert np.array_equal(np.argsort(word, kind='stable'), order)
+    assert (word[np.isnan(score)] == 0).all() and (word[~np.isnan(score)] > 0).all()
+
+
+def test_host_twin_under_address_and_undefined_behaviour_sanitizers(tmp_path):
+    """csrc/eval_ap_cpu.cpp compiled together with a stand-alone driver (tests/hostmath/eval_ap_sanitize.cpp, its own main) under
+    -fsanitize=address,undefined,float-cast-overflow and run as a program on the CPU: exactly sized heap blocks, n = 0, a NULL
+    `matched`, G = 0, matches and groups outside their ranges, NaN and infinite scores, T = 32, K = 1 and a few thousand, 1, 3 and
+    all threads.  The device kernels share the key, limb and finish code.  A sanitizer build belongs on a CPU-only machine: with a GPU
+    present the test skips before it compiles or starts anything."""
+    if torch.cuda.is_available():
+        pytest.skip('sanitizer builds run on a CPU-only machine, never where a GPU is present')
+    cxx = _lib._build.host_cxx_path()
+    if cxx is None:
+        pytest.skip('no host C++ compiler')
+    exe = str(tmp_path / 'eval_ap_sanitize')
+    cmd = [cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined,float-cast-overflow', '-fno-sanitize-recover=all', '-ffp-contract=off',
+           '-pthread', os.path.join(ROOT, 'tests', 'hostmath', 'eval_ap_sanitize.cpp'),
+           os.path.join(ROOT, 'mmdet3d-gaussian_amd', 'csrc', 'eval_ap_cpu.cpp'), '-o', exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith('OK') and 'runtime error' not in r.stderr, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 # ---- the surface -------------------------------------------------------------------------------------------------------------------------
