@@ -624,6 +624,51 @@ int eval_ap_accumulate_cpu(const int32_t* group, const float* score, const uint3
                            const int64_t* num_gt, int64_t n, int64_t K, int32_t T, int64_t* num_det, double* recall, double* ap,
                            int32_t nthreads);
 
+/* Flexible mAP, a batch of frames: every record of every (frame, class) problem, breakdown row and threshold of a batch in a FIXED
+ * number of launches (an addition inside ABI 6; csrc/eval_frames.hip).  What the affinity entry
+ * (riou_eval_3d / riou_eval_bev / riou_eval_trans_bev), eval_match_coco and eval_tp_records give when they are called once per
+ * problem and breakdown row, and the same bits.
+ *
+ * eval_frames_records:
+ *   mode: 0 riou_eval_3d with z_offset, 1 riou_eval_bev, 2 riou_eval_trans_bev.  negate != 0: the matcher sees -affinity and -thrs
+ *   (what BaseMatcher.__call__ does for LARGER_CLOSER affinities; the negation is exact).
+ *   Problem p in [0, P) owns the detection rows [det_seg[p], det_seg[p+1]) of det (ND, 7) and score (ND), ALREADY in the problem's
+ *   rank order, and the gt rows [gt_seg[p], gt_seg[p+1]) of gt (NG, 7): D_p and G_p rows.  det_seg, gt_seg (P + 1) int32 ascending from
+ *   0 to ND / NG; pair_off (P + 1) int64: the prefix sums of D_p * G_p, pairs = pair_off[P]; max_gt >= every G_p.  These tables are
+ *   DEVICE memory for the device entry; their contents are known to the host from shapes alone.
+ *   gt_crowd (NG) bytes or NULL (no crowd gt).  det_flag (R, ND), gt_flag (R, NG) bytes: the box lies in breakdown row b (ignored gts
+ *   already cleared).  group (P, R) int32: the record group of problem p's row b, or -1 where the row does not apply to the problem.
+ *   thrs (T) fp32.  1 <= T <= 32, R >= 1, P >= 0.
+ *   Writes R * ND rows of four columns, each pointer at the row where the caller's block starts; the row of (b, detection row i) is
+ *   b * ND + i.  For i in problem p: group = group[p, b]; score = a copy of score[i]; and with
+ *     matched = eval_match_coco(cost_p, thrs, is_ignore = !gt_flag[b, p's gts], is_crowd = gt_crowd or zeros)
+ *   bit t of tp_bits and msk_bits is what eval_tp_records(matched, det_flag[b], gt_flag[b], ...) writes; G_p == 0 takes its no-match
+ *   branch (matched NULL); D_p == 0 has no rows.  A row with group[p, b] == -1 gets group -1, the score copy and zero bits: nothing is
+ *   matched for it.
+ *   alias_tp != 0: the tp_bits of every row (b, i) of problem p with group[p, b] >= 0 are those of (b_last, i), b_last the largest b
+ *   with group[p, b] >= 0 — the reference's one-cls_tp-array aliasing (mean_ap_flexible.py:90, :115-116, :124-126).  They are written
+ *   from the last row's matcher result, never copied: no race.
+ *   Limits: max_gt <= 2048, pairs, R * ND and P * R * T <= 2^31 - 1: GD3D_E_TOOLARGE beyond.  Null pointers with non-zero sizes, T
+ *   or mode out of range, R < 1: GD3D_E_BADARG.  Whatever the tables hold, nothing is read or written out of range.
+ *   THREE launches (pair affinities; matcher, one wave per (problem, row, threshold); records), whatever P, R, T and the frames are;
+ *   a batch with pairs == 0 runs the records launch alone.  No host read, no atomic, static shapes, capturable on one stream.
+ *   workspace: eval_frames_workspace_bytes(ND, pairs, R, T) bytes, 256-byte aligned (the same carve at address 0; 0 for arguments
+ *   out of range); its contents need not be cleared between calls. */
+int eval_frames_records(int32_t mode, float z_offset, int32_t negate, const float* det, const float* score, const int32_t* det_seg,
+                        int64_t ND, const float* gt, const int32_t* gt_seg, int64_t NG, const uint8_t* gt_crowd,
+                        const int64_t* pair_off, int64_t pairs, int64_t max_gt, const uint8_t* det_flag, const uint8_t* gt_flag,
+                        const int32_t* group, const float* thrs, int32_t P, int32_t R, int32_t T, int32_t alias_tp, int32_t* out_group,
+                        float* out_score, uint32_t* out_tp_bits, uint32_t* out_msk_bits, void* workspace, void* stream);
+size_t eval_frames_workspace_bytes(int64_t ND, int64_t pairs, int32_t R, int32_t T);
+/* `_cpu` twin (csrc/eval_frames_cpu.cpp): the same contract on HOST memory; the problems are spread over `nthreads` std::threads
+ * (<= 0: hardware concurrency) and each runs the existing `_cpu` twins, so all four columns carry the same bits.  The tables are
+ * host memory here, so tables that contradict ND, NG, pairs or max_gt are refused with GD3D_E_BADARG. */
+int eval_frames_records_cpu(int32_t mode, float z_offset, int32_t negate, const float* det, const float* score, const int32_t* det_seg,
+                            int64_t ND, const float* gt, const int32_t* gt_seg, int64_t NG, const uint8_t* gt_crowd,
+                            const int64_t* pair_off, int64_t pairs, int64_t max_gt, const uint8_t* det_flag, const uint8_t* gt_flag,
+                            const int32_t* group, const float* thrs, int32_t P, int32_t R, int32_t T, int32_t alias_tp,
+                            int32_t* out_group, float* out_score, uint32_t* out_tp_bits, uint32_t* out_msk_bits, int32_t nthreads);
+
 /* ------------------------------------------------------------------------------------
  * Dynamic point-to-voxel scatter-reduce.  Replaces
  * dynamic_point_to_voxel_scatter_reduce / dynamic_point_to_voxel_backward

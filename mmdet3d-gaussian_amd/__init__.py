@@ -67,7 +67,7 @@ from .registry import LOSSES, Registry, build_loss
 from . import sharded
 from .coders import CenterPointBBoxCoderRev, CenterPointBBoxYawCoder, DeltaXYZWLHRBBoxCoder, PointBBoxYawCoder
 from .graphed import GraphedStep
-from .evaluation import ap_accumulate, match_coco, tp_records, trans_bev
+from .evaluation import ap_accumulate, frames_records, match_coco, tp_records, trans_bev
 from .registry import (EVAL_AFFINITYCALS, EVAL_BREAKDOWNS, EVAL_MATCHERS, EVAL_TPMETRIC, build_eval_affinity_calculator, build_eval_breakdown,
                        build_eval_matcher, build_eval_tp_metric)
 from .eval_map import (FlexibleStatisticsEval, LidarCenterTransBEV, LidarIOU3D, LidarIOUBEV, MatcherCoCo, NoBreakdown, RangeBreakdown,
@@ -124,6 +124,6 @@ __all__ = ['GDLoss', 'LOSSES', 'Registry', 'build_loss', 'make_params', 'nms_gpu
            'SparseBatchNorm1d', 'SparseNormBasicBlock', 'convert_sparse_batchnorm', 'sparse_conv_index_inverse', 'sparse_inverse_conv', 'SparseInverseConv3d',
            'make_sparse_inverse_convmodule', 'sparse_max_pool', 'SparseMaxPool3d', 'ToDense', 'SparseUNet', 'rpn_proposals', 'PartA2RPNHeadProposals',
            'extras', 'voxel_query_index', 'voxel_point_indices', 'voxel_query_coords', 'voxel_query', 'VoxelQueryIndex', 'VoxelQueryAndGroup',
-           'tp_records', 'ap_accumulate', 'FlexibleStatisticsEval', 'eval_map_flexible', 'NoBreakdown', 'RangeBreakdown', 'VolumeBreakdown',
+           'tp_records', 'frames_records', 'ap_accumulate', 'FlexibleStatisticsEval', 'eval_map_flexible', 'NoBreakdown', 'RangeBreakdown', 'VolumeBreakdown',
            'LidarIOU3D', 'LidarIOUBEV', 'LidarCenterTransBEV', 'MatcherCoCo', 'EVAL_MATCHERS', 'EVAL_AFFINITYCALS', 'EVAL_BREAKDOWNS',
            'EVAL_TPMETRIC', 'build_eval_matcher', 'build_eval_affinity_calculator', 'build_eval_breakdown', 'build_eval_tp_metric']

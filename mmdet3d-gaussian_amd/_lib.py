@@ -386,6 +386,12 @@ SYMBOLS = {
     'eval_ap_workspace_bytes': (_sz, [_i64, _i64, _i32]),
     'eval_ap_accumulate': (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     'eval_ap_accumulate_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32]),
+    # the per-frame stage of the flexible mAP for a batch of frames (csrc/eval_frames.hip)
+    'eval_frames_records': (_int, [_i32, _f32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32,
+                                   _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'eval_frames_workspace_bytes': (_sz, [_i64, _i64, _i32, _i32]),
+    'eval_frames_records_cpu': (_int, [_i32, _f32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32,
+                                       _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32]),
     'gd3d_abi_version': (_int, [ctypes.POINTER(ctypes.c_char_p)]),
 }
 

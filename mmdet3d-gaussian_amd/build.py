@@ -50,6 +50,7 @@ SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'sparse_pool.hip': ['-ffp-contract=off'],  # sparse max pooling: copies and plain fp32 adds in a fixed order replay bit for bit in sparse_pool_cpu.cpp
     'voxel_query.hip': ['-ffp-contract=off'],   # memberships, slots, keys and query cells replay bit for bit in voxel_query_cpu.cpp; sort from device_sort.h, gather from vsa_gather.h
     'eval_ap.hip': ['-ffp-contract=off'],       # keys, counts, the fp64 precisions and the exact envelope sum replay bit for bit in eval_ap_cpu.cpp; sort from device_sort.h
+    'eval_frames.hip': ['-ffp-contract=off'],    # the affinities are rbox.hip's, the matcher eval_match.hip's, the records eval_ap.hip's: same bits, and in eval_frames_cpu.cpp
     'rpn_proposal.hip': ['-ffp-contract=off'],  # the order keys, the sigmoid and the decode on fx_expf, the threshold and the direction fix replay bit for bit in rpn_proposal_cpu.cpp
 }
 # The frozen round-3 extras OUTSIDE §8 (DESIGN_EXTRAS.md; include/gd3d_extras.h): a library of their own since round 6,
@@ -91,6 +92,7 @@ HOST_SOURCES = {
     'voxel_query_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],    # same for voxel_query.hip: every output bit-identical
     'rpn_proposal_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],   # same for rpn_proposal.hip: every output bit-identical
     'eval_ap_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],        # same for eval_ap.hip: every output bit-identical
+    'eval_frames_cpu.cpp': ['-march=x86-64-v3', '-ffp-contract=off', '-pthread'],    # same for eval_frames.hip: the existing twins per problem
 }
 HOST_COMMON = ['-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 

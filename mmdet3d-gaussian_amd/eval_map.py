@@ -11,7 +11,8 @@ registered in registry.py's EVAL_* registries (builder.py:4-23), so the referenc
 Per frame and class the affinity matrix is computed once (iou_3d / iou_bev / trans_bev), `match_coco` runs once per breakdown and
 `tp_records` turns each result into rows of ONE record buffer that lives where the detections live; the dataset's AP of every
 (class, breakdown, threshold) is then ONE `ap_accumulate` call and one read-back.  numpy inputs move to the GPU when there is one;
-CPU tensors (and numpy without a GPU) run the library's `_cpu` twins.  What differs from the reference is listed in
+CPU tensors (and numpy without a GPU) run the library's `_cpu` twins.  With `frame_batch=N` the per-frame stage runs for N frames
+per `frames_records` call instead — the same records, breakdown-major inside a batch, and the same results.  What differs from the reference is listed in
 INTEGRATION.md §1c: ties between scores have a definite order, `nproc` starts no process, the table is plain text.
 """
 import logging
@@ -306,6 +307,112 @@ class FlexibleStatisticsEval(object):
                 tp[first:first + (num_bkd - 1) * D].view(num_bkd - 1, D).copy_(last.expand(num_bkd - 1, D))
         return blocks
 
+    # -- the per-frame stage for a batch of frames: ONE frames_records call ----------------------------------------------------------------
+
+    def _batch_mode(self):
+        """The `frames_records` mode of this evaluator.  The batched path replays exactly the built-in classes; a subclass may compute
+        anything, so it is refused by name instead of being silently replaced."""
+        aff, mode = self.affinity_calculator, None
+        for cls, m in ((LidarIOU3D, 'iou3d'), (LidarIOUBEV, 'ioubev'), (LidarCenterTransBEV, 'trans')):
+            if type(aff) is cls:
+                mode = m
+        if mode is None:
+            raise ValueError(f'frame_batch > 0 serves LidarIOU3D, LidarIOUBEV and LidarCenterTransBEV, not {type(aff).__name__}')
+        if type(self.matcher) is not MatcherCoCo:
+            raise ValueError(f'frame_batch > 0 serves MatcherCoCo, not {type(self.matcher).__name__}')
+        for fun in self.breakdown:
+            if type(fun) not in (NoBreakdown, RangeBreakdown, VolumeBreakdown):
+                raise ValueError(f'frame_batch > 0 serves NoBreakdown, RangeBreakdown and VolumeBreakdown, not {type(fun).__name__}')
+        return mode
+
+    def _class_rows(self, cls, group_of):
+        """(R,) int32: the group of the class's breakdown row b, -1 where the row's breakdown does not apply to the class."""
+        names, rows = [], []
+        for fun in self.breakdown:
+            mine = fun.breakdown_names(cls)
+            rows += [len(names) + k if mine else -1 for k in range(len(fun.names))]
+            names += mine
+        gid0 = group_of(cls, names)
+        return np.array([gid0 + r if r >= 0 else -1 for r in rows], np.int32)
+
+    def _batch_records(self, dets, annos, rec, group_of, num_gt, mode):
+        """`_frame_records` for a batch of frames in one `frames_records` call.  Problem p = (frame, class), frame-major.  Returns False,
+        having done nothing, for a batch this path does not serve: the caller then goes frame by frame, with the same results."""
+        dev = rec.device
+        num_cls = len(dets[0])
+        flat = [d for det in dets for d in det]
+        as_tensor = [isinstance(d, torch.Tensor) for d in flat]
+        if num_cls == 0 or any(len(det) != num_cls for det in dets) or (any(as_tensor) and not all(as_tensor)):
+            return False
+        if not all(as_tensor):
+            flat = [np.asarray(d) for d in flat]
+            if len({d.dtype for d in flat}) != 1:        # broken down in their own precision: one precision per batch
+                return False
+        keys = set(annos[0]['gt_attrs'].keys())
+        if any(set(a['gt_attrs'].keys()) != keys for a in annos) or 'iscrowd' in keys:
+            return False           # (an `iscrowd` attribute meets the affinity callables' assertion on the per-frame path)
+        # the gts of every problem, packed on the host in their own precision
+        gt_boxes, gt_attrs, G_p = [], {k: [] for k in keys}, []
+        for anno in annos:
+            boxes, labels = _host_np(anno['gt_bboxes']), _host_np(anno['gt_labels'])
+            attrs = {k: _host_np(anno['gt_attrs'][k]) for k in keys}
+            for cls in range(num_cls):
+                msk = labels == cls
+                gt_boxes.append(boxes[msk])
+                for k in keys:
+                    gt_attrs[k].append(attrs[k][msk])
+                G_p.append(len(gt_boxes[-1]))
+        if max(G_p) > _ev.FRAMES_MAX_GT or len({b.dtype for b in gt_boxes}) != 1 or any(len({a.dtype for a in v}) != 1 for v in gt_attrs.values()):
+            return False
+        gt_all = np.concatenate(gt_boxes, axis=0)
+        attrs_all = {k: np.concatenate(v, axis=0) for k, v in gt_attrs.items()}
+        gt_seg = np.concatenate([[0], np.cumsum(G_p)])
+        D_p = [len(d) for d in flat]
+        det_seg = np.concatenate([[0], np.cumsum(D_p)])
+        P, ND = len(flat), int(det_seg[-1])
+        # every breakdown's flags ONCE on the packed boxes; a class's rows of a breakdown that does not apply get group -1
+        gt_flag = np.concatenate([fun.breakdown_flags(gt_all, attrs_all) for fun in self.breakdown], axis=0)
+        rows_of = [self._class_rows(cls, group_of) for cls in range(num_cls)]
+        group = np.stack([rows_of[p % num_cls] for p in range(P)])
+        counts = np.concatenate([np.zeros((gt_flag.shape[0], 1), np.int64), np.cumsum(gt_flag, axis=1, dtype=np.int64)], axis=1)
+        per_problem = counts[:, gt_seg[1:]] - counts[:, gt_seg[:-1]]            # (R, P): the gts of the row in the problem
+        for p in range(P):
+            for b in np.nonzero(group[p] >= 0)[0]:
+                num_gt[group[p, b]] += int(per_problem[b, p])
+        if ND == 0:
+            return True
+        # the detections: packed, then each problem ordered by descending score, stably — two stable sorts (score descending, then
+        # problem id), so NaN and +-0 fall where the per-problem torch.sort(descending=True, stable=True) puts them
+        if all(as_tensor):
+            packed = torch.cat([d.detach().to(device=dev, dtype=torch.float32) for d in flat], dim=0)
+            host_boxes = None
+        else:
+            host = np.concatenate(flat, axis=0)
+            host_boxes = host[:, :-1]
+            packed = torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32)).to(dev)
+        pid = torch.from_numpy(np.repeat(np.arange(P), D_p)).to(dev)
+        by_score = torch.sort(packed[:, -1], descending=True, stable=True)[1]
+        order = by_score[torch.sort(pid[by_score], stable=True)[1]]
+        scores = packed[:, -1][order].contiguous()
+        boxes = packed[:, :-1][order].contiguous()
+        if host_boxes is not None:
+            # detections given on the host are broken down there, in their own precision, as the reference does
+            det_flag = np.concatenate([fun.breakdown_flags(host_boxes) for fun in self.breakdown], axis=0)
+            det_flag = torch.from_numpy(det_flag.astype(np.uint8)).to(dev)[:, order]
+        else:
+            det_flag = torch.cat([fun.breakdown_flags(boxes) for fun in self.breakdown], dim=0).to(torch.uint8)
+        R = group.shape[1]
+        # Rows land breakdown-major inside the batch, (b, detection), where the per-frame path appends (frame, class, b, rank).
+        # ap_accumulate depends only on the relative order of the rows of ONE group, and under both layouts that order is frame
+        # order, then rank: a group's rows are one breakdown row of one class, and the packed detections are frame-major.
+        rec.reserve(R * ND)
+        _ev.frames_records(boxes, scores, det_seg, torch.from_numpy(np.ascontiguousarray(gt_all, dtype=np.float32)).to(dev), gt_seg,
+                           det_flag.contiguous(), gt_flag, group, np.array(self.matcher.match_thrs, np.float32), mode,
+                           z_offset=getattr(self.affinity_calculator, 'z_offset', 0.5), negate=self.matcher.negate, alias_tp=True,
+                           out=rec.cols, row=rec.rows)
+        rec.rows += R * ND
+        return True
+
     def _group_table(self):
         """Group ids in the reference's tp_score_info order: class-major, NoBreakdown first, breakdowns that do not apply skipped."""
         table, start = [], {}
@@ -357,14 +464,24 @@ class FlexibleStatisticsEval(object):
         res = torch.stack([nd.double(), rc, ap]).cpu().numpy()
         return self._results([(cls, bkd)], [num_gt], res[0], res[1], res[2])
 
-    def statistics_eval(self, det_results, annotations):
+    def statistics_eval(self, det_results, annotations, frame_batch=0):
+        """frame_batch 0 / None: one frame at a time (`_frame_records`); N > 0: N frames per `frames_records` call, the same results."""
         num_thrs = len(self.matcher.match_thrs)
         rec = _Records(_device_of(det_results))
         table, _, group_of = self._group_table()
         num_cls = len(det_results[0]) if len(det_results) else 0
         num_gt = [0] * (num_cls * sum(len(f.names) for f in self.breakdown))
-        for det, anno in zip(det_results, annotations):
-            self._frame_records(det, anno, rec, group_of, num_gt)
+        if not frame_batch:
+            for det, anno in zip(det_results, annotations):
+                self._frame_records(det, anno, rec, group_of, num_gt)
+        else:
+            mode = self._batch_mode()
+            pairs = list(zip(det_results, annotations))
+            for first in range(0, len(pairs), int(frame_batch)):
+                batch = pairs[first:first + int(frame_batch)]
+                if not self._batch_records([d for d, _ in batch], [a for _, a in batch], rec, group_of, num_gt, mode):
+                    for det, anno in batch:
+                        self._frame_records(det, anno, rec, group_of, num_gt)
         if not table:
             return []
         num_gt = num_gt[:len(table)]
@@ -416,7 +533,8 @@ def eval_map_flexible(det_results,
                       report_config=[
                           ('map', lambda x: x['breakdown'] == 'All')
                       ],
-                      nproc=None):
+                      nproc=None,
+                      frame_batch=0):
     assert len(det_results) == len(annotations)
 
     if nproc is None:
@@ -424,7 +542,7 @@ def eval_map_flexible(det_results,
 
     fse = FlexibleStatisticsEval(classes, match_thrs, breakdowns, affinity_calculator, matcher, [], nproc)
 
-    eval_result_list = fse.statistics_eval(det_results, annotations)
+    eval_result_list = fse.statistics_eval(det_results, annotations, frame_batch=frame_batch)
     report = fse.report(eval_result_list, report_config)
 
     table_data = [['Class', 'Breakdown', 'Thres', 'Dets', 'GTs', 'Recall', 'mAP']]

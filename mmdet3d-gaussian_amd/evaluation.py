@@ -6,7 +6,9 @@ flexible mAP above them:
 * ``match_coco`` — ops/eval/matcher.cpp:8-74;
 * ``tp_records`` — core/evaluation/mean_ap_flexible.py:98-126, one matcher result as rows of a record buffer;
 * ``ap_accumulate`` — mean_ap_flexible.py:130-148 with mmdet's average_precision(mode='area'), for every (group, threshold) of
-  the buffer in one call (include/gd3d.h "Flexible mAP").
+  the buffer in one call (include/gd3d.h "Flexible mAP", DESIGN.md §3.27).;
+* ``frames_records`` — mean_ap_flexible.py:37-126 for every (frame, class) problem, breakdown row and threshold of a BATCH of frames in
+  three launches: affinities, matcher and records, the same bits as the three calls above per problem.
 
 The evaluator that drives them with the reference's surface (FlexibleStatisticsEval, the breakdowns, the affinity and matcher
 callables, eval_map_flexible) is eval_map.py.
@@ -113,6 +115,96 @@ def tp_records(matched, det_flag, gt_flag, score, group, num_thrs=None, out=None
         cols.append(c[row:row + D])
     _host.call('eval_tp_records', dev, (_host.ptr(m), df.data_ptr(), _host.ptr_or_null(gf), s.data_ptr(), int(group), D, gf.numel(), T,
                                         cols[0].data_ptr(), cols[1].data_ptr(), cols[2].data_ptr(), cols[3].data_ptr()))
+    return tuple(cols)
+
+
+FRAMES_MODES = {'iou3d': 0, 'ioubev': 1, 'trans': 2}
+FRAMES_MAX_GT = 2048     # gts of one problem; beyond it eval_frames_records answers GD3D_E_TOOLARGE
+
+_frames_workspace_bytes = _host.memo(lambda ND, pairs, R, T: _lib_query('eval_frames_workspace_bytes', ND, pairs, R, T))
+
+
+def _host_table(x, dtype):
+    """A small table whose contents the host knows (segment bounds, groups): a contiguous numpy array."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(x), dtype=dtype)
+
+
+def frames_records(det, score, det_seg, gt, gt_seg, det_flag, gt_flag, group, thrs, mode, z_offset=0.5, negate=None, gt_crowd=None,
+                   alias_tp=True, out=None, row=0):
+    """Every record of a batch of frames in a fixed number of launches (include/gd3d.h "Flexible mAP, a batch of frames").
+
+    A problem is one (frame, class) pair.  Problem p owns rows [det_seg[p], det_seg[p+1]) of det (ND, 7) and score (ND,), already in
+    the problem's rank order, and rows [gt_seg[p], gt_seg[p+1]) of gt (NG, 7).  det_flag (R, ND) / gt_flag (R, NG) bool: the box lies
+    in breakdown row b (ignored gts cleared); group (P, R): the record group of problem p's row b, -1 where the row does not apply;
+    thrs (T,) fp32; mode 'iou3d' (with z_offset) | 'ioubev' | 'trans'; negate (default: True for the two IoUs) hands the matcher
+    -affinity and -thrs; gt_crowd (NG,) bool or None.  det_seg, gt_seg and group are host tables (lists, numpy, CPU tensors).
+
+    Returns the four columns (group int32, score fp32, tp_bits, msk_bits) of R * ND rows, the row of (b, i) at b * ND + i — fresh
+    tensors, or rows [row, row + R * ND) of the four columns given as `out`.  What `tp_records` gives for `match_coco` on the
+    problem's affinity, per problem and row, bit for bit; alias_tp: every applicable row of a problem carries the tp bits of the
+    problem's last applicable row (the reference's one-array aliasing).  CPU tensors take the `_cpu` twin."""
+    d = _dev_tensor(det, torch.float32, 'frames_records', cpu_ok=True)
+    dev = d.device
+    s = _dev_tensor(score, torch.float32, 'frames_records', cpu_ok=True).to(dev).reshape(-1)
+    g = _dev_tensor(gt, torch.float32, 'frames_records', cpu_ok=True).to(dev)
+    df = _dev_tensor(det_flag, torch.uint8, 'frames_records', cpu_ok=True).to(dev)
+    gf = _dev_tensor(gt_flag, torch.uint8, 'frames_records', cpu_ok=True).to(dev)
+    th = _dev_tensor(thrs, torch.float32, 'frames_records', cpu_ok=True).to(dev).reshape(-1)
+    if mode not in FRAMES_MODES:
+        raise RuntimeError(f'frames_records: mode must be one of {sorted(FRAMES_MODES)}, got {mode!r}')
+    dseg, gseg = _host_table(det_seg, np.int64).reshape(-1), _host_table(gt_seg, np.int64).reshape(-1)
+    grp = _host_table(group, np.int32)
+    ND, NG, T = s.numel(), g.shape[0] if g.dim() == 2 else -1, th.numel()
+    P = dseg.size - 1
+    if d.dim() != 2 or d.shape != (ND, 7) or g.dim() != 2 or g.shape[1] != 7:
+        raise RuntimeError(f'frames_records: expected det ({ND}, 7) and gt (NG, 7), got {tuple(d.shape)} and {tuple(g.shape)}')
+    if P < 0 or gseg.size != P + 1 or grp.ndim != 2 or grp.shape[0] != P or grp.shape[1] < 1:
+        raise RuntimeError(f'frames_records: det_seg ({dseg.size},), gt_seg ({gseg.size},) and group {grp.shape} do not describe one set of problems')
+    R = grp.shape[1]
+    D_p, G_p = np.diff(dseg), np.diff(gseg)
+    if dseg[0] != 0 or gseg[0] != 0 or dseg[-1] != ND or gseg[-1] != NG or (D_p < 0).any() or (G_p < 0).any():
+        raise RuntimeError(f'frames_records: the segment tables must ascend from 0 to {ND} detections and {NG} gts')
+    if df.shape != (R, ND) or gf.shape != (R, NG):
+        raise RuntimeError(f'frames_records: flags must be ({R}, {ND}) and ({R}, {NG}), got {tuple(df.shape)} and {tuple(gf.shape)}')
+    if not 1 <= T <= MAX_THRS:
+        raise RuntimeError(f'frames_records: {T} thresholds, expected 1..{MAX_THRS}')
+    crowd = None
+    if gt_crowd is not None:
+        crowd = _dev_tensor(gt_crowd, torch.uint8, 'frames_records', cpu_ok=True).to(dev).reshape(-1)
+        if crowd.numel() != NG:
+            raise RuntimeError(f'frames_records: {NG} gts but {crowd.numel()} crowd flags')
+    pair_off = np.zeros(P + 1, np.int64)
+    np.cumsum(D_p * G_p, out=pair_off[1:])
+    pairs, max_gt = int(pair_off[-1]), int(G_p.max()) if P else 0
+    rows = R * ND
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.float32, device=dev),
+               torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.int32, device=dev))
+        row = 0
+    cols = []
+    for c, dt in zip(out, (torch.int32, torch.float32, torch.int32, torch.int32)):
+        if c.dtype != dt or c.device != dev or c.dim() != 1 or not c.is_contiguous() or row < 0 or row + rows > c.numel():
+            raise RuntimeError(f'frames_records: every column of `out` must be a contiguous 1-D {dt} tensor on {dev} with rows '
+                               f'[{row}, {row + rows})')
+        cols.append(c[row:row + rows])
+    # the small tables: built on the host from shapes, one packed copy per call
+    table = np.concatenate([pair_off.view(np.int32), dseg.astype(np.int32), gseg.astype(np.int32), grp.reshape(-1)])
+    tab = torch.from_numpy(table).to(dev)
+    p_off = tab.data_ptr()                    # int64 words first: 8-byte aligned
+    p_dseg = p_off + 8 * (P + 1)
+    p_gseg = p_dseg + 4 * (P + 1)
+    p_grp = p_gseg + 4 * (P + 1)
+    neg = FRAMES_MODES[mode] != 2 if negate is None else bool(negate)
+    args = (FRAMES_MODES[mode], float(z_offset), int(neg), _host.ptr_or_null(d), _host.ptr_or_null(s), p_dseg, ND, _host.ptr_or_null(g), p_gseg,
+            NG, _host.ptr(crowd), p_off, pairs, max_gt, _host.ptr_or_null(df), _host.ptr_or_null(gf), p_grp, th.data_ptr(), P, R, T,
+            int(bool(alias_tp)), _host.ptr_or_null(cols[0]), _host.ptr_or_null(cols[1]), _host.ptr_or_null(cols[2]), _host.ptr_or_null(cols[3]))
+    if dev.type == 'cuda':
+        ws = torch.empty(_frames_workspace_bytes(ND, pairs, R, T) or 256, dtype=torch.uint8, device=dev)   # the allocator aligns to 512 bytes
+        _host.call('eval_frames_records', dev, args + (ws.data_ptr(),))
+    else:
+        _host.call('eval_frames_records', dev, args, (torch.get_num_threads(),))
     return tuple(cols)
 
 
