@@ -1522,6 +1522,16 @@ int gd3d_sparse_to_dense_backward_cpu(const float* grad_dense, const int32_t* co
  *   are FP32 — master weights receive unrounded gradients.  The operands are widened (their products are exact in fp32) and summed
  *   by gd3d_sparse_conv_backward_weight's two stages in its order; workspace:
  *   gd3d_sparse_conv_backward_weight_workspace_bytes(R, K, Cin, Cout) bytes, 256-byte aligned.
+ * gd3d_sparse_conv_backward_weight_16_mfma (csrc/sparse_conv_wgrad_16.hip) : the same call — arguments, workspace,
+ *   argument checks in the same order with the same codes, empty cases, fp32 outputs — with the per-chunk partial sums X^T gY taken on
+ *   v_mfma_f32_16x16x32_{f16,bf16}: 32 rows a step, each of a workgroup's four waves on its own steps, the waves' sums added in
+ *   ascending wave order, the chunks' in ascending chunk order by the same second stage.  A row without the neighbour at offset j, a
+ *   row at or past num[0] and the channels past Cin / Cout enter as zeros on BOTH operands: a NaN in a row that offset j does not use
+ *   does not reach grad_weight[j].  grad_bias is gd3d_sparse_conv_backward_weight_16's, bit for bit.  grad_weight has another order of
+ *   addition than that entry: it agrees with it to the bound of DESIGN.md §3.29, and bit for bit wherever every partial sum is exact
+ *   in fp32.  No atomics, no host read: the same bits from run to run and under graph replay.  Cin % 8 == 0 with a 16-byte aligned
+ *   `features` (Cout, `grad_out`) takes 16-byte gathers, anything else the element-wise form of the same arithmetic.  Opt-in: nothing
+ *   else calls it, and it has no `_cpu` twin.
  * gd3d_sparse_to_dense_16 / _backward_16 : gd3d_sparse_to_dense and its backward for 2-byte elements of either type (a fill and a
  *   copy: no dtype argument); dense (B, C, D, H, W) and grad_features (N, C) in the features' type.
  * Limits, error codes and the empty cases (R == 0, N == 0) are those of the fp32 entries.
@@ -1538,6 +1548,9 @@ int gd3d_sparse_conv_backward_input_16(const void* grad_out, const void* weight,
 int gd3d_sparse_conv_backward_weight_16(const void* features, const void* grad_out, const int32_t* nbr, const int64_t* num, int64_t N,
                                         int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* workspace,
                                         float* grad_weight, float* grad_bias, void* stream);
+int gd3d_sparse_conv_backward_weight_16_mfma(const void* features, const void* grad_out, const int32_t* nbr, const int64_t* num, int64_t N,
+                                             int64_t R, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* workspace,
+                                             float* grad_weight, float* grad_bias, void* stream);
 int gd3d_sparse_to_dense_16(const void* features, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H, int32_t W,
                             void* dense, void* stream);
 int gd3d_sparse_to_dense_backward_16(const void* grad_dense, const int32_t* coors, int64_t N, int32_t C, int32_t B, int32_t D, int32_t H,

@@ -334,6 +334,7 @@ SYMBOLS = {
     'gd3d_sparse_conv_forward_16': (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     'gd3d_sparse_conv_backward_input_16': (_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     'gd3d_sparse_conv_backward_weight_16': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'gd3d_sparse_conv_backward_weight_16_mfma': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'gd3d_sparse_to_dense_16': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     'gd3d_sparse_to_dense_backward_16': (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     'gd3d_sparse_conv_forward_16_cpu': (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),

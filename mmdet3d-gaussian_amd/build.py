@@ -45,6 +45,7 @@ SOURCES = {   # the SURVEY.md §8 surface: libgd3d.so (include/gd3d.h)
     'sparse_conv.hip': ['-ffp-contract=off'],  # every table of the index build replays bit for bit in sparse_conv_cpu.cpp; explicit fmaf for the values; sorts + scan from device_sort.h
     'sparse_conv_16.hip': ['-ffp-contract=off'],  # the fp16 / bf16 forms on v_mfma_f32_16x16x32: the epilogues' fp32 sequences stay as written
     'sparse_conv_wgrad.hip': ['-ffp-contract=off'],  # the weight and bias gradient, one source for fp32 / fp16 / bf16: explicit fmaf in a fixed order
+    'sparse_conv_wgrad_16.hip': ['-ffp-contract=off'],  # stage one of the 16-bit weight gradient on v_mfma_f32_16x16x32; the wave sums in a fixed order, the rest is sparse_conv_wgrad.hip's
     'sparse_dense.hip': ['-ffp-contract=off'],     # dense() and its backward for 4- and 2-byte elements: copies only, flagged as the rest of the sparse conv
     'sparse_bn.hip': ['-ffp-contract=off'],    # live-row BatchNorm: every multiply-add is an explicit fmaf, the order of every sum is fixed
     'sparse_pool.hip': ['-ffp-contract=off'],  # sparse max pooling: copies and plain fp32 adds in a fixed order replay bit for bit in sparse_pool_cpu.cpp

@@ -7,36 +7,19 @@
 //   bias_kernel   column sums of gY over the chunk's rows that have a neighbour.
 //   wfinish_kernel  adds the chunks' partial sums of both in ascending chunk order.
 // The tables are those of csrc/sparse_conv.hip's index build; weight_parts (csrc/sparse_conv_common.h) cuts the rows into chunks.
-// Compiled with -ffp-contract=off; the multiply-adds are explicit fmaf (the matrix-core form is the open item of DESIGN.md §3.19).
+// Compiled with -ffp-contract=off; the multiply-adds are explicit fmaf.  The matrix-core stage one for fp16 / bf16
+// (gd3d_sparse_conv_backward_weight_16_mfma) is csrc/sparse_conv_wgrad_16.hip: it shares the arguments and the workspace
+// (csrc/sparse_conv_wgrad.h) and runs bias_kernel and wfinish_kernel of this unit through finish_wgrad.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/gd3d.h"
 #include "gd3d_fill.h"
-#include "gd3d_workspace.h"
-#include "sparse_conv_common.h"
+#include "sparse_conv_wgrad.h"
 
 namespace sparse_conv {
 
 constexpr int BLOCK = 256;
-
-struct WgradArgs {
-  const void *X, *gY;       // (n_src, Cin) and (rows, Cout) of E::T
-  const int32_t* nbr;
-  const long long* num;
-  long long n_src, rows, chunk, parts;
-  int K, Cin, Cout, tiles_co;
-  float *part_w, *part_b;   // (parts, K, Cin, Cout) and (parts, Cout)
-  float *gW, *gb;           // gb nullable
-};
-
-// part_w and part_b out of the caller's workspace (256-byte aligned), for the a.parts and a.Cout set.  At address 0 it is the size function.
-static size_t carve(WgradArgs& a, void* workspace, int64_t kcc) {
-  gd3d::Carver c(workspace, gd3d::Carver::CALLER_ALIGNED);
-  a.part_w = c.take<float>((size_t)a.parts * (size_t)kcc);
-  a.part_b = c.take<float>((size_t)a.parts * (size_t)a.Cout);
-  return c.bytes();
-}
 
 // grid (parts, K, tiles of TI x TO of W[j]): the partial sum of chunk p.  TI, TO in {16, 32, 64}: the smallest tiles that hold Cin and
 // Cout; a thread owns TI / 16 x TO / 16 elements.
@@ -168,13 +151,7 @@ __global__ __launch_bounds__(BLOCK) void wfinish_kernel(const WgradArgs a) {
 }
 
 template <class E>
-static int run_wgrad(WgradArgs& a, hipStream_t s) {
-  const int to = tile_of(a.Cout);
-  switch (tile_of(a.Cin)) {
-    case 16: launch_wgrad_in<E, 16>(a, to, s); break;
-    case 32: launch_wgrad_in<E, 32>(a, to, s); break;
-    default: launch_wgrad_in<E, 64>(a, to, s); break;
-  }
+static int run_finish(const WgradArgs& a, hipStream_t s) {
   if (a.gb != nullptr) {
     int cp = 1;
     while (cp < a.Cout) cp <<= 1;                                // <= 256 = BLOCK
@@ -185,6 +162,21 @@ static int run_wgrad(WgradArgs& a, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
+int finish_wgrad(const WgradArgs& a, int32_t dtype, hipStream_t s) {
+  return sparse_elem::with_elem(dtype, [&](auto e) { return run_finish<decltype(e)>(a, s); });
+}
+
+template <class E>
+static int run_wgrad(WgradArgs& a, hipStream_t s) {
+  const int to = tile_of(a.Cout);
+  switch (tile_of(a.Cin)) {
+    case 16: launch_wgrad_in<E, 16>(a, to, s); break;
+    case 32: launch_wgrad_in<E, 32>(a, to, s); break;
+    default: launch_wgrad_in<E, 64>(a, to, s); break;
+  }
+  return run_finish<E>(a, s);
+}
+
 // elem 4: fp32 operands, dtype 0; elem 2: dtype GD3D_DTYPE_F16 / GD3D_DTYPE_BF16
 static int backward_weight(size_t elem, int32_t dtype, const void* features, const void* grad_out, const int32_t* nbr, const int64_t* num,
                            int64_t N, int64_t R, int32_t K, int32_t Cin, int32_t Cout, void* workspace, float* grad_weight, float* grad_bias,
@@ -192,18 +184,9 @@ static int backward_weight(size_t elem, int32_t dtype, const void* features, con
   bool run;
   const int rc = check_wgrad_call(elem, dtype, N, R, K, Cin, Cout, features, grad_out, nbr, workspace, true, grad_weight, &run);
   if (rc != 0) return rc;
-  const int64_t kcc = (int64_t)K * Cin * Cout;
-  if (!run) {                                                    // no pair: the gradients are zeros
-    int e = gd3d::fill_words(grad_weight, sizeof(float) * (size_t)kcc, 0u, s);
-    if (e == 0 && grad_bias != nullptr) e = gd3d::fill_words(grad_bias, sizeof(float) * (size_t)Cout, 0u, s);
-    return e;
-  }
+  if (!run) return zero_wgrad(K, Cin, Cout, grad_weight, grad_bias, s);
   WgradArgs a;
-  a.X = features; a.gY = grad_out; a.nbr = nbr; a.num = (const long long*)num; a.n_src = N; a.rows = R;
-  weight_parts(R, kcc, (int64_t*)&a.parts, (int64_t*)&a.chunk);
-  a.K = K; a.Cin = Cin; a.Cout = Cout; a.tiles_co = 1;
-  carve(a, workspace, kcc);
-  a.gW = grad_weight; a.gb = grad_bias;
+  fill_args(a, features, grad_out, nbr, num, N, R, K, Cin, Cout, workspace, grad_weight, grad_bias);
   return sparse_elem::with_elem(dtype, [&](auto e) { return run_wgrad<decltype(e)>(a, s); });
 }
 

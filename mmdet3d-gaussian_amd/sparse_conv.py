@@ -12,7 +12,8 @@ in fp32 and cast back.  `compute_dtype=torch.float16 / torch.bfloat16 / 'auto'` 
 builder of sparse_encoder.py) selects the mixed-precision form (csrc/sparse_conv_16.hip): 16-bit operands on the matrix cores, fp32
 accumulation, a 16-bit output, fp32 weight and bias gradients.  `scale=, shift=, residual=, activation=` on `sparse_conv`, and
 `FusedSparseConv` as the module, put an eval BatchNorm, a block's residual add and the ReLU into the
-forward launch.  Dilation must be 1.
+forward launch.  `weight_grad='mfma'` (same places; opt-in) takes the 16-bit weight gradient's partial sums on the matrix
+cores too (csrc/sparse_conv_wgrad_16.hip).  Dilation must be 1.
 
 The way back up: `sparse_conv_index` keeps the rows it was built over (`in_coors`, `in_shape`), and
 `sparse_conv_index_inverse` hands the same tables back with the roles swapped, so `sparse_inverse_conv` / `SparseInverseConv3d` (spconv 1.x's
@@ -136,9 +137,23 @@ def _weight3(weight, who):
     return weight.reshape(-1, weight.size(-2), weight.size(-1))
 
 
-def _backward_entries(x, w, gy, nbr, nbr_t, num, subm, need_x, need_w, has_bias, dtype):
+def check_weight_grad(weight_grad, who):
+    if weight_grad is not None and not (isinstance(weight_grad, str) and weight_grad == 'mfma'):
+        raise RuntimeError(f"{who}: weight_grad must be None or 'mfma', got {weight_grad!r}")
+    return weight_grad
+
+
+def _weight_entry(dtype, dev, weight_grad):
+    """the weight-gradient entry of a compute dtype (None: fp32) on a device: the matrix-core form only for 'mfma' on 16-bit operands on the
+    device"""
+    if dtype is None:
+        return 'gd3d_sparse_conv_backward_weight'
+    return 'gd3d_sparse_conv_backward_weight_16' + ('_mfma' if weight_grad == 'mfma' and dev.type == 'cuda' else '')
+
+
+def _backward_entries(x, w, gy, nbr, nbr_t, num, subm, need_x, need_w, has_bias, dtype, weight_grad=None):
     """the backward entries on contiguous operands of the kernels' types (dtype None: fp32) -> (gx, gw, gb) as the kernels wrote them,
-    None where not asked for"""
+    None where not asked for.  weight_grad: None or 'mfma' (`sparse_conv`)"""
     N, (K, Cin, Cout), R, dev = x.size(0), w.shape, nbr.size(0), x.device
     suffix, code = ('', ()) if dtype is None else ('_16', (DTYPE_CODES[dtype],))
     ptr = _host.ptr_or_null
@@ -151,7 +166,7 @@ def _backward_entries(x, w, gy, nbr, nbr_t, num, subm, need_x, need_w, has_bias,
         gw = torch.empty((K, Cin, Cout), dtype=torch.float32, device=dev)              # fp32 also on the 16-bit path: master weights get unrounded gradients
         gb = torch.empty((Cout,), dtype=torch.float32, device=dev) if has_bias else None
         work = _workspace(_weight_workspace_bytes(R, K, Cin, Cout), dev)
-        _host.call('gd3d_sparse_conv_backward_weight' + suffix, dev,
+        _host.call(_weight_entry(dtype, dev, weight_grad), dev,
                    (ptr(x), ptr(gy), ptr(nbr), ptr(num), N, R, K, Cin, Cout, *code, ptr(work), ptr(gw), ptr(gb)))
     return gx, gw, gb
 
@@ -188,7 +203,7 @@ class _SparseConv(torch.autograd.Function):
     constants (a frozen BatchNorm).  The backward is the same entries in every form (`_backward_entries`)."""
 
     @staticmethod
-    def forward(ctx, features, weight, bias, residual, scale, shift, nbr, nbr_t, num, subm, activation, dtype):
+    def forward(ctx, features, weight, bias, residual, scale, shift, nbr, nbr_t, num, subm, activation, dtype, weight_grad=None):
         if dtype is None:
             x, w, code = _host.f32c(features), _host.f32c(weight), ()
         else:
@@ -212,14 +227,14 @@ class _SparseConv(torch.autograd.Function):
                        (ptr(x), ptr(w), ptr(sc), ptr(sh), ptr(res), ptr(nbr), ptr(num), N, R, K, Cin, Cout, ACT_CODES[activation], *code, ptr(out)))
         ctx.save_for_backward(x, w, nbr, nbr_t, num, sc, out if activation == 'relu' else None)
         ctx.state = (subm, bias is not None, features.dtype, weight.dtype, None if bias is None else bias.dtype,
-                     None if residual is None else residual.dtype, weight.shape, dtype)
+                     None if residual is None else residual.dtype, weight.shape, dtype, weight_grad)
         return out if dtype is not None or features.dtype == torch.float32 else out.to(features.dtype)
 
     @staticmethod
     @_host.guard_double_backward
     def backward(ctx, grad_out):
         x, w, nbr, nbr_t, num, sc, out = ctx.saved_tensors
-        subm, has_bias, x_dtype, w_dtype, b_dtype, r_dtype, w_shape, dtype = ctx.state
+        subm, has_bias, x_dtype, w_dtype, b_dtype, r_dtype, w_shape, dtype, weight_grad = ctx.state
         g = grad_out if dtype is not None else _host.f32c(grad_out)
         if out is not None:
             g = g * (out > 0)                                                          # the ReLU's gradient, exact
@@ -227,11 +242,11 @@ class _SparseConv(torch.autograd.Function):
         gy = g if sc is None else g.float() * sc                                       # what reaches the convolution: the existing backward entries run on it
         gy = _host.f32c(gy) if dtype is None else as_dtype(gy, dtype)
         gx, gw, gb = _backward_entries(x, w, gy, nbr, nbr_t, num, subm, ctx.needs_input_grad[0],
-                                       ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]), has_bias, dtype)
+                                       ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]), has_bias, dtype, weight_grad)
         gx = None if gx is None else gx.to(x_dtype)
         gw = None if gw is None else gw.to(w_dtype).reshape(w_shape)
         gb = None if gb is None else gb.to(b_dtype)
-        return gx, gw, gb, gres, None, None, None, None, None, None, None, None
+        return gx, gw, gb, gres, None, None, None, None, None, None, None, None, None
 
 
 def _check_fused_operands(scale, shift, residual, activation, features, Cout, R):
@@ -253,7 +268,7 @@ def _check_fused_operands(scale, shift, residual, activation, features, Cout, R)
             raise RuntimeError(f'sparse_conv: residual is on {residual.device}, features on {features.device}')
 
 
-def sparse_conv(features, weight, bias, index, compute_dtype=None, *, scale=None, shift=None, residual=None, activation=None):
+def sparse_conv(features, weight, bias, index, compute_dtype=None, *, scale=None, shift=None, residual=None, activation=None, weight_grad=None):
     """One sparse convolution layer over the tables of `sparse_conv_index` -> (R, Cout), differentiable w.r.t. features, weight, bias.
 
     out[o] = sum over the offsets j with index.nbr[o, j] >= 0 of features[nbr[o, j]] @ weight[j] (+ bias); weight is spconv 1.x's
@@ -274,7 +289,15 @@ def sparse_conv(features, weight, bias, index, compute_dtype=None, *, scale=None
     requires grad raises.  residual: (R, Cout), the identity of a basic block.  activation: None or 'relu'.  The conv's own bias is folded on
     the host, shift' = bias * scale + shift, and each output element is one fixed fp32 sequence — fmaf(acc, scale, shift'), + residual, the
     ReLU — rounded once on the 16-bit path.  Differentiable w.r.t. features, weight, bias and residual: g = grad_out * (out > 0) under the
-    ReLU, grad_residual = g, and the backward launches above run on g * scale.  With all four None the call is the one it always was."""
+    ReLU, grad_residual = g, and the backward launches above run on g * scale.  With all four None the call is the one it always was.
+
+    weight_grad (keyword-only): None — the weight and bias gradients as they always were, entry for entry.  'mfma': on the
+    device, where the resolved compute dtype is torch.float16 / torch.bfloat16, the backward takes the per-chunk partial sums of the weight
+    gradient on the matrix cores (gd3d_sparse_conv_backward_weight_16_mfma): the same chunks, workspace, fp32 outputs and bias gradient,
+    another order of addition inside a chunk, the same bits from run to run.  It is inert where the resolved compute dtype is None (fp32),
+    and inert on CPU tensors, where the `_cpu` twin of the default entry runs: a network can carry the switch through 'auto' and through
+    CPU runs.  Anything else raises."""
+    check_weight_grad(weight_grad, 'sparse_conv')
     if not isinstance(index, SparseConvIndex):
         raise RuntimeError('sparse_conv: index must be the record sparse_conv_index returns')
     w = _weight3(weight, 'sparse_conv')
@@ -294,10 +317,12 @@ def sparse_conv(features, weight, bias, index, compute_dtype=None, *, scale=None
     dtype = _resolve_compute_dtype(compute_dtype, features)
     if scale is not None or shift is not None or residual is not None or activation is not None:
         _check_fused_operands(scale, shift, residual, activation, features, Cout, index.nbr.size(0))
-    return _SparseConv.apply(features, w, bias, residual, scale, shift, index.nbr, index.nbr_t, index.num, index.subm, activation, dtype)
+    return _SparseConv.apply(features, w, bias, residual, scale, shift, index.nbr, index.nbr_t, index.num, index.subm, activation, dtype,
+                             weight_grad)
 
 
-def sparse_inverse_conv(features, weight, bias, index, compute_dtype=None, *, scale=None, shift=None, residual=None, activation=None):
+def sparse_inverse_conv(features, weight, bias, index, compute_dtype=None, *, scale=None, shift=None, residual=None, activation=None,
+                        weight_grad=None):
     """spconv 1.x's inverse convolution over the tables of the FORWARD layer's `index` (a strided `sparse_conv_index`) -> (N, Cout):
     `sparse_conv` over `sparse_conv_index_inverse(index)` — the same launches, forward and backward, the 16-bit and the fused forms included.
 
@@ -306,16 +331,17 @@ def sparse_inverse_conv(features, weight, bias, index, compute_dtype=None, *, sc
     forward layer.  It equals the dense `conv_transpose3d` of the densified features read at the forward layer's input sites.
     The rule for a row without a valid neighbour holds: that row is ZERO, bias or not — an inactive input row, an active input that no
     output cell reaches (a stride above the kernel, a truncated edge), an input whose outputs were all dropped by `max_out`.  spconv writes
-    the bias to such a row; mmdet3d builds these layers without bias, where the two agree."""
+    the bias to such a row; mmdet3d builds these layers without bias, where the two agree.  weight_grad: as in `sparse_conv`."""
     return sparse_conv(features, weight, bias, sparse_conv_index_inverse(index), compute_dtype, scale=scale, shift=shift, residual=residual,
-                       activation=activation)
+                       activation=activation, weight_grad=weight_grad)
 
 
 class SparseConvolution(SparseModule):
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, subm=False, indice_key=None,
-                 max_out=None, *, compute_dtype=None):
+                 max_out=None, *, compute_dtype=None, weight_grad=None):
         super().__init__()
         self.compute_dtype = check_compute_dtype(compute_dtype, type(self).__name__)     # None, torch.float16, torch.bfloat16 or 'auto': `sparse_conv`
+        self.weight_grad = check_weight_grad(weight_grad, type(self).__name__)           # None or 'mfma': `sparse_conv`; an attribute, not a buffer
         if triple(dilation, 'dilation') != (1, 1, 1):
             raise RuntimeError(f'{type(self).__name__}: dilation must be 1, got {dilation}')
         self.in_channels, self.out_channels = int(in_channels), int(out_channels)
@@ -365,28 +391,31 @@ class SparseConvolution(SparseModule):
 
     def forward(self, x):
         index = self.index_of(x)
-        return self.output_of(x, index, sparse_conv(x.features, self.weight, self.bias, index, self.compute_dtype))
+        return self.output_of(x, index, sparse_conv(x.features, self.weight, self.bias, index, self.compute_dtype, weight_grad=self.weight_grad))
 
     def extra_repr(self):
         return (f'{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, '
                 f'bias={self.bias is not None}, indice_key={self.indice_key!r}'
-                + ('' if self.compute_dtype is None else f', compute_dtype={self.compute_dtype!r}'))
+                + ('' if self.compute_dtype is None else f', compute_dtype={self.compute_dtype!r}')
+                + ('' if self.weight_grad is None else f', weight_grad={self.weight_grad!r}'))
 
 
 class SubMConv3d(SparseConvolution):
     """spconv 1.x's submanifold convolution: the outputs are the inputs.  `stride` and `padding` are accepted and not used (k // 2)."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, indice_key=None, *, compute_dtype=None):
-        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, bias, True, indice_key, compute_dtype=compute_dtype)
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, indice_key=None, *, compute_dtype=None,
+                 weight_grad=None):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, bias, True, indice_key, compute_dtype=compute_dtype,
+                         weight_grad=weight_grad)
 
 
 class SparseConv3d(SparseConvolution):
     """spconv 1.x's regular sparse convolution.  max_out (an addition): an int gives the static form of `sparse_conv_index`."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=True, indice_key=None, max_out=None, *,
-                 compute_dtype=None):
+                 compute_dtype=None, weight_grad=None):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, bias, False, indice_key, max_out,
-                         compute_dtype=compute_dtype)
+                         compute_dtype=compute_dtype, weight_grad=weight_grad)
 
 
 class SparseInverseConv3d(SparseConvolution):
@@ -395,8 +424,9 @@ class SparseInverseConv3d(SparseConvolution):
     (`sparse_inverse_conv`).  Builds nothing and leaves `indice_dict` as it was; a missing key raises.  A row without a valid neighbour is
     zero, bias or not (spconv writes the bias there)."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, indice_key, bias=True, *, compute_dtype=None):
-        super().__init__(in_channels, out_channels, kernel_size, 1, 0, 1, bias, False, indice_key, compute_dtype=compute_dtype)
+    def __init__(self, in_channels, out_channels, kernel_size, indice_key, bias=True, *, compute_dtype=None, weight_grad=None):
+        super().__init__(in_channels, out_channels, kernel_size, 1, 0, 1, bias, False, indice_key, compute_dtype=compute_dtype,
+                         weight_grad=weight_grad)
 
     def build_index(self, x):
         raise RuntimeError(f'{type(self).__name__} builds no index: it needs the one a SparseConv3d stored under indice_key {self.indice_key!r}')
@@ -419,7 +449,8 @@ class SparseInverseConv3d(SparseConvolution):
 
     def extra_repr(self):
         return (f'{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, bias={self.bias is not None}, '
-                f'indice_key={self.indice_key!r}' + ('' if self.compute_dtype is None else f', compute_dtype={self.compute_dtype!r}'))
+                f'indice_key={self.indice_key!r}' + ('' if self.compute_dtype is None else f', compute_dtype={self.compute_dtype!r}')
+                + ('' if self.weight_grad is None else f', weight_grad={self.weight_grad!r}'))
 
 
 # ---- conv + BatchNorm + residual + ReLU in one launch ----------------------------------------------------------------
@@ -442,7 +473,7 @@ def _fold_batchnorm(bn):
 class FusedSparseConv(SparseModule):
     """A `SubMConv3d` / `SparseConv3d` with the eval BatchNorm1d and / or the ReLU that followed it, evaluated in ONE launch
     (`sparse_conv(..., scale, shift, residual, activation)`).  `conv` is the layer itself: its parameters, `indice_key`, `max_out` and
-    `compute_dtype` are shared, not copied.  scale, shift: fp32 buffers (None without a BatchNorm).  forward(x, residual=None)."""
+    `compute_dtype` and `weight_grad` are shared, not copied.  scale, shift: fp32 buffers (None without a BatchNorm).  forward(x, residual=None)."""
 
     def __init__(self, conv, norm=None, activation=None):
         super().__init__()
@@ -460,13 +491,15 @@ class FusedSparseConv(SparseModule):
     indice_key = property(lambda self: self.conv.indice_key)
     max_out = property(lambda self: self.conv.max_out)
     compute_dtype = property(lambda self: self.conv.compute_dtype)
+    weight_grad = property(lambda self: self.conv.weight_grad)
 
     def forward(self, x, residual=None):
         conv = self.conv
         index = conv.index_of(x)
         return conv.output_of(x, index, sparse_conv(x.features, conv.weight, conv.bias, index, conv.compute_dtype, scale=self.scale, shift=self.shift,
-                                                    residual=residual, activation=self.activation))
+                                                    residual=residual, activation=self.activation, weight_grad=conv.weight_grad))
 
     def extra_repr(self):
         return (f'norm={self.scale is not None}, activation={self.activation!r}, indice_key={self.indice_key!r}, max_out={self.max_out!r}'
-                + ('' if self.compute_dtype is None else f', compute_dtype={self.compute_dtype!r}'))
+                + ('' if self.compute_dtype is None else f', compute_dtype={self.compute_dtype!r}')
+                + ('' if self.weight_grad is None else f', weight_grad={self.weight_grad!r}'))

@@ -10,7 +10,8 @@ import torch
 from torch import nn
 
 from .sparse_bn import SparseBatchNorm1d
-from .sparse_conv import FusedSparseConv, SparseConv3d, SparseConvolution, SparseInverseConv3d, SubMConv3d, check_compute_dtype
+from .sparse_conv import (FusedSparseConv, SparseConv3d, SparseConvolution, SparseInverseConv3d, SubMConv3d, check_compute_dtype,
+                          check_weight_grad)
 from .sparse_tensor import SparseConvTensor, SparseModule, SparseSequential
 
 
@@ -193,6 +194,17 @@ def fuse_sparse_conv_bn(module):
     return module
 
 
+def set_weight_grad(module, mode):
+    """Sets `weight_grad` (None or 'mfma': `sparse_conv`) on every `SparseConvolution` under `module`, in place, and returns
+    the module.  The switch is an attribute of the conv, read at every forward, never a buffer or a parameter: `state_dict` is unchanged, and
+    it works before or after `convert_sparse_batchnorm` / `fuse_sparse_conv_bn`, whose modules share the conv itself."""
+    check_weight_grad(mode, 'set_weight_grad')
+    for m in module.modules():
+        if isinstance(m, SparseConvolution):
+            m.weight_grad = mode
+    return module
+
+
 class SparseEncoder(nn.Module):
     """mmdet3d 0.x's `SparseEncoder`, restated from its published sparse_encoder.py (absent from the reference tree: not pinned):
     CenterPoint's `pts_middle_encoder` (configs/_base_/models/centerpoint_01voxel_second_secfpn_nus.py:10-19).  forward returns
@@ -264,6 +276,11 @@ class SparseEncoder(nn.Module):
         """`convert_sparse_batchnorm` on this encoder (opt-in, in place): every BatchNorm1d (+ ReLU) and every basic block on the live-row
         `SparseBatchNorm1d` — what training in the static form needs; `.eval().fuse()` still works afterwards"""
         return convert_sparse_batchnorm(self)
+
+    def set_weight_grad(self, mode):
+        """`set_weight_grad` on this encoder (opt-in, in place): 'mfma' takes the weight gradient of every conv on the matrix cores where it
+        runs in fp16 / bf16 on the device (inert in fp32 and on CPU tensors); None is the default again"""
+        return set_weight_grad(self, mode)
 
 
 class MlvlSparseEncoder(SparseEncoder):
